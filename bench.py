@@ -21,6 +21,11 @@ Prints ONE JSON line (rank 0).  `value` = cell-updates/s of the whole job;
 on the launch stream) against the 8 TB/s HBM3E peak; `cpu_baseline` = the
 reference Fortran executable itself (oracle/_ref, built from /root/reference
 by oracle/build_ref.py) timed on this box's host, 1 core, ncrms=4096.
+
+A plain run does only what the headline needs: set-up, wake-up and warm-up,
+the K timed steps, the line.  --full adds everything else (measured ceilings,
+layout conversion times, the per-launch spread, the side blocks, the CPU
+baselines); --dump-outputs DIR writes what the last timed step computed.
 """
 import argparse
 import json
@@ -93,6 +98,16 @@ def parse():
                     help="the headline block and the cpu_baseline only: no side block runs")
     ap.add_argument("--layout", choices=["wavemajor", "reference"], default="wavemajor",
                     help="device layout of the plans the headline runs on (include/mpdata_hip.h section 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline as well: the measured copy / stream ceilings, the layout "
+                         "conversion times, the per-launch spread of the headline, every side block and the CPU "
+                         "baselines (the --no-* switches and --headline-only select among them).  Without it a run "
+                         "sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- f and flux of its field "
+                         "set, reference layout (reversed-axes torch order, tracer axis first if --tracers > 1), in the "
+                         "headline's precision -- as DIR/f.npy and DIR/flux.npy.  Larger than 48 MB: a fixed, seeded "
+                         "sample of the CRM instances (last axis), the same one in every run.  N > 1: rank 0's shard")
     return ap.parse_args()
 
 
@@ -506,12 +521,15 @@ def wake_up(torch, prewarm_launch, cap_ms, min_ms):
     return info
 
 
-def timed_loop(torch, dist_mod, world, launch, steps, warmup, prewarm_launch=None, collective=True):
+def timed_loop(torch, dist_mod, world, launch, steps, warmup, prewarm_launch=None, collective=True, spread=True,
+               on_timed_end=None):
     """W untimed warm-up steps, then EXACTLY `steps` timed steps bracketed by barrier +
     synchronize, with ONE pair of HIP events on the launch stream around the K launches (kernel
     time per step = elapsed / K: the kernels run back to back, nothing else is on the stream; an
     event pair per step would put two marker packets between any two kernels and is kept out of
-    the timed region).  A second, untimed pass with an event pair per step gives the spread.
+    the timed region).  on_timed_end() runs right after the timed region, before anything else
+    touches the field sets.  spread: a second, untimed pass with an event pair per step gives the
+    spread (off: no samples).
     Returns (max-over-ranks wall seconds, [mean kernel ms per step] + per-step samples).
 
     collective = False (every side block): NO barrier and no all-reduce in here -- the rank times
@@ -546,8 +564,10 @@ def timed_loop(torch, dist_mod, world, launch, steps, warmup, prewarm_launch=Non
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     k_avg = e0.elapsed_time(e1) / steps
+    if on_timed_end is not None:
+        on_timed_end()
     # spread: the same launches once more, one event pair each (not timed, not part of `value`)
-    ns = min(steps, 20)
+    ns = min(steps, 20) if spread else 0
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(ns)]
     for i in range(ns):
         ev[i][0].record()
@@ -602,17 +622,18 @@ class PlanSets:
     barrier of the timed loop."""
 
     def __init__(self, M, torch, dev, shared, shape_f, n_loc, n_glob, sl0, nx, nz, ntr, steps, warmup,
-                 dist_law, np_dtype, tdt, mem_frac=0.55, shared_uw=False):
+                 dist_law, np_dtype, tdt, mem_frac=0.55, shared_uw=False, conversion=True):
+        """conversion: also time the layout entry / exit on the first set (info["conversion"])"""
         self.plans = []
         try:
             self._setup(M, torch, dev, shared, shape_f, n_loc, n_glob, sl0, nx, nz, ntr, steps, warmup, dist_law,
-                        np_dtype, tdt, mem_frac, shared_uw)
+                        np_dtype, tdt, mem_frac, shared_uw, conversion)
         except BaseException:
             self.close(torch)
             raise
 
     def _setup(self, M, torch, dev, shared, shape_f, n_loc, n_glob, sl0, nx, nz, ntr, steps, warmup, dist_law,
-               np_dtype, tdt, mem_frac, shared_uw):
+               np_dtype, tdt, mem_frac, shared_uw, conversion):
         eb = 8 if tdt == torch.float64 else 4
         f_bytes = n_loc * (nx + 6) * (nz - 1) * eb * ntr
         uw_bytes = n_loc * ((nx + 5) * (nz - 1) + (nx + 4) * nz) * eb
@@ -643,14 +664,14 @@ class PlanSets:
                 pl.set_timing(False)   # (timed_loop brackets the K launches with ONE event pair)
                 for k in tmp:
                     M.fill_synthetic(tmp[k], k, 100 + 7919 * (sset + 1), dist_law, ncrms_global=n_glob, sl0=sl0)
-                if sset == 0:   # layout-entry cost, measured on its own (no fill inside): u + w, then one tracer of f
+                if sset == 0 and conversion:   # layout-entry cost, measured on its own (no fill inside): u + w, then one tracer of f
                     pl.import_device(None, tmp["u"], tmp["w"], tmp["rho"], tmp["rhow"], tmp["adz"], None)
                     conv["import_ms_u_and_w"] = _ev_ms(torch, lambda: pl.import_device(None, tmp["u"], tmp["w"]), 3)
                 pl.import_device(None, tmp["u"], tmp["w"], tmp["rho"], tmp["rhow"], tmp["adz"], None)
                 for t in range(ntr):
                     M.fill_synthetic(ftmp, "f", 100 + sset * ntr + t, dist_law, ncrms_global=n_glob, sl0=sl0)
                     pl.import_device(ftmp, flux=shared["flux"], first_tracer=t)
-                if sset == 0:
+                if sset == 0 and conversion:
                     conv["import_ms_f_per_tracer"] = _ev_ms(torch, lambda: pl.import_device(ftmp, first_tracer=ntr - 1), 3)
                     conv["export_ms_f_per_tracer"] = _ev_ms(torch, lambda: pl.export_device(ftmp, first_tracer=ntr - 1), 3)
                     conv["bytes_per_array"] = int(ftmp.numel() * eb)
@@ -662,6 +683,7 @@ class PlanSets:
         nscr = min(max(warmup, 1), N_SCRATCH, nset - 1)
         ntimed = nset - nscr
         self.run, self.nset, self.nscr, self.ntimed = run, nset, nscr, ntimed
+        self.ntr, self.shared_uw = ntr, shared_uw
         self.info = {"layout": "wave-major (plan-private)" if plans[0].layout == M.LAYOUT_WAVEMAJOR else "reference",
                      "field_sets": ntimed, "steps_per_field_set": -(-steps // ntimed),
                      "uw_shared_across_steps": bool(shared_uw), "conversion": conv}
@@ -669,6 +691,18 @@ class PlanSets:
     def launch(self, i):
         """i >= 0: timed step i on field set i mod ntimed; i < 0: warm-up step on the scratch sets"""
         self.run((self.nset - 1 - ((-1 - i) % self.nscr)) if i < 0 else (i % self.ntimed))
+
+    def export_step(self, i, torch, shape_f, shape_flux, tdt, dev):
+        """f and flux of the field set that timed step i ran on, as reference-layout device tensors
+        ([ntr,] shape_f) and ([ntr,] shape_flux)"""
+        s = i % self.ntimed
+        plan, t0 = (self.plans[0], s * self.ntr) if self.shared_uw else (self.plans[s], 0)
+        f = torch.empty((self.ntr,) + tuple(shape_f), dtype=tdt, device=dev)
+        flux = torch.empty((self.ntr,) + tuple(shape_flux), dtype=tdt, device=dev)
+        for t in range(self.ntr):
+            plan.export_device(f[t], flux[t], first_tracer=t0 + t)
+        torch.cuda.synchronize()
+        return (f[0], flux[0]) if self.ntr == 1 else (f, flux)
 
     def prewarm(self, n):
         """GPU wake-up launch number n: CYCLES through the scratch sets, so that consecutive wake-up
@@ -760,11 +794,12 @@ def roofline_block(alg_bytes, kms, extra=None, full=False):
     k_avg = kavg(kms)
     ach = alg_bytes / (k_avg * 1e-3) / 1e9
     r = {"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-         "traffic": None, "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms_avg": k_avg,
-         "kernel_ms_min": min(kms), "kernel_ms_median": statistics.median(kms),
-         "avg_over_median": k_avg / statistics.median(kms)}
+         "traffic": None, "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms_avg": k_avg}
+    if len(kms):   # (no per-launch samples: a plain run skips the spread pass)
+        r.update(kernel_ms_min=min(kms), kernel_ms_median=statistics.median(kms),
+                 avg_over_median=k_avg / statistics.median(kms))
     wake = getattr(kms, "wake", None)
-    if full:
+    if full and len(kms):
         r["kernel_ms_note"] = "HIP events around the K timed launches / K; min / median / samples: event pair per launch, separate pass"
         r["kernel_ms_samples"] = [round(x, 4) for x in kms]
         if wake is not None:
@@ -919,7 +954,7 @@ def main():
     sets, err = None, None
     try:
         sets = PlanSets(M, torch, dev, shared, sh_f1, n_loc, n_glob, sl0, nx, nz, ntr, steps, warmup, args.dist, npdt,
-                        tdt, mem_frac, shared_uw=args.shared_uw)
+                        tdt, mem_frac, shared_uw=args.shared_uw, conversion=args.full)
     except Exception as exc:
         err = repr(exc)
     if agree(err is not None)[0]:
@@ -927,8 +962,13 @@ def main():
               "error": "headline setup failed: " + (err or "on another rank")}, code=1)
         return
     # phase 2: W warm-up + K timed steps, barrier + synchronize on both sides, max over ranks
+    def dump():   # --dump-outputs: what the last timed step computed, before anything else runs on its field set
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(np, torch, sets, steps - 1, sh_f1, sh["flux"], tdt, dev, args.dump_outputs)
+
     try:
-        dt, kms = timed_loop(torch, dist, world, sets.launch, steps, warmup, prewarm_launch=sets.prewarm, collective=True)
+        dt, kms = timed_loop(torch, dist, world, sets.launch, steps, warmup, prewarm_launch=sets.prewarm, collective=True,
+                             spread=args.full, on_timed_end=dump)
         info = sets.info
     finally:
         sets.close(torch)
@@ -972,11 +1012,12 @@ def main():
                 "traffic_source": None if traffic is None else "profiles/hbm_traffic.json[%s]: PMC passes of "
                                   "tools/profile_round.sh on the builder's box, not measured in this run" % key,
                 "cell_updates_per_sec_kernel": n_loc * nx * (nz - 1) * ntr / (kavg(kms) * 1e-3)}),
-            "layout_conversion": dict(info["conversion"], note=
-                                      "reference layout <-> plan layout on the device (HIP events, no fill inside), "
-                                      "outside the timed region of the headline like the reference's `!$acc update "
-                                      "device`, :107; `step_with_fresh_uw` charges it"),
         }
+        if args.full:
+            result["layout_conversion"] = dict(info["conversion"], note=
+                                               "reference layout <-> plan layout on the device (HIP events, no fill "
+                                               "inside), outside the timed region of the headline like the reference's "
+                                               "`!$acc update device`, :107; `step_with_fresh_uw` charges it")
         # the headline exists: on stderr at once (a later block that takes the process down cannot lose it);
         # stdout gets the ONE full line at the end
         print("BENCH_HEADLINE " + json.dumps(result), file=sys.stderr, flush=True)
@@ -987,7 +1028,7 @@ def main():
     #      exception on any rank becomes {"error": ...} under the block's name; every rank then meets in the
     #      one all-reduce of side() and goes on to the next block.
     def side(name, body, rank0_only=False):
-        if args.headline_only:
+        if args.headline_only or not args.full:
             return
         failed, dt_loc, entry, msg = False, 0.0, None, None
         CURRENT_BLOCK[0] = name
@@ -1312,7 +1353,7 @@ def main():
         return 0.0, lambda dtm: r
 
     try:
-        if rank == 0 and not args.headline_only:
+        if rank == 0 and args.full and not args.headline_only:
             ceilings()
         one = ntr == 1
         if not args.no_shared_block and not args.shared_uw and one:
@@ -1340,7 +1381,7 @@ def main():
             side("high_order_flux", b_nlk, rank0_only=True)
         if world > 1 and not args.no_scatter:
             side("scatter_gather", b_scatter)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 result["cpu_baseline"] = cpu_baseline(nx, nz)
             except Exception as exc:
@@ -1353,6 +1394,26 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         life.disarm()
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: at most this much (a seeded sample of the instances beyond it)
+DUMP_SEED = 20240101
+
+
+def dump_outputs(np, torch, sets, step, shape_f, shape_flux, tdt, dev, outdir):
+    """f.npy, flux.npy of timed step `step`: every CRM instance, or a fixed seeded sample of them (sorted, last
+    axis) when the whole arrays exceed DUMP_BYTES; float64 / float32 as the headline's precision"""
+    f, flux = sets.export_step(step, torch, shape_f, shape_flux, tdt, dev)
+    n = f.shape[-1]
+    per_instance = (f.numel() + flux.numel()) // n * f.element_size()
+    k = min(n, max(1, DUMP_BYTES // per_instance))
+    if k < n:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+        sel = torch.from_numpy(idx).to(dev)
+        f, flux = f.index_select(f.dim() - 1, sel), flux.index_select(flux.dim() - 1, sel)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "f.npy"), f.cpu().numpy())
+    np.save(os.path.join(outdir, "flux.npy"), flux.cpu().numpy())
 
 
 def bench_scatter_gather(M, torch, dist, world, rank, dev, n_loc, nx, nz):

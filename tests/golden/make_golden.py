@@ -49,6 +49,29 @@ CASES_F32 = [
 ]
 
 
+NLK_SAMPLE_EDGES, NLK_SAMPLE_SEED = 16, 7
+
+
+def nlk_edge_sample(inp, ref, nedges, seed):
+    """A fixed, seeded sample of the edges of one reference run of the third mini-app: the edges' own
+    arrays, the cells they gather (renumbered 1..n in ascending order of their original numbers) and
+    the edges' refFlx columns.  An edge's flux depends on nothing else, so the oracle on the sample
+    reproduces those columns."""
+    edges = np.sort(np.random.default_rng(seed).choice(ref.shape[1], nedges, replace=False))
+    adv = inp["advCellsForEdge"][:, edges]
+    cells = np.unique(np.concatenate([adv[:n, j] for j, n in enumerate(inp["nAdvCellsForEdge"][edges])]))
+    renum = np.zeros(inp["tracerCur"].shape[1] + 1, np.int32)
+    renum[cells] = np.arange(1, len(cells) + 1, dtype=np.int32)
+    out = {"nAdvCellsForEdge": inp["nAdvCellsForEdge"][edges], "advCellsForEdge": renum[adv],
+           "minLevelCell": inp["minLevelCell"][cells - 1], "maxLevelCell": inp["maxLevelCell"][cells - 1],
+           "tracerCur": inp["tracerCur"][:, cells - 1]}
+    for k in ("normalThicknessFlux", "advMaskHighOrder", "advCoefs", "advCoefs3rd"):
+        out[k] = inp[k][:, edges]
+    out = {k: np.asfortranarray(v) for k, v in out.items()}
+    out.update(coef3rdOrder=inp["coef3rdOrder"], nVertLevels=inp["nVertLevels"], edges=edges, cells=cells)
+    return out, np.asfortranarray(ref[:, edges])
+
+
 def case_name(ncrms, nx, nz, seed, dist, f32=False):
     return f"ref_{ncrms}x{nx}x{nz}_seed{seed}_dist{dist}" + ("_f32" if f32 else "")
 
@@ -83,7 +106,7 @@ def main():
     # element in full, the shipped size (16 elements) as a sha256.
     manifest["bwk"] = {"reference": "atmosphere/biharmonic_wk_kernel.F90 (biharmonic_wk_scalar CPU, :186-200; "
                                     "inputs: initialize_data :48-58)", "cases": []}
-    for nelemd, keep in ((1, True), (16, False)):
+    for nelemd, keep in ((1, True), (2, False), (16, False)):
         build_ref.build_bwk(nelemd)
         inp, out, _ = B.run_reference(nelemd)
         name = f"bwk_ref_ne{nelemd}"
@@ -109,6 +132,15 @@ def main():
             "name": name, "nEdges": shape[0], "nCells": shape[1], "nVertLevels": shape[2], "nAdv": shape[3],
             "seed": seed, "stored": keep, "refFlx_sha256": hashlib.sha256(ref.tobytes(order="F")).hexdigest()})
         print(name, ref.shape)
+        if name == "nlk_ref_nml":   # the shipped size is too large to store: a seeded sample of its edges
+            sname = name + "_sample"
+            sinp, sref = nlk_edge_sample(inp, ref, NLK_SAMPLE_EDGES, NLK_SAMPLE_SEED)
+            np.savez(os.path.join(HERE, sname + ".npz"), refFlx=sref, **sinp)
+            manifest["nlk"]["cases"].append({
+                "name": sname, "of": name, "nEdges": NLK_SAMPLE_EDGES, "nCells": int(sinp["tracerCur"].shape[1]),
+                "sample_seed": NLK_SAMPLE_SEED, "stored": True,
+                "refFlx_sha256": hashlib.sha256(sref.tobytes(order="F")).hexdigest()})
+            print(sname, sref.shape)
     with open(os.path.join(HERE, "manifest.json"), "w") as fh:
         json.dump(manifest, fh, indent=1)
 

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_live_line_meets_the_contract():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "4", "--warmup", "2",
            "--prewarm-ms", "60", "--prewarm-min-ms", "10", "--ncrms-per-gpu", "8192", "--batched-tracers", "3", "--batched-steps", "2",
            "--no-fp32", "--no-bwk", "--no-host-call"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)

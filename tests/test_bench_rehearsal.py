@@ -29,7 +29,7 @@ def _two_ranks(extra_env=None, extra_args=(), rc0=True, launcher=False):
             port = sk.getsockname()[1]
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    cmd += [os.path.join(ROOT, "bench.py"),
+    cmd += [os.path.join(ROOT, "bench.py"), "--full",
             "--gpus", "2", "--steps", "3", "--warmup", "1", "--prewarm-ms", "0", "--ncrms-per-gpu", "4096",
             "--batched-tracers", "3", "--batched-steps", "2", "--no-fp32", "--no-bwk", "--no-exact", "--no-cpu-baseline", *extra_args]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)

@@ -207,7 +207,7 @@ def test_bench_on_two_real_gpus_with_the_plain_command():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MPDATA_BENCH_REHEARSAL"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "5", "--warmup", "2",
                           "--ncrms-per-gpu", "16384", "--batched-tracers", "3", "--batched-steps", "2", "--no-fp32",
                           "--no-bwk", "--no-x2", "--no-shared-block", "--no-exact", "--block-timeout", "120"],
                          env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)

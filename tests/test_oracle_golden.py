@@ -46,11 +46,14 @@ def test_fp32_oracle_matches_fp32_reference_golden_bitwise(oracle, case):
 
 @pytest.mark.parametrize("case", golden_cases()[:5], ids=lambda c: c["name"])
 def test_reference_binary_still_agrees(oracle, case):
-    """When oracle/_ref holds the reference executable for a shape, run it."""
-    if oracle.ref_exe(case["ncrms"], case["nx"], case["nz"]) is None:
-        pytest.skip("no oracle/_ref binary for this shape")
+    """When oracle/_ref holds the reference executable for a shape, run it; without it, the reference's
+    output for the case as stored under tests/golden/."""
     inp = oracle.make_inputs(case["ncrms"], case["nx"], case["nz"], seed=case["seed"], dist=case["dist"])
-    f_ref, flux_ref, _ = oracle.run_reference(inp)
+    if oracle.ref_exe(case["ncrms"], case["nx"], case["nz"]) is not None:
+        f_ref, flux_ref, _ = oracle.run_reference(inp)
+    else:
+        f_ref, flux_ref = load_golden(case)
+        assert hashlib.sha256(flux_ref.tobytes(order="F")).hexdigest() == case["flux_sha256"]
     f, flux = oracle.advect(inp)
     assert np.array_equal(f, f_ref) and np.array_equal(flux, flux_ref)
 

@@ -1,6 +1,6 @@
 # usage: bash tools/ab_ref.sh suffixA suffixB ...   ("-" = default library)
 # interleaved bench.py runs, reference-layout device call block only (x-march kernel)
-F="--steps 40 --warmup 10 --no-cpu-baseline --no-fp32 --no-bwk --no-host-call --no-shared-block --no-fresh-uw --no-x2 --no-batched"
+F="--full --steps 40 --warmup 10 --no-cpu-baseline --no-fp32 --no-bwk --no-host-call --no-shared-block --no-fresh-uw --no-x2 --no-batched"
 for i in 1 2 3; do for v in "$@"; do
   s=$v; [ "$s" = "-" ] && s=""
   echo "== lib$v $i"

@@ -1,7 +1,7 @@
 # 25 tracers, COLD protocol of bench.py (a plan per field set), interleaved: odd tracer inside the batch launch (default)
 # against a launch of its own behind it (MPDATA_WM_SPLIT=1).  -> gpurun_out/ab_t25_cold.log
 mkdir -p gpurun_out; L=gpurun_out/ab_t25_cold.log; : > $L
-X="--steps 20 --warmup 5 --no-fp32 --no-bwk --no-exact --no-host-call --no-reflayout --no-x2 --no-shared-block --no-fresh-uw --no-cpu-baseline"
+X="--full --steps 20 --warmup 5 --no-fp32 --no-bwk --no-exact --no-host-call --no-reflayout --no-x2 --no-shared-block --no-fresh-uw --no-cpu-baseline"
 for i in 1 2 3; do
   for v in default split; do
     if [ $v = split ]; then export MPDATA_WM_SPLIT=1; else unset MPDATA_WM_SPLIT; fi

@@ -43,7 +43,7 @@ echo "== 3. bench.py --gpus 1 .. $N (plain command)" | tee -a "$OUT/summary.txt"
 rc3=0
 G=1
 while [ "$G" -le "$N" ]; do
-  timeout -k 10 1500 python3 bench.py --gpus "$G" --steps 20 --warmup 5 > "$OUT/3_bench_gpus$G.json" 2> "$OUT/3_bench_gpus$G.err"
+  timeout -k 10 1500 python3 bench.py --full --gpus "$G" --steps 20 --warmup 5 > "$OUT/3_bench_gpus$G.json" 2> "$OUT/3_bench_gpus$G.err"
   rc=$?
   [ $rc != 0 ] && rc3=$rc
   python3 - "$OUT/3_bench_gpus$G.json" "$G" <<'PY' | tee -a "$OUT/summary.txt"

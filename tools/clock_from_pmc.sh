@@ -2,7 +2,7 @@
 # usage (GPU box): bash tools/clock_from_pmc.sh     (MPDATA_WM_TPW1=1 in the environment: one tracer per wave)
 ROOT=$PWD; OUT=$ROOT/gpurun_out/clk; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-X="--no-cpu-baseline --no-fp32 --no-bwk --no-reflayout"
+X="--full --no-cpu-baseline --no-fp32 --no-bwk --no-reflayout"
 for tag in tpw2 tpw1; do
   if [ $tag = tpw1 ]; then export MPDATA_WM_TPW1=1; else unset MPDATA_WM_TPW1; fi
   timeout -k 10 300 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/${tag}_clk -o run -- python3 $ROOT/bench.py --steps 2 --warmup 1 --prewarm-ms 0 --batched-steps 4 $X > $OUT/$tag.log 2>&1 || exit 1

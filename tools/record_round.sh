@@ -11,8 +11,8 @@
 TAG=${1:-r05}
 OUT=gpurun_out/${TAG}_final
 mkdir -p $OUT
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench driver rc=$?"
-timeout -k 10 400 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench driver rc=$?"
+timeout -k 10 400 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
 F=codesign-kernels_amd/fortran/advect
 {
   echo "== host mode, 1 tracer, FAST:  $F 65536 32 28 1 1 - - 1 1 host"
