@@ -23,6 +23,7 @@ _LIB_PATH = os.environ.get("MPDATA_HIP_LIB") or os.path.join(HERE, "libmpdata_hi
 VARIANT_EXACT, VARIANT_FAST = 0, 1
 EINVAL, EUNSUPPORTED, ESTATE, ECOMM = -1, -2, -3, -4   # MPDATA_E* of include/mpdata_hip.h
 LAYOUT_REFERENCE, LAYOUT_WAVEMAJOR = 0, 1
+BOUNDARY_GIVEN, BOUNDARY_PERIODIC = 0, 1   # MPDATA_BOUNDARY_* (include/mpdata_hip.h section 3a)
 
 _lib = None
 
@@ -89,6 +90,13 @@ def lib():
             getattr(L, name).argtypes = [vp]
         L.mpdata_set_plan_layout.restype = ci
         L.mpdata_set_plan_layout.argtypes = [ci]
+        L.mpdata_plan_set_boundary.restype = ci
+        L.mpdata_plan_set_boundary.argtypes = [vp, ci]
+        L.mpdata_plan_boundary.restype = ci
+        L.mpdata_plan_boundary.argtypes = [vp]
+        for name in ("mpdata_periodic_halo_device", "mpdata_periodic_halo_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, dp, vp]
         L.mpdata_plan_create_multi.restype = ci
         L.mpdata_plan_create_multi.argtypes = [i64, ci, ci, ci, ci, ctypes.POINTER(vp)]
         L.mpdata_plan_create_multi_devices.restype = ci
@@ -436,6 +444,16 @@ class Plan:
     def device(self):
         return lib().mpdata_plan_device(self._p)
 
+    @property
+    def boundary(self):
+        """lateral boundary mode (BOUNDARY_GIVEN, BOUNDARY_PERIODIC)"""
+        return lib().mpdata_plan_boundary(self._p)
+
+    def set_boundary(self, mode):
+        """BOUNDARY_PERIODIC: every run steps f with halos that are copies of the interior, and f is
+        read back wrapped; BOUNDARY_GIVEN (the default): halos are the caller's (mpdata_plan_set_boundary)."""
+        _check(lib().mpdata_plan_set_boundary(self._p, int(mode)))
+
     def upload(self, f, u, w, rho, rhow, adz, flux=None):
         ptrs = _host_ptrs((("f", f), ("u", u), ("w", w), ("rho", rho), ("rhow", rhow), ("adz", adz), ("flux", flux)),
                           self.dims, self._dt)
@@ -516,6 +534,34 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+def periodic_halo(f=None, u=None, w=None, stream=None):
+    """Make reference-layout DEVICE tensors (reversed-axes torch layout, float64 or float32, all of one
+    dtype) periodic in x, in place: f's columns -2..0, nx+1..nx+3, u's -1, 0, nx+1..nx+3, w's -1, 0,
+    nx+1, nx+2 := column 1 + ((i-1) mod nx) (mpdata_periodic_halo_device).  None = left alone."""
+    import torch
+    given = [(k, t) for k, t in (("f", f), ("u", u), ("w", w)) if t is not None]
+    if not given:
+        raise MpdataError(-1, "periodic_halo: f, u and w are all None")
+    dt = given[0][1].dtype
+    if dt not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"periodic_halo: dtype {dt} is neither float64 nor float32")
+    nt = 1
+    if f is not None:
+        nt = f.shape[0] if f.dim() == 4 else 1
+        nzm, nxp6, ncrms = f.shape[-3:]
+        nx, nz = nxp6 - 6, nzm + 1
+    elif u is not None:
+        nzm, nxp5, ncrms = u.shape
+        nx, nz = nxp5 - 5, nzm + 1
+    else:
+        nz, nxp4, ncrms = w.shape
+        nx = nxp4 - 4
+    sh = shapes(ncrms, nx, nz, nt)
+    ptrs = [None if t is None else _dev_ptr(t, sh[k], k, dt) for k, t in (("f", f), ("u", u), ("w", w))]
+    fn = lib().mpdata_periodic_halo_device if dt == torch.float64 else lib().mpdata_periodic_halo_f32_device
+    _check(fn(ncrms, nx, nz, nt, *ptrs, _stream_handle(stream)))
 
 
 def fill_synthetic(t, name, seed, dist, ncrms_global=None, sl0=0, stream=None):

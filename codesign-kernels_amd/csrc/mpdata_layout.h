@@ -40,4 +40,12 @@ hipError_t mpdata_layout_convert_cols(const MpdataLayoutJob* jobs, int nj, bool 
 // met (odd ncrms, unaligned base, array of 4 GiB or more), take mpdata_layout_convert_cols
 hipError_t mpdata_layout_import_rows(const MpdataLayoutJob* jobs, int nj, hipStream_t stream);
 
+// periodic lateral boundaries: f's halo columns -2..0, nx+1..nx+3 := copies of columns 1 + ((i-1) mod nx).
+//   _wm: the plan layout, a job of f (wm_job(which = 0): ntr tracers, ncol_p = nx + 6), one wave per (tracer, tile);
+//   _ref: a reference-layout array of ncols columns (column i at slot i + coff) and nlev levels per tracer, halo
+//   columns ilo..0 and nx+1..ihi (f: ncols nx+6, coff 2, -2, nx+3; u: nx+5, 1, -1, nx+3; w: nx+4, 1, -1, nx+2)
+hipError_t mpdata_layout_periodic_halo_wm(const MpdataLayoutJob& j, hipStream_t stream);
+hipError_t mpdata_layout_periodic_halo_ref(void* a, int elem_bytes, long long ncrms, int nx, int ncols, int coff, int nlev,
+                                           int ntr, int ilo, int ihi, hipStream_t stream);
+
 #endif

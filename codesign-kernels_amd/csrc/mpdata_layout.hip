@@ -283,7 +283,85 @@ __global__ void __launch_bounds__(16 * LPS) wm_import_rows_kernel(const MpdataRo
   }
 }
 
+// ---- Periodic lateral boundaries (mpdata_plan_set_boundary, mpdata_periodic_halo_device).  Halo column i in
+// {-2,-1,0,nx+1,nx+2,nx+3} of f takes column 1 + ((i-1) mod nx) -- always an interior column, never a halo one, so
+// every source is read before any store of the same wave can touch it and no ordering is needed between waves.
+
+// Plan layout: a wave per (tracer, tile) copies the 3 + 3 column chunks of its tile, lanes along the chunk (the
+// line-aligned main part and the remainder of a column, as the plan kernels address them).  8-byte elements (fp32
+// plans: a pair of instances).  Any LPS: the chunk is walked 64 elements at a time (LPS 128: nzm <= 237 elements).
+__global__ void __launch_bounds__(256) wm_periodic_halo_kernel(const MpdataLayoutJob j) {
+  const int lane = threadIdx.x & 63;
+  const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wv >= (long long)j.ntr * j.ntiles) return;
+  const int tr = (int)(wv / j.ntiles);
+  const long long tile = wv - (long long)tr * j.ntiles;
+  unsigned long long* base = static_cast<unsigned long long*>(j.prv) + (long long)tr * j.prv_tstride + tile * j.prv_tile_stride;
+  const int nx = j.ncol_p - 6;
+  int cs[6], cd[6];   // column slots (slot = i + 2) of the sources and destinations
+#pragma unroll
+  for (int h = 0; h < 6; ++h) {
+    const int i = h < 3 ? h - 2 : nx + h - 2;
+    cd[h] = i + 2;
+    cs[h] = 1 + (((i - 1) % nx) + nx) % nx + 2;
+  }
+  const long long main_e = j.main_e, rem_e = j.chunk - j.main_e, rem0 = (long long)j.ncol_p * j.main_e;
+  for (long long e = lane; e < j.chunk; e += 64) {
+    const bool in_main = e < main_e;
+    const long long cstep = main_e == 0 ? j.chunk : (in_main ? main_e : rem_e);
+    const long long o = main_e == 0 ? e : (in_main ? e : rem0 + (e - main_e));
+    unsigned long long v[6];
+#pragma unroll
+    for (int h = 0; h < 6; ++h) v[h] = base[o + cs[h] * cstep];
+#pragma unroll
+    for (int h = 0; h < 6; ++h) base[o + cd[h] * cstep] = v[h];
+  }
+}
+
+// Reference layout: element (sl, column i, level kk, tracer tr) at a + sl + ncrms * ((i + coff) + ncols * (kk + nlev * tr)).
+// Halo columns ilo .. 0 and nx+1 .. ihi; one row (halo column, level, tracer) of ncrms elements per blockIdx.y, the
+// instances along x.  E: 4- or 8-byte elements, copied as bits.
+template <typename E>
+__global__ void __launch_bounds__(256) ref_periodic_halo_kernel(E* a, long long ncrms, int nx, int ncols, int coff, int nlev,
+                                                               long long rows, int ilo, int ihi) {
+  const long long sl = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (sl >= ncrms) return;
+  const int nlo = 1 - ilo, nh = nlo + (ihi - nx);
+  for (long long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const int h = (int)(r % nh);
+    const long long lt = r / nh;   // level + nlev * tracer
+    const int i = h < nlo ? ilo + h : nx + 1 + (h - nlo);
+    const int is = 1 + (((i - 1) % nx) + nx) % nx;
+    E* row = a + lt * ncols * ncrms;
+    row[(long long)(i + coff) * ncrms + sl] = row[(long long)(is + coff) * ncrms + sl];
+  }
+}
+
 }  // namespace
+
+hipError_t mpdata_layout_periodic_halo_wm(const MpdataLayoutJob& j, hipStream_t stream) {
+  if (j.ntr < 1 || j.ntiles < 1 || j.ncol_p < 7 || j.chunk < 1 || j.main_e < 0 || j.main_e > j.chunk) return hipErrorInvalidValue;
+  const long long waves = (long long)j.ntr * j.ntiles;
+  hipLaunchKernelGGL(wm_periodic_halo_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, j);
+  return hipGetLastError();
+}
+
+hipError_t mpdata_layout_periodic_halo_ref(void* a, int elem_bytes, long long ncrms, int nx, int ncols, int coff, int nlev,
+                                           int ntr, int ilo, int ihi, hipStream_t stream) {
+  if (!a || ncrms < 1 || nx < 1 || nlev < 1 || ntr < 1 || ilo > 0 || ihi <= nx || ilo + coff < 0 || ihi + coff >= ncols)
+    return hipErrorInvalidValue;
+  const long long rows = (long long)(1 - ilo + ihi - nx) * nlev * ntr;
+  const dim3 grid((unsigned)((ncrms + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
+  if (elem_bytes == 8)
+    hipLaunchKernelGGL(ref_periodic_halo_kernel<unsigned long long>, grid, dim3(256), 0, stream, static_cast<unsigned long long*>(a),
+                       ncrms, nx, ncols, coff, nlev, rows, ilo, ihi);
+  else if (elem_bytes == 4)
+    hipLaunchKernelGGL(ref_periodic_halo_kernel<unsigned>, grid, dim3(256), 0, stream, static_cast<unsigned*>(a), ncrms, nx, ncols,
+                       coff, nlev, rows, ilo, ihi);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
 
 // f, u, w (split arrays, many columns) in one launch; nj = 1 or 2 jobs of equal nlev / slp
 hipError_t mpdata_layout_convert_cols(const MpdataLayoutJob* jobs, int nj, bool to_private, hipStream_t stream) {

@@ -83,6 +83,10 @@ struct mpdata_plan {
   bool have_u, have_w;   // the plan holds velocities (imported since the last mpdata_plan_run_uw)
   bool timing;     // record the event pair around every run (mpdata_plan_last_kernel_ms); mpdata_plan_set_timing
   unsigned runs;   // launches so far (serpentine tile order)
+  int boundary;    // MPDATA_BOUNDARY_* (mpdata_plan_set_boundary)
+  // per tracer: f's halo columns hold copies of its interior (set by the halo kernel; cleared by an import of f and
+  // by every run, whose kernels leave first-pass values there)
+  unsigned char* halo_ok;
   mpdata_multi* multi;  // != null: a multi-GPU plan (mpdata_multi.hip); nothing else above is used
 };
 
@@ -166,6 +170,7 @@ int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, con
   const int eb = p->eb;
   const size_t f1 = p->sz.f / p->ntracers;  // elements of one tracer of f
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (f) memset(p->halo_ok + first, 0, (size_t)count);   // (imported halos are not trusted: a periodic plan wraps again)
   if (p->layout == MPDATA_LAYOUT_REFERENCE) {
     if (f) HIP_TRY(hipMemcpyAsync((char*)p->f + first * f1 * eb, f, f1 * count * eb, kind, p->stream));
     if (u) { HIP_TRY(hipMemcpyAsync(p->u, u, p->sz.u * eb, kind, p->stream)); p->have_u = true; }
@@ -233,8 +238,31 @@ int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, con
   return rc;
 }
 
+// Periodic plans: f's halo columns of tracers [first, first + count) := copies of the interior, where they are not
+// already (mpdata_layout_periodic_halo_*: one launch over the unmarked span of the range); a no-op in GIVEN mode.
+int plan_wrap_f(mpdata_plan* p, int first, int count) {
+  if (p->boundary != MPDATA_BOUNDARY_PERIODIC) return 0;
+  int lo = first, hi = first + count;
+  while (lo < hi && p->halo_ok[lo]) ++lo;
+  while (hi > lo && p->halo_ok[hi - 1]) --hi;
+  if (lo == hi) return 0;
+  if (p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
+    HIP_TRY(mpdata_layout_periodic_halo_wm(wm_job(p, 0, nullptr, lo, hi - lo), p->stream));
+  } else {
+    const size_t f1 = p->sz.f / p->ntracers;
+    HIP_TRY(mpdata_layout_periodic_halo_ref((char*)p->f + (size_t)lo * f1 * p->eb, p->eb, p->ncrms, p->nx, p->nx + 6, 2, p->nz - 1,
+                                            hi - lo, -2, p->nx + 3, p->stream));
+  }
+  memset(p->halo_ok + lo, 1, (size_t)(hi - lo));
+  return 0;
+}
+
 int plan_export(mpdata_plan* p, void* f, void* flux, int first, int count, bool dev) {
   const int eb = p->eb;
+  if (f) {   // (periodic plans hand out wrapped halos)
+    const int rc = plan_wrap_f(p, first, count);
+    if (rc) return rc;
+  }
   const size_t f1 = p->sz.f / p->ntracers;
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (p->layout == MPDATA_LAYOUT_REFERENCE) {
@@ -296,6 +324,11 @@ static int plan_create(int64_t ncrms, int nx, int nz, int ntracers, mpdata_plan*
   p->variant = var;
   p->layout = wmaj ? MPDATA_LAYOUT_WAVEMAJOR : MPDATA_LAYOUT_REFERENCE;
   p->sz = sizes_of(ncrms, nx, nz, ntracers);
+  p->halo_ok = (unsigned char*)calloc((size_t)ntracers, 1);
+  if (!p->halo_ok) {
+    free(p);
+    return set_err(MPDATA_EINVAL, "out of host memory");
+  }
   hipError_t e = hipGetDevice(&p->device);
   if (e == hipSuccess && !wmaj) {
     const size_t nb[7] = {p->sz.f * eb, p->sz.u * eb, p->sz.w * eb, p->sz.k * eb, p->sz.kz * eb, p->sz.k * eb,
@@ -322,6 +355,7 @@ static int plan_create(int64_t ncrms, int nx, int nz, int ntracers, mpdata_plan*
     // (chunk = (64/LPS) * nzm * 8 bytes with LPS/2 <= nzm < LPS, nz >= 3: 128 .. 504 bytes); checked
     // here so that a future tiling cannot break the wait silently.
     if (p->lps <= 64 && (p->main_e * web < 128 || p->main_e * web > 384)) {   // (nz > 64: one fetch instruction per array and pair)
+      free(p->halo_ok);
       free(p);
       return set_err(MPDATA_EUNSUPPORTED, "internal: column chunk of %lld bytes breaks the two-instructions-per-fetch "
                                           "invariant of the wave-major kernels", (long long)(p->chunk * web));
@@ -557,7 +591,9 @@ int mpdata_plan_run_tracers(mpdata_plan* p, int first, int count) {
                                   "ran since -- it leaves none behind): import u and w first");
   DevGuard g(p->device);
   if (p->timing) HIP_TRY(hipEventRecord(p->ev0, p->stream));
-  rc = plan_launch(p, first, count);
+  rc = plan_wrap_f(p, first, count);
+  memset(p->halo_ok + first, 0, (size_t)count);   // (the run leaves first-pass values in the halos)
+  if (!rc) rc = plan_launch(p, first, count);
   if (rc) return rc;
   if (p->timing) HIP_TRY(hipEventRecord(p->ev1, p->stream));
   p->ran = p->timing;
@@ -604,6 +640,9 @@ int mpdata_plan_run_uw(mpdata_plan* p, int first, int count, const void* u, cons
   // plan's u, w (they would be stale), the other paths overwrite them (they would be the new ones):
   // neither is promised, mpdata_plan_run returns MPDATA_ESTATE until u, w are imported again.
   p->have_u = p->have_w = false;
+  rc = plan_wrap_f(p, first, count);
+  if (rc) return rc;
+  memset(p->halo_ok + first, 0, (size_t)count);
   if (ring && count == 1) {
     rc = plan_launch(p, first, count, u, w);
   } else if (ring && p->lps <= 32) {
@@ -686,6 +725,48 @@ int mpdata_plan_set_timing(mpdata_plan* p, int on) {
 int mpdata_plan_layout(const mpdata_plan* p) { return p ? p->layout : MPDATA_EINVAL; }
 int mpdata_plan_device(const mpdata_plan* p) { return p ? p->device : MPDATA_EINVAL; }
 
+// Lateral boundary mode.  PERIODIC: f's halo columns are refreshed from the interior in front of every run and every
+// read-back (plan_wrap_f).  Back to GIVEN: the plan first holds what an export would return (wrapped halos).
+int mpdata_plan_set_boundary(mpdata_plan* p, int mode) {
+  if (!p) return set_err(MPDATA_EINVAL, "null plan");
+  if (mode != MPDATA_BOUNDARY_GIVEN && mode != MPDATA_BOUNDARY_PERIODIC) return set_err(MPDATA_EINVAL, "unknown boundary mode %d", mode);
+  if (p->multi) {   // every shard plan holds its own halos
+    for (int g = 0; g < mpdata_multi_ngpus(p->multi); ++g) {
+      const int rc = mpdata_plan_set_boundary(mpdata_multi_sub(p->multi, g), mode);
+      if (rc) return rc;
+    }
+    p->boundary = mode;
+    return 0;
+  }
+  if (p->boundary == MPDATA_BOUNDARY_PERIODIC && mode == MPDATA_BOUNDARY_GIVEN && p->uploaded) {
+    DevGuard g(p->device);
+    const int rc = plan_wrap_f(p, 0, p->ntracers);
+    if (rc) return rc;
+  }
+  p->boundary = mode;
+  return 0;
+}
+int mpdata_plan_boundary(const mpdata_plan* p) { return p ? p->boundary : MPDATA_EINVAL; }
+
+// Reference-layout device arrays made periodic in x, in place (include/mpdata_hip.h 3c).
+static int periodic_halo(int64_t ncrms, int nx, int nz, int ntracers, void* f, void* u, void* w, void* stream, int eb) {
+  int rc = validate(ncrms, nx, nz, ntracers);
+  if (rc) return rc;
+  if (!f && !u && !w) return set_err(MPDATA_EINVAL, "mpdata_periodic_halo_device: f, u and w are all NULL");
+  const hipStream_t s = (hipStream_t)stream;
+  const int nzm = nz - 1;
+  if (f) HIP_TRY(mpdata_layout_periodic_halo_ref(f, eb, ncrms, nx, nx + 6, 2, nzm, ntracers, -2, nx + 3, s));
+  if (u) HIP_TRY(mpdata_layout_periodic_halo_ref(u, eb, ncrms, nx, nx + 5, 1, nzm, 1, -1, nx + 3, s));
+  if (w) HIP_TRY(mpdata_layout_periodic_halo_ref(w, eb, ncrms, nx, nx + 4, 1, nz, 1, -1, nx + 2, s));
+  return 0;
+}
+int mpdata_periodic_halo_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, double* u, double* w, void* stream) {
+  return periodic_halo(ncrms, nx, nz, ntracers, f, u, w, stream, 8);
+}
+int mpdata_periodic_halo_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, float* u, float* w, void* stream) {
+  return periodic_halo(ncrms, nx, nz, ntracers, f, u, w, stream, 4);
+}
+
 // ---- multi-GPU plans (mpdata_multi.hip): the same handle type; upload / run / run_tracers /
 // sync / download / last_kernel_ms / destroy dispatch to the per-device plans.
 static int plan_create_multi(int64_t ncrms, int nx, int nz, int ntracers, int ngpus, const int* devices,
@@ -750,6 +831,7 @@ int mpdata_plan_transfer_stats(const mpdata_plan* p, double* scatter_s, double* 
 
 int mpdata_plan_destroy(mpdata_plan* p) {
   if (!p) return 0;
+  free(p->halo_ok);
   if (p->multi) {
     const int rc = mpdata_multi_destroy(p->multi);
     free(p);

@@ -18,6 +18,10 @@ module mpdata_hip_mod
   public :: advect_scalar2D, advect_resident_begin, advect_resident_run, advect_resident_end
   public :: mpdata_set_variant, mpdata_check, advect_transfer_stats
   public :: advect_device_problem_run
+  ! periodic lateral boundaries (include/mpdata_hip.h sections 3a, 3c): the CRMs of the MMF are periodic in x
+  public :: MPDATA_BOUNDARY_GIVEN, MPDATA_BOUNDARY_PERIODIC
+  public :: mpdata_plan_set_boundary_c, mpdata_plan_boundary_c, mpdata_periodic_halo_device_c
+  integer(c_int), parameter :: MPDATA_BOUNDARY_GIVEN = 0, MPDATA_BOUNDARY_PERIODIC = 1
 
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
@@ -26,11 +30,13 @@ module mpdata_hip_mod
 #define MPDATA_C_PLAN_CREATE "mpdata_plan_create_f32"
 #define MPDATA_C_PLAN_UPLOAD "mpdata_plan_upload_f32"
 #define MPDATA_C_PLAN_DOWNLOAD "mpdata_plan_download_f32"
+#define MPDATA_C_PERIODIC_HALO "mpdata_periodic_halo_f32_device"
 #else
 #define MPDATA_C_ADVECT "mpdata_advect_scalar2d"
 #define MPDATA_C_PLAN_CREATE "mpdata_plan_create"
 #define MPDATA_C_PLAN_UPLOAD "mpdata_plan_upload"
 #define MPDATA_C_PLAN_DOWNLOAD "mpdata_plan_download"
+#define MPDATA_C_PERIODIC_HALO "mpdata_periodic_halo_device"
 #endif
 
   interface
@@ -140,6 +146,24 @@ module mpdata_hip_mod
     integer(c_int) function mpdata_plan_ranks_seen_c(plan) bind(C, name="mpdata_plan_ranks_seen")
       import :: c_int, c_ptr
       type(c_ptr), value :: plan
+    end function
+    ! mode: MPDATA_BOUNDARY_GIVEN (default) or MPDATA_BOUNDARY_PERIODIC; returns 0 or MPDATA_EINVAL (-1)
+    integer(c_int) function mpdata_plan_set_boundary_c(plan, mode) bind(C, name="mpdata_plan_set_boundary")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int), value :: mode
+    end function
+    integer(c_int) function mpdata_plan_boundary_c(plan) bind(C, name="mpdata_plan_boundary")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: plan
+    end function
+    ! reference-layout DEVICE arrays (c_null_ptr: skipped) made periodic in x, in place, on `stream`
+    integer(c_int) function mpdata_periodic_halo_device_c(ncrms, nx, nz, ntracers, f, u, w, stream) &
+        bind(C, name=MPDATA_C_PERIODIC_HALO)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      type(c_ptr), value :: f, u, w, stream
     end function
   end interface
 

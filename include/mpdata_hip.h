@@ -158,7 +158,7 @@ int mpdata_plan_destroy(mpdata_plan* plan);
  * the plan's device, asynchronous on the plan's stream.  Import: NULL pointers are skipped
  * (the plan keeps what it has); f and flux cover tracers [first_tracer, first_tracer+ntracers).
  * A caller whose state lives on the device imports once, runs many times, exports when it
- * needs the field back. */
+ * needs the field back (several steps of one boundary condition: mpdata_plan_set_boundary, 3a). */
 int mpdata_plan_import_device(mpdata_plan* plan, const void* f, const void* u, const void* w,
                               const void* rho, const void* rhow, const void* adz,
                               const void* flux, int first_tracer, int ntracers);
@@ -168,6 +168,35 @@ int mpdata_plan_set_stream(mpdata_plan* plan, void* stream);
 int mpdata_plan_layout(const mpdata_plan* plan);   /* MPDATA_LAYOUT_* */
 int mpdata_plan_device(const mpdata_plan* plan);   /* HIP device ordinal */
 int mpdata_set_plan_layout(int layout);            /* default for new plans; returns previous */
+
+/* ---- 3a. Lateral boundary of a plan.  The routine reads f's halo columns -2..0 and nx+1..nx+3 as
+ * INPUTS (the caller's boundary exchange fills them before every call) and leaves first-pass values in
+ * -1, 0, nx+1, nx+2 (see the array contract above), so a second run of a GIVEN plan does not step any
+ * boundary condition.  MPDATA_BOUNDARY_PERIODIC (the CRMs of the MMF are periodic in x): in front of
+ * EVERY run (run, run_tracers, run_uw) and every read-back of f (download, export_device, the
+ * multi-GPU gather) the halo columns of the tracers concerned become copies of the interior --
+ * column i takes column 1 + ((i-1) mod nx), at every level, any nx >= 1 -- so K runs are K steps of
+ * `wrap(f); advect(f)` and f comes back wrapped (EXACT: bit-identical to that loop, flux included).
+ * Halo columns are not state in this mode: imported halos are ignored.  u and w are used as given
+ * (periodic flow: wrap them with mpdata_periodic_halo_device); flux is unaffected.  The refresh is
+ * one small kernel in the run's event pair (its tracers only, and only where a run or an import
+ * since the last refresh left the halos stale).  set_boundary(GIVEN) on a periodic plan first wraps,
+ * so the plan then holds what an export just before the switch would have returned.  Multi-GPU
+ * plans forward the mode to every shard.  Default: GIVEN, today's behaviour exactly. */
+#define MPDATA_BOUNDARY_GIVEN 0
+#define MPDATA_BOUNDARY_PERIODIC 1
+int mpdata_plan_set_boundary(mpdata_plan* plan, int mode); /* 0, or MPDATA_EINVAL (null plan, unknown mode) */
+int mpdata_plan_boundary(const mpdata_plan* plan);        /* MPDATA_BOUNDARY_*; MPDATA_EINVAL for a null plan */
+
+/* ---- 3c. Periodic halos of reference-layout DEVICE arrays, in place, asynchronous on `stream`
+ * (NULL = default stream): f in columns -2..0, nx+1..nx+3 (ntracers tracers); u in columns -1, 0,
+ * nx+1..nx+3 (every level); w in columns -1, 0, nx+1, nx+2 (all nz levels) -- column i := column
+ * 1 + ((i-1) mod nx).  Any of f, u, w may be NULL, not all three.  Arguments are checked before any
+ * device call (MPDATA_EINVAL). */
+int mpdata_periodic_halo_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, double* u, double* w,
+                                void* stream);
+int mpdata_periodic_halo_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, float* u, float* w,
+                                    void* stream);
 
 /* ---- 3b. One problem on several GPUs of the node.  No statement of the routine couples two
  * CRM instances (reference :505-637), so the ncrms axis is cut into `ngpus` contiguous blocks
