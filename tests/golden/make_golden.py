@@ -9,7 +9,8 @@ from (shape, seed, dist).  Only data is committed (npz + manifest.json); no
 reference source text.  Runs in the build container only (needs
 /root/reference + amdflang).
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py             # everything
+    python tests/golden/make_golden.py --regimes   # only the value-regime fixtures (manifest key "regimes")
 """
 import hashlib
 import json
@@ -25,6 +26,7 @@ from oracle import build_ref  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from oracle import bwk as B  # noqa: E402
 from oracle import nlk as N  # noqa: E402
+from oracle import regimes as RG  # noqa: E402
 
 # (ncrms, nx, nz, seed, dist)
 CASES = [
@@ -47,6 +49,45 @@ CASES_F32 = [
     (8, 32, 28, 100, O.DIST_CONDITIONED),
     (64, 32, 28, 100, O.DIST_RAW),
 ]
+
+
+# value regimes (oracle/regimes.py) through the reference, fp64 and fp32: every regime at 8 x 32 x 28, a few at
+# 3 x 8 x 6.  They pin the oracle where the limiter's eps matters (the fp32 eps included, which the unit-scale
+# cases above cannot see) and the sign of zero; kept apart from "cases" (those are rebuilt from (shape, seed, dist)).
+REGIME_SHAPES = [((8, 32, 28), RG.REGIMES),
+                 ((3, 8, 6), ("scaled_m30", "sparse", "fronts", "signed_zero", "f32_tiny"))]
+REGIME_SEED = 100
+
+
+def regime_name(regime, ncrms, nx, nz, seed, f32=False):
+    return f"regime_{regime}_{ncrms}x{nx}x{nz}_seed{seed}" + ("_f32" if f32 else "")
+
+
+def make_regimes():
+    """Run the reference on every regime case; write the .npz fixtures, return the manifest entries."""
+    out = []
+    for (ncrms, nx, nz), names in REGIME_SHAPES:
+        for f32 in (False, True):
+            dt = np.float32 if f32 else np.float64
+            build_ref.build(ncrms, nx, nz, f32=f32)
+            for regime in names:
+                if regime not in RG.regimes_for(dt):
+                    continue
+                inp = RG.make(regime, ncrms, nx, nz, seed=REGIME_SEED, dtype=dt)
+                f, flux, _ = O.run_reference(inp)
+                name = regime_name(regime, ncrms, nx, nz, REGIME_SEED, f32)
+                np.savez(os.path.join(HERE, name + ".npz"), f=f, flux=flux)
+                out.append({
+                    "name": name, "regime": regime, "ncrms": ncrms, "nx": nx, "nz": nz, "seed": REGIME_SEED,
+                    "dtype": "f32" if f32 else "f64",
+                    "f_sha256": hashlib.sha256(f.tobytes(order="F")).hexdigest(),
+                    "flux_sha256": hashlib.sha256(flux.tobytes(order="F")).hexdigest(),
+                    "inputs_sha256": hashlib.sha256(b"".join(
+                        inp[k].tobytes(order="F") for k in ("adz", "f", "u", "w", "rho", "rhow", "flux")
+                    )).hexdigest(),
+                    "f_min": float(f.min()), "f_max": float(f.max())})
+                print(name, f.shape, flux.shape)
+    return out
 
 
 NLK_SAMPLE_EDGES, NLK_SAMPLE_SEED = 16, 7
@@ -77,6 +118,13 @@ def case_name(ncrms, nx, nz, seed, dist, f32=False):
 
 
 def main():
+    if "--regimes" in sys.argv[1:]:
+        with open(os.path.join(HERE, "manifest.json")) as fh:
+            manifest = json.load(fh)
+        manifest["regimes"] = make_regimes()
+        with open(os.path.join(HERE, "manifest.json"), "w") as fh:
+            json.dump(manifest, fh, indent=1)
+        return
     manifest = {"generator": "tests/golden/make_golden.py",
                 "reference": "mmf-mpdata-tracer/advect_scalar2D_pushncols_openacc.F90 "
                              "(advect_scalar2D_cpu, :477-642)",
@@ -141,6 +189,7 @@ def main():
                 "sample_seed": NLK_SAMPLE_SEED, "stored": True,
                 "refFlx_sha256": hashlib.sha256(sref.tobytes(order="F")).hexdigest()})
             print(sname, sref.shape)
+    manifest["regimes"] = make_regimes()
     with open(os.path.join(HERE, "manifest.json"), "w") as fh:
         json.dump(manifest, fh, indent=1)
 
