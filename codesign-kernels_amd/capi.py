@@ -83,6 +83,13 @@ def lib():
         L.mpdata_plan_import_device.argtypes = [vp] + [vp] * 7 + [ci, ci]
         L.mpdata_plan_export_device.restype = ci
         L.mpdata_plan_export_device.argtypes = [vp, vp, vp, ci, ci]
+        L.mpdata_plan_import_instances_device.restype = ci
+        L.mpdata_plan_import_instances_device.argtypes = [vp, i64, i64] + [vp] * 7 + [ci, ci]
+        L.mpdata_plan_export_instances_device.restype = ci
+        L.mpdata_plan_export_instances_device.argtypes = [vp, i64, i64, vp, vp, ci, ci]
+        for name in ("mpdata_plan_download_instances", "mpdata_plan_download_instances_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -511,6 +518,66 @@ class Plan:
         pl = None if flux is None else _dev_ptr(flux, sh["flux"], "flux", self._tdt())
         _check(lib().mpdata_plan_export_device(self._p, pf, pl, int(first_tracer), int(ntr)))
 
+    def _block_dims(self, given):
+        """(n, ntr) of the block the tensors `given` = [(name, tensor)] describe: n is their common last axis, ntr
+        the leading axis of a 4-d f / 3-d flux."""
+        n, ntr = None, 1
+        for name, t in given:
+            if t.dim() < 2:
+                raise MpdataError(-1, f"{name}: shape {tuple(t.shape)} is no reference-layout array of a block")
+            if n is None:
+                n = int(t.shape[-1])
+            if name in ("f", "flux") and t.dim() == (4 if name == "f" else 3):
+                ntr = int(t.shape[0])
+        if n is None:
+            raise MpdataError(-1, "block call without an array")
+        return n, ntr
+
+    def import_block(self, sl0, f=None, u=None, w=None, rho=None, rhow=None, adz=None, flux=None, first_tracer=0):
+        """Reference-layout DEVICE tensors that cover ONLY instances [sl0, sl0+n) -> those instances of the plan
+        (mpdata_plan_import_instances_device): exactly the tensors of a problem shapes(n, nx, nz, ntr), n = their last
+        axis.  None = keep what the plan has.  The plan must have been filled once as a whole."""
+        _, nx, nz, _ = self.dims
+        arrs = (("f", f), ("u", u), ("w", w), ("rho", rho), ("rhow", rhow), ("adz", adz), ("flux", flux))
+        n, ntr = self._block_dims([(k, t) for k, t in arrs if t is not None])
+        sh = shapes(n, nx, nz, ntr)
+        args = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in arrs]
+        _check(lib().mpdata_plan_import_instances_device(self._p, int(sl0), n, *args, int(first_tracer), ntr))
+
+    def export_block(self, sl0, f=None, flux=None, first_tracer=0):
+        """Instances [sl0, sl0+n) of the plan's f / flux of tracers first_tracer.. -> reference-layout device tensors
+        of a problem of n instances (mpdata_plan_export_instances_device): the slice of what export_device returns."""
+        _, nx, nz, _ = self.dims
+        arrs = (("f", f), ("flux", flux))
+        n, ntr = self._block_dims([(k, t) for k, t in arrs if t is not None])
+        sh = shapes(n, nx, nz, ntr)
+        pf, pl = (None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in arrs)
+        _check(lib().mpdata_plan_export_instances_device(self._p, int(sl0), n, pf, pl, int(first_tracer), ntr))
+
+    def download_block(self, sl0, f, flux):
+        """Instances [sl0, sl0+n) of f / flux, all tracers -> HOST arrays (numpy, Fortran order, host_shapes(n, nx, nz,
+        ntracers); either may be None), synchronous (mpdata_plan_download_instances)."""
+        _, nx, nz, nt = self.dims
+        given = [a for a in (f, flux) if a is not None]
+        if not given or not isinstance(given[0], np.ndarray) or given[0].ndim < 2:
+            raise MpdataError(-1, "download_block: need a numpy array for f or flux")
+        n = int(given[0].shape[0])
+        ptrs = _host_ptrs((("f", f), ("flux", flux)), (n, nx, nz, nt), self._dt, writable=("f", "flux"))
+        _check(getattr(lib(), "mpdata_plan_download_instances" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
+    def shard_plan(self, g):
+        """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
+        import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
+        nothing; it must not be used after the plan it came from is closed."""
+        h = lib().mpdata_plan_shard_plan(self._p, int(g))
+        if not h:
+            raise MpdataError(-1, f"shard_plan: no shard {g} (the plan has {self.ngpus})")
+        nloc = self.shards()[int(g)][2]
+        v = Plan.__new__(Plan)
+        v._p, v._dt, v._sfx, v._view = ctypes.c_void_p(h), self._dt, self._sfx, True
+        v.dims = (int(nloc),) + tuple(self.dims[1:])
+        return v
+
     def set_stream(self, stream=None):
         """Run on a torch stream (default: torch's current stream) from now on."""
         _check(lib().mpdata_plan_set_stream(self._p, _stream_handle(stream)))
@@ -526,7 +593,8 @@ class Plan:
 
     def close(self):
         if self._p:
-            lib().mpdata_plan_destroy(self._p)
+            if not getattr(self, "_view", False):   # (a shard_plan view owns nothing)
+                lib().mpdata_plan_destroy(self._p)
             self._p = ctypes.c_void_p()
 
     def __del__(self):

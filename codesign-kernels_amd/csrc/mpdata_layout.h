@@ -48,4 +48,25 @@ hipError_t mpdata_layout_periodic_halo_wm(const MpdataLayoutJob& j, hipStream_t 
 hipError_t mpdata_layout_periodic_halo_ref(void* a, int elem_bytes, long long ncrms, int nx, int ncols, int coff, int nlev,
                                            int ntr, int ilo, int ihi, hipStream_t stream);
 
+// ---- blocks of instances (include/mpdata_hip.h 3d): instances [sl0, sl0 + n) of a plan <-> compact reference-layout
+// arrays of leading dimension n.  A job of its own around the whole-plan one (the whole-plan kernels do not see it).
+//   j: the plan side exactly as wm_job makes it for a whole-plan conversion (j.ncrms, j.ntiles, j.chunk, j.main_e,
+//      the strides: in 8-byte elements of the private side); j.ref: the BLOCK's array, element (b, cs, kk) of tracer tr at
+//      ref + tr*j.ref_tstride + b + n*(cs*ref_colmul + kk*ref_levmul), in reals (j.ref_tstride: for leading dimension n)
+//   ipe: reals per 8-byte element of the private side -- 1 (fp64), 2 (fp32 plans: pairs of adjacent instances; a block
+//      may split a pair, so both sides move single reals)
+//   ncrms: the plan's instances (reals).  Import keeps the whole-plan invariant: the padding instances of the last tile
+//      are copies of the plan's last instance (fp32: of its last pair) -- they follow a block that contains it.
+struct MpdataBlockJob {
+  MpdataLayoutJob j;
+  long long sl0, n, ncrms;
+  int ipe;
+};
+// one launch per array; the grid covers the tiles that intersect the block x the array's columns x tracers
+hipError_t mpdata_layout_convert_block(const MpdataBlockJob& b, bool to_private, hipStream_t stream);
+// rows x n elements between two pitched arrays (element (r, s) at base + r*pitch + s; pitches in elements of elem_bytes
+// = 4 or 8): the slab a block is in a reference-layout array of leading dimension ncrms
+hipError_t mpdata_layout_copy_rows(void* dst, const void* src, int elem_bytes, long long n, long long rows, long long dst_pitch,
+                                   long long src_pitch, hipStream_t stream);
+
 #endif

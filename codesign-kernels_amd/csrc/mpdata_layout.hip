@@ -186,6 +186,83 @@ __global__ void __launch_bounds__(256) wm_convert_cols_kernel(const MpdataLayout
   }
 }
 
+// ---- A block of instances [sl0, sl0 + n) of a plan <-> compact reference-layout arrays of leading dimension n
+// (MpdataBlockJob).  A workgroup moves all levels of `ti` consecutive instance slots of one column through the LDS
+// tile of wm_convert_kernel; the slots start at a multiple of ti, hence on a tile boundary (ti is a multiple of the
+// slp * ipe instances of a tile), and blockIdx.x counts from the group that holds sl0: the grid is the block's, not
+// the plan's.  E is ONE real as bits (unsigned long long / unsigned): the first and last tile of a block are partial
+// and an fp32 block may split an instance pair, so both sides move single reals and a store happens only for a slot
+// whose instance lies in the block -- the neighbours in the tile and the partner of a split pair are never touched.
+// Import: a padding slot of the last tile takes the plan's last instance (fp32: the same half of its last pair) when
+// the block contains it.
+template <typename E, bool TO_PRIVATE>
+__global__ void __launch_bounds__(256) wm_block_kernel(const MpdataBlockJob b, const int ti) {
+  extern __shared__ double lds_raw[];
+  E* tile = reinterpret_cast<E*>(lds_raw);   // [nlev][ti + 1]
+  const MpdataLayoutJob& j = b.j;
+  const int tid = threadIdx.x, tp = ti + 1;
+  const int cs = blockIdx.y, tr = blockIdx.z;
+  const int nlev = j.nlev, slp = j.slp, ipe = b.ipe;
+  const int nel = nlev * ti;
+  const long long g0 = (b.sl0 / ti + blockIdx.x) * ti;             // first slot of this workgroup
+  const long long nslot = (long long)j.ntiles * slp * ipe;         // slots the private side holds (padded)
+  E* ref = static_cast<E*>(j.ref) + (long long)tr * j.ref_tstride;
+  E* prv = static_cast<E*>(j.prv) + (long long)tr * j.prv_tstride * ipe;
+  const long long c = cs + j.prv_col0, rem_e = j.chunk - j.main_e;
+
+  // slot -> index of its instance in the block's arrays; -1: not this call's
+  auto block_index = [&](const long long q) -> long long {
+    if (q >= nslot) return -1;
+    long long s = q;
+    if (q >= b.ncrms) {
+      if (!TO_PRIVATE) return -1;
+      s = b.ncrms - ipe + q % ipe;
+    }
+    return (s >= b.sl0 && s < b.sl0 + b.n) ? s - b.sl0 : -1;
+  };
+  auto ref_at = [&](const long long bi, const int kk) -> long long {
+    return bi + b.n * ((long long)cs * j.ref_colmul + (long long)kk * j.ref_levmul);
+  };
+  auto prv_at = [&](const long long q, const int kk) -> long long {
+    const long long inst = q / ipe, h = q - inst * ipe;
+    const long long t = inst / slp;
+    const long long e = (inst - t * slp) * nlev + kk;
+    const long long o = j.main_e == 0 ? c * j.chunk + e : (e < j.main_e ? c * j.main_e + e : j.ncol_p * j.main_e + c * rem_e + (e - j.main_e));
+    return (t * j.prv_tile_stride + o) * ipe + h;
+  };
+  // reference side: i -> (level, slot), a row segment per level; private side: i -> (instance, level, half of the pair),
+  // the chunk of a tile contiguous
+  auto ref_side = [&](const int i, int& kk, int& t) { kk = i / ti; t = i - kk * ti; };
+  auto prv_side = [&](const int i, int& kk, int& t) {
+    const int h = i % ipe, r = i / ipe;
+    const int pr = r / nlev;
+    kk = r - pr * nlev; t = pr * ipe + h;
+  };
+  int kk, t;
+  for (int i = tid; i < nel; i += 256) {
+    if (TO_PRIVATE) ref_side(i, kk, t); else prv_side(i, kk, t);
+    const long long bi = block_index(g0 + t);
+    if (bi >= 0) tile[kk * tp + t] = TO_PRIVATE ? ref[ref_at(bi, kk)] : prv[prv_at(g0 + t, kk)];
+  }
+  __syncthreads();
+  for (int i = tid; i < nel; i += 256) {
+    if (TO_PRIVATE) prv_side(i, kk, t); else ref_side(i, kk, t);
+    const long long bi = block_index(g0 + t);
+    if (bi >= 0) {
+      if (TO_PRIVATE) prv[prv_at(g0 + t, kk)] = tile[kk * tp + t];
+      else ref[ref_at(bi, kk)] = tile[kk * tp + t];
+    }
+  }
+}
+
+// rows x n elements between two pitched arrays (reference-layout plans: a block is a strided slab)
+template <typename E>
+__global__ void __launch_bounds__(256) copy_rows_kernel(E* dst, const E* src, long long n, long long total, long long dp, long long sp) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long r = i / n, s = i - r * n;
+    dst[r * dp + s] = src[r * sp + s];
+  }
+}
 
 // ---- Import (reference -> plan) of f, u, w by ROW SEGMENTS through LDS-DMA (round 4).  The data path of the
 // kernel that reads u, w from the reference layout (mpdata_kernel_wm_body.h, UWREF) without the arithmetic: a
@@ -431,6 +508,45 @@ hipError_t mpdata_layout_import_rows(const MpdataLayoutJob* jobs, int nj, hipStr
     case 64: hipLaunchKernelGGL((wm_import_rows_kernel<64>), grid, dim3(1024), 0, stream, js); break;
     default: return hipErrorNotSupported;
   }
+  return hipGetLastError();
+}
+
+// a block of instances of one array (wm_block_kernel); any array: split (f, u, w) or not
+hipError_t mpdata_layout_convert_block(const MpdataBlockJob& b, bool to_private, hipStream_t stream) {
+  const MpdataLayoutJob& j = b.j;
+  if (j.ncols < 1 || j.ncols > 65535 || j.ntr < 1 || j.ntr > 65535 || j.nlev < 1 || j.nlev > 256 || j.slp < 1 || j.ntiles < 1 ||
+      (b.ipe != 1 && b.ipe != 2) || j.main_e < 0 || j.main_e > j.chunk)
+    return hipErrorInvalidValue;
+  if (b.sl0 < 0 || b.n < 1 || b.sl0 + b.n > b.ncrms || b.ncrms > (long long)j.ntiles * j.slp * b.ipe || b.ncrms < b.ipe)
+    return hipErrorInvalidValue;
+  // slots per workgroup: the LDS tile is nlev x (ti + 1) reals, 32 KB at most
+  const int ti = j.nlev > 63 ? 16 : 64;
+  if (ti % (j.slp * b.ipe) != 0) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((b.sl0 + b.n - 1) / ti - b.sl0 / ti + 1), (unsigned)j.ncols, (unsigned)j.ntr), block(256);
+  const size_t lds = (size_t)j.nlev * (ti + 1) * (8 / b.ipe);
+  if (b.ipe == 1) {
+    if (to_private) hipLaunchKernelGGL((wm_block_kernel<unsigned long long, true>), grid, block, lds, stream, b, ti);
+    else hipLaunchKernelGGL((wm_block_kernel<unsigned long long, false>), grid, block, lds, stream, b, ti);
+  } else {
+    if (to_private) hipLaunchKernelGGL((wm_block_kernel<unsigned, true>), grid, block, lds, stream, b, ti);
+    else hipLaunchKernelGGL((wm_block_kernel<unsigned, false>), grid, block, lds, stream, b, ti);
+  }
+  return hipGetLastError();
+}
+
+hipError_t mpdata_layout_copy_rows(void* dst, const void* src, int elem_bytes, long long n, long long rows, long long dst_pitch,
+                                   long long src_pitch, hipStream_t stream) {
+  if (!dst || !src || n < 1 || rows < 1 || dst_pitch < n || src_pitch < n) return hipErrorInvalidValue;
+  const long long total = n * rows, want = (total + 255) / 256;
+  const dim3 grid((unsigned)(want < (1 << 20) ? want : (1 << 20)));
+  if (elem_bytes == 8)
+    hipLaunchKernelGGL(copy_rows_kernel<unsigned long long>, grid, dim3(256), 0, stream, static_cast<unsigned long long*>(dst),
+                       static_cast<const unsigned long long*>(src), n, total, dst_pitch, src_pitch);
+  else if (elem_bytes == 4)
+    hipLaunchKernelGGL(copy_rows_kernel<unsigned>, grid, dim3(256), 0, stream, static_cast<unsigned*>(dst),
+                       static_cast<const unsigned*>(src), n, total, dst_pitch, src_pitch);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -72,6 +72,8 @@ struct mpdata_plan {
   void *pf, *pu, *pw, *pkc, *pflux;  // private arrays
   void* stage;                       // reference-layout staging: one tracer of f (or u, w)
   size_t stage_elems;
+  void* bstage;                      // staging of mpdata_plan_download_instances: f and flux of one block (grown on demand)
+  size_t bstage_bytes;
   void* flux_ref;                    // flux in the reference layout (level nz is carried through)
   void* wpark;                       // EXACT: park array of the limited vertical fluxes (bit-identical flux); with park_regs
   size_t wpark_bytes;                // only mpdata_plan_run_uw needs it: allocated by its first call
@@ -300,6 +302,102 @@ int plan_export(mpdata_plan* p, void* f, void* flux, int first, int count, bool 
   return 0;
 }
 
+// ---- Blocks of instances (include/mpdata_hip.h 3d): instances [sl0, sl0 + n) of the plan <-> reference-layout DEVICE
+// arrays of leading dimension n.  Wave-major plans: the block kernel of mpdata_layout.hip, one launch per array over
+// the tiles the block touches; reference-layout plans: the block is a strided slab of every array.
+MpdataBlockJob wm_block_job(const mpdata_plan* p, int which, void* ref, int64_t sl0, int64_t n, int first_tracer, int ntr) {
+  MpdataBlockJob b;
+  b.j = wm_job(p, which, ref, first_tracer, ntr);
+  b.j.ref_tstride = which == 0 ? (long long)n * (p->nx + 6) * (p->nz - 1) : which == 6 ? (long long)n * p->nz : 0;
+  b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
+  return b;
+}
+
+int plan_import_block(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w, const void* rho,
+                      const void* rhow, const void* adz, const void* flux, int first, int count) {
+  const int eb = p->eb, nx = p->nx, nz = p->nz, nzm = nz - 1;
+  if (f) memset(p->halo_ok + first, 0, (size_t)count);   // (as a whole import: a periodic plan wraps these tracers again)
+  // the slab of rows x n reals at instance sl0 of a reference-layout array of the plan
+  auto slab = [&](void* dst, const void* src, long long rows) -> int {
+    HIP_TRY(mpdata_layout_copy_rows((char*)dst + (size_t)sl0 * eb, src, eb, n, rows, p->ncrms, n, p->stream));
+    return 0;
+  };
+  int rc = 0;
+  if (p->layout == MPDATA_LAYOUT_REFERENCE) {
+    const size_t f1 = p->sz.f / p->ntracers;
+    if (f) rc = slab((char*)p->f + first * f1 * eb, f, (long long)(nx + 6) * nzm * count);
+    if (!rc && u) rc = slab(p->u, u, (long long)(nx + 5) * nzm);
+    if (!rc && w) rc = slab(p->w, w, (long long)(nx + 4) * nz);
+    if (!rc && rho) rc = slab(p->rho, rho, nzm);
+    if (!rc && rhow) rc = slab(p->rhow, rhow, nz);
+    if (!rc && adz) rc = slab(p->adz, adz, nzm);
+    if (!rc && flux) rc = slab((char*)p->flux + first * p->sz.kz * eb, flux, (long long)nz * count);
+    return rc;
+  }
+  auto conv = [&](int which, const void* ref, int tr, int ntr) -> int {
+    HIP_TRY(mpdata_layout_convert_block(wm_block_job(p, which, const_cast<void*>(ref), sl0, n, tr, ntr), true, p->stream));
+    return 0;
+  };
+  if (f) rc = conv(0, f, first, count);
+  if (!rc && u) rc = conv(1, u, 0, 1);
+  if (!rc && w) rc = conv(2, w, 0, 1);
+  if (!rc && rho) rc = conv(3, rho, 0, 1);
+  if (!rc && rhow) rc = conv(4, rhow, 0, 1);
+  if (!rc && adz) rc = conv(5, adz, 0, 1);
+  if (!rc && flux) {   // kept twice (plan_import): the reference-layout copy carries level nz
+    rc = slab((char*)p->flux_ref + (size_t)first * p->sz.kz * eb, flux, (long long)nz * count);
+    if (!rc) rc = conv(6, flux, first, count);
+  }
+  return rc;
+}
+
+// f, flux: device arrays of the block
+int plan_export_block(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flux, int first, int count) {
+  const int eb = p->eb, nx = p->nx, nz = p->nz, nzm = nz - 1;
+  auto slab = [&](void* dst, const void* src, long long rows) -> int {
+    HIP_TRY(mpdata_layout_copy_rows(dst, (const char*)src + (size_t)sl0 * eb, eb, n, rows, n, p->ncrms, p->stream));
+    return 0;
+  };
+  int rc = 0;
+  if (p->layout == MPDATA_LAYOUT_REFERENCE) {
+    const size_t f1 = p->sz.f / p->ntracers;
+    if (f) rc = slab(f, (char*)p->f + first * f1 * eb, (long long)(nx + 6) * nzm * count);
+    if (!rc && flux) rc = slab(flux, (char*)p->flux + first * p->sz.kz * eb, (long long)nz * count);
+  } else {
+    if (f) HIP_TRY(mpdata_layout_convert_block(wm_block_job(p, 0, f, sl0, n, first, count), false, p->stream));
+    if (flux) {
+      // levels 1..nzm from the private array, level nz from the reference-layout copy (plan_export)
+      HIP_TRY(mpdata_layout_convert_block(wm_block_job(p, 6, flux, sl0, n, first, count), false, p->stream));
+      const char* fr = (const char*)p->flux_ref + ((size_t)first * p->sz.kz + (size_t)nzm * p->ncrms + (size_t)sl0) * eb;
+      HIP_TRY(mpdata_layout_copy_rows((char*)flux + (size_t)nzm * n * eb, fr, eb, n, count, (long long)n * nz,
+                                      (long long)p->ncrms * nz, p->stream));
+    }
+  }
+  if (rc) return rc;
+  // periodic plans hand out wrapped halos: where the plan's own are stale, the BLOCK's copy is wrapped (the same bits
+  // as a refresh of the plan followed by the read-back, at the cost of the block; the plan's state is not touched)
+  if (f && p->boundary == MPDATA_BOUNDARY_PERIODIC) {
+    bool stale = false;
+    for (int t = first; t < first + count; ++t) stale = stale || !p->halo_ok[t];
+    if (stale) HIP_TRY(mpdata_layout_periodic_halo_ref(f, eb, n, nx, nx + 6, 2, nzm, count, -2, nx + 3, p->stream));
+  }
+  return 0;
+}
+
+// argument checks of the block entry points that need nothing of the plan but its sizes
+int block_range(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n) {
+  if (!p) return set_err(MPDATA_EINVAL, "%s: null plan", what);
+  if (n < 1) return set_err(MPDATA_EINVAL, "%s: a block of n = %lld instances", what, (long long)n);
+  if (sl0 < 0) return set_err(MPDATA_EINVAL, "%s: first instance sl0 = %lld", what, (long long)sl0);
+  if (p->multi)
+    return set_err(MPDATA_EUNSUPPORTED, "%s on a multi-GPU handle: a block is taken by the single-device plan of a shard "
+                                        "(mpdata_plan_shard_plan) with a shard-local sl0", what);
+  if (sl0 > p->ncrms - n)
+    return set_err(MPDATA_EINVAL, "%s: instances [%lld, %lld) outside the plan's %lld", what, (long long)sl0, (long long)(sl0 + n),
+                   (long long)p->ncrms);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -493,6 +591,72 @@ int mpdata_plan_export_device(mpdata_plan* p, void* f, void* flux, int first_tra
   if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_export_device before upload / import");
   DevGuard g(p->device);
   return plan_export(p, f, flux, first_tracer, ntracers, true);
+}
+
+// ---- 3d: blocks of instances
+int mpdata_plan_import_instances_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w,
+                                        const void* rho, const void* rhow, const void* adz, const void* flux, int first_tracer,
+                                        int ntracers) {
+  int rc = block_range("mpdata_plan_import_instances_device", p, sl0, n);
+  if (rc) return rc;
+  rc = tracer_range(p, first_tracer, ntracers);
+  if (rc) return rc;
+  if (!f && !u && !w && !rho && !rhow && !adz && !flux)
+    return set_err(MPDATA_EINVAL, "mpdata_plan_import_instances_device: all seven array pointers are NULL");
+  if (!p->uploaded)
+    return set_err(MPDATA_ESTATE, "mpdata_plan_import_instances_device before the plan was filled once (upload / whole import): "
+                                  "a plan is not first filled block by block");
+  if ((u && !p->have_u) || (w && !p->have_w))
+    return set_err(MPDATA_ESTATE, "mpdata_plan_import_instances_device: a block of %s while the plan holds no velocities (none "
+                                  "imported yet, or mpdata_plan_run_uw ran since): import whole u and w first",
+                   (u && !p->have_u) ? "u" : "w");
+  DevGuard g(p->device);
+  return plan_import_block(p, sl0, n, f, u, w, rho, rhow, adz, flux, first_tracer, ntracers);
+}
+
+int mpdata_plan_export_instances_device(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flux, int first_tracer, int ntracers) {
+  int rc = block_range("mpdata_plan_export_instances_device", p, sl0, n);
+  if (rc) return rc;
+  rc = tracer_range(p, first_tracer, ntracers);
+  if (rc) return rc;
+  if (!f && !flux) return set_err(MPDATA_EINVAL, "mpdata_plan_export_instances_device: f and flux are both NULL");
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_export_instances_device before upload / import");
+  DevGuard g(p->device);
+  return plan_export_block(p, sl0, n, f, flux, first_tracer, ntracers);
+}
+
+// host arrays, all tracers, synchronous: the block goes through a device staging buffer of its own size
+static int plan_download_block(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flux, int eb) {
+  int rc = block_range("mpdata_plan_download_instances", p, sl0, n);
+  if (rc) return rc;
+  if (!f && !flux) return set_err(MPDATA_EINVAL, "mpdata_plan_download_instances: f and flux are both NULL");
+  rc = plan_check(p, eb);
+  if (rc) return rc;
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_download_instances before upload / import");
+  DevGuard g(p->device);
+  const size_t fb = f ? (size_t)n * (p->nx + 6) * (p->nz - 1) * p->ntracers * eb : 0;
+  const size_t lb = flux ? (size_t)n * p->nz * p->ntracers * eb : 0;
+  if (p->bstage_bytes < fb + lb) {
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->bstage) (void)hipFree(p->bstage);
+    p->bstage = nullptr; p->bstage_bytes = 0;
+    HIP_TRY(hipMalloc(&p->bstage, fb + lb));
+    p->bstage_bytes = fb + lb;
+  }
+  void* df = f ? p->bstage : nullptr;
+  void* dl = flux ? (char*)p->bstage + fb : nullptr;
+  rc = plan_export_block(p, sl0, n, df, dl, 0, p->ntracers);
+  if (rc) return rc;
+  if (f) HIP_TRY(hipMemcpyAsync(f, df, fb, hipMemcpyDeviceToHost, p->stream));
+  if (flux) HIP_TRY(hipMemcpyAsync(flux, dl, lb, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+int mpdata_plan_download_instances(mpdata_plan* p, int64_t sl0, int64_t n, double* f, double* flux) {
+  return plan_download_block(p, sl0, n, f, flux, 8);
+}
+int mpdata_plan_download_instances_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* f, float* flux) {
+  return plan_download_block(p, sl0, n, f, flux, 4);
 }
 
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)
@@ -839,7 +1003,7 @@ int mpdata_plan_destroy(mpdata_plan* p) {
   }
   DevGuard g(p->device);
   arena_free(p->arena);
-  void* bufs[8] = {p->pf, p->pu, p->pw, p->pkc, p->pflux, p->stage, p->flux_ref, p->wpark};
+  void* bufs[9] = {p->pf, p->pu, p->pw, p->pkc, p->pflux, p->stage, p->flux_ref, p->wpark, p->bstage};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (p->ev0) (void)hipEventDestroy(p->ev0);

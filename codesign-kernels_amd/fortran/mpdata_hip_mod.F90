@@ -31,12 +31,14 @@ module mpdata_hip_mod
 #define MPDATA_C_PLAN_UPLOAD "mpdata_plan_upload_f32"
 #define MPDATA_C_PLAN_DOWNLOAD "mpdata_plan_download_f32"
 #define MPDATA_C_PERIODIC_HALO "mpdata_periodic_halo_f32_device"
+#define MPDATA_C_PLAN_DOWNLOAD_INSTANCES "mpdata_plan_download_instances_f32"
 #else
 #define MPDATA_C_ADVECT "mpdata_advect_scalar2d"
 #define MPDATA_C_PLAN_CREATE "mpdata_plan_create"
 #define MPDATA_C_PLAN_UPLOAD "mpdata_plan_upload"
 #define MPDATA_C_PLAN_DOWNLOAD "mpdata_plan_download"
 #define MPDATA_C_PERIODIC_HALO "mpdata_periodic_halo_device"
+#define MPDATA_C_PLAN_DOWNLOAD_INSTANCES "mpdata_plan_download_instances"
 #endif
 
   interface
@@ -142,6 +144,30 @@ module mpdata_hip_mod
       import :: c_int, c_ptr
       type(c_ptr), value :: plan, f, flux
       integer(c_int), value :: first, n
+    end function
+    ! ---- blocks of CRM instances [sl0, sl0+n) of a filled plan (include/mpdata_hip.h 3d; sl0 counts from 0): reference-layout
+    ! arrays of a problem of n instances (leading dimension n); device forms asynchronous (c_null_ptr: skipped), the
+    ! host form synchronous and over all tracers
+    integer(c_int) function mpdata_plan_import_instances_device_c(plan, sl0, n, f, u, w, rho, rhow, adz, flux, first, ntr) &
+        bind(C, name="mpdata_plan_import_instances_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan, f, u, w, rho, rhow, adz, flux
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: first, ntr
+    end function
+    integer(c_int) function mpdata_plan_export_instances_device_c(plan, sl0, n, f, flux, first, ntr) &
+        bind(C, name="mpdata_plan_export_instances_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan, f, flux
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: first, ntr
+    end function
+    integer(c_int) function mpdata_plan_download_instances_c(plan, sl0, n, f, flux) &
+        bind(C, name=MPDATA_C_PLAN_DOWNLOAD_INSTANCES)
+      import :: c_int, c_int64_t, c_ptr, rp
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      real(rp) :: f(*), flux(*)
     end function
     integer(c_int) function mpdata_plan_ranks_seen_c(plan) bind(C, name="mpdata_plan_ranks_seen")
       import :: c_int, c_ptr

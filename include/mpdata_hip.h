@@ -230,6 +230,37 @@ int mpdata_plan_transfer_stats(const mpdata_plan* plan, double* scatter_s, doubl
                                int64_t* scatter_bytes_per_peer, int64_t* gather_bytes_per_peer,
                                int* transport);
 
+/* ---- 3d. Blocks of CRM instances of a resident plan.  No statement of the routine couples two instances (3b), so
+ * instances [sl0, sl0+n) of a plan are a complete problem (n, nx, nz, ntracers) of their own; these calls move one in
+ * or out at the cost of the block, not of the plan (the grid of the conversion kernel covers the tiles the block
+ * touches; time per call on the MI355X: not measured yet, docs/EXPERIMENTS.md E).  The arrays are reference-layout arrays of the
+ * plan's precision that cover ONLY the block: exactly the arrays of a problem of n instances, leading dimension n,
+ * not ncrms.  Any 0 <= sl0, 1 <= n, sl0 + n <= ncrms: a block need not respect the plan's tiles, the instance pairs
+ * of fp32 plans (the partner of a split pair keeps its value), or any alignment beyond that of a real.  Both plan
+ * layouts, both precisions.
+ *   export / download: exactly the slice [sl0, sl0+n) along the instance axis of what mpdata_plan_export_device /
+ *     _download of the whole plan would return at that moment -- every element of f (halo columns included; a
+ *     PERIODIC plan hands them out wrapped) and all nz levels of flux.
+ *   import: replaces exactly those instances of the arrays given (NULL: skipped); every other instance and every
+ *     other array stay bit-identical, and the plan then behaves as if the whole arrays with the slice replaced had
+ *     been imported.  PERIODIC plans: an f block marks the halos of its tracers stale and imported halos are
+ *     ignored, as with a whole import; GIVEN plans take the block's halos as given.
+ * The device forms are asynchronous on the plan's stream; the host forms cover all tracers and are synchronous.
+ * State: a plan cannot be FIRST filled block by block -- "filled" and "holds velocities" stay facts about the whole
+ * plan: MPDATA_ESTATE until one mpdata_plan_upload / whole mpdata_plan_import_device has run, for a u or w block
+ * while the plan holds no velocities (after mpdata_plan_run_uw), and for a host form of the other precision.
+ * MPDATA_EINVAL (before any device call): null plan, n < 1, a range outside [0, ncrms), a bad tracer range, all
+ * pointers NULL.  A multi-GPU handle returns MPDATA_EUNSUPPORTED: take the single-device plan of a shard
+ * (mpdata_plan_shard_plan) and a shard-local sl0. */
+int mpdata_plan_import_instances_device(mpdata_plan* plan, int64_t sl0, int64_t n,
+                                        const void* f, const void* u, const void* w, const void* rho,
+                                        const void* rhow, const void* adz, const void* flux,
+                                        int first_tracer, int ntracers);
+int mpdata_plan_export_instances_device(mpdata_plan* plan, int64_t sl0, int64_t n, void* f, void* flux,
+                                        int first_tracer, int ntracers);
+int mpdata_plan_download_instances(mpdata_plan* plan, int64_t sl0, int64_t n, double* f, double* flux);
+int mpdata_plan_download_instances_f32(mpdata_plan* plan, int64_t sl0, int64_t n, float* f, float* flux);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
