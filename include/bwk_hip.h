@@ -15,6 +15,10 @@
  *   dvv(np,np)                      deriv%Dvv (:19-21)
  *   elem(144,nelemd)                per element, in the declaration order of type element_t
  *                                   (:23-27): Dinv(np,np,2,2) | spheremp(np,np) | tensorVisc(np,np,2,2)
+ * qtens and elem must be 32-byte aligned (else BWK_EINVAL, checked before any device call); dvv needs
+ * the alignment of a double only.  elem and dvv are not written, and nothing outside qtens is.  Limits
+ * per call: nelemd <= 65535, nlev*qsize <= 2^27 (else BWK_EUNSUPPORTED); qtens may exceed 2^31
+ * elements (tests/test_bwk_edges.py).
  * (a Fortran caller passes `elem` itself when element_t is a SEQUENCE / bind(C) type, else a
  * packed copy).
  *

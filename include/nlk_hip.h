@@ -20,8 +20,23 @@
  * For every edge and level:  highOrderFlx = sum over i = 1..nAdvCellsForEdge, for the cells whose
  * [minLevelCell, maxLevelCell] contains the level, of
  *   tracerCur(k,cell) * (normalThicknessFlux*advMaskHighOrder) * (advCoefs + advCoefs3rd*coef3rdOrder*sign)
- * in the reference's order.  A cell index outside 1..nCells contributes nothing (the reference
- * would read out of bounds).
+ * in the reference's order.  Where the reference's behaviour is undefined, the library promises
+ * (tests/test_nlk_edges.py):
+ *   - a cell index outside 1..nCells contributes nothing (the reference would read out of bounds):
+ *     the result is the reference loop on the row with that slot deleted;
+ *   - nAdvCellsForEdge is clipped to 0..nAdv: a count <= 0 gives +0.0 on every level, a count above
+ *     nAdv reads nAdv slots (the reference would read past the row);
+ *   - maxLevelCell above nVertLevels (above nvldim too) means nVertLevels; maxLevelCell <= 0,
+ *     minLevelCell > maxLevelCell and minLevelCell > nVertLevels are empty ranges; minLevelCell <= 0
+ *     means 1;
+ *   - a level outside a cell's range is SKIPPED as in the reference, whatever tracerCur holds there:
+ *     fill values (-1e34), huge values and NaN in masked levels, in the padding rows
+ *     nVertLevels+1..nvldim of tracerCur, normalThicknessFlux and advMaskHighOrder, and in whole
+ *     columns of cells with an empty range never reach highOrderFlx;
+ *   - the inputs are not written; highOrderFlx is written on levels 1..nVertLevels only; any base
+ *     alignment that the element types allow is accepted (the 16-byte forms need 16-byte aligned
+ *     double arrays, an even nvldim and a tracerCur below 4 GiB, else the 8-byte form runs; the
+ *     form is not observable through this interface, the results are the same).
  *
  * Functions return 0, a negative NLK_E* code, or a positive hipError_t; nlk_last_error() has
  * text.  No CPU fallback.
@@ -58,8 +73,9 @@ int nlk_set_variant(int variant); /* returns the previous one; default: NLK_VARI
 int nlk_get_variant(void);
 /* kernel form: -1 automatic (default; NLK_KERNEL=0 / 1 in the environment presets it), 0 one level per
  * lane (8-byte accesses), 1 two levels per lane (16-byte accesses: half the vector-memory instructions;
- * needs an even nvldim and 16-byte aligned arrays, else form 0 is taken).  Same results.  Returns the
- * previous setting. */
+ * needs an even nvldim, 16-byte aligned arrays and nCells*nvldim*8 < 4 GiB, else form 0 is taken), 2 the
+ * same with the per-cell bookkeeping on the vector unit (needs nAdv <= 64 as well, else form 1).  Same
+ * results.  Returns the previous setting. */
 int nlk_set_kernel(int mode);
 /* minimal HBM traffic of one call: every input array read once, highOrderFlx written once
  * (the gather re-reads of tracerCur hit in cache: 10 x 100 x 8 B per edge from 2.2 MB) */

@@ -11,6 +11,8 @@ import tempfile
 
 import numpy as np
 
+from oracle.rounding import GAMMA_U, gamma  # noqa: F401  (the bound gamma(PATH_ROUNDINGS) * S, biharmonic_hi below)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libbwk_oracle.so")
 REF_DIR = os.path.join(HERE, "_ref")
@@ -105,3 +107,49 @@ def run_reference(nelemd):
 def l2norm(a, b):
     """The reference's own metric (reference :69-73)."""
     return float(np.sqrt(np.sum((a - b) ** 2) / np.sum(b ** 2)))
+
+
+# ------------------------------------------------------------------ a second, independent reference
+# Rounded operations on the longest input-to-output path of the reference expression (reference :109-200):
+#   gradient_sphere      Dvv*s (1), four additions of the running sum (5), *rrearth (6);
+#                        Dinv*v (7), the addition of the two products (8)
+#   laplace_sphere_wk    oldgrads*tensorVisc (9), the addition (10)
+#   divergence_sphere_wk Dinv*v (11), the addition (12); spheremp*vtemp (13), *Dvv (14), the addition inside
+#                        the parentheses (15), *rrearth (16), four subtractions from the running div (20)
+# rrearth is the same double in every implementation (the fp32 literal widened), so it carries no error.  Two of
+# the 20 (the first addition of each running sum: 0 + x) are exact; that margin covers the np.longdouble
+# reference's own error gamma_64(20) * S = 2^-11 gamma_53(20) * S.
+PATH_ROUNDINGS = 20
+
+
+def _laplace_ld(q, dvv, elem, rr):
+    """laplace_sphere_wk on q(4,4,nslab,nelemd) in the dtype of its arguments, whole-array einsum form; with
+    non-negative arguments and sign=+1 it is the sum S of absolute values of every term"""
+    di = elem[0:64].reshape((4, 4, 2, 2, -1), order="F")[:, :, :, :, None, :]     # Dinv(i,j,c,d) -> (i,j,c,d,1,e)
+    sp = elem[64:80].reshape((4, 4, -1), order="F")[:, :, None, :]
+    tv = elem[80:144].reshape((4, 4, 2, 2, -1), order="F")[:, :, :, :, None, :]
+    v1 = np.einsum("il,ijse->ljse", dvv, q) * rr                                   # :121, :124
+    v2 = np.einsum("il,jise->jlse", dvv, q) * rr                                   # :122, :125
+    ds1 = di[:, :, 0, 0] * v1 + di[:, :, 1, 0] * v2                                # :130
+    ds2 = di[:, :, 0, 1] * v1 + di[:, :, 1, 1] * v2                                # :131
+    g1 = ds1 * tv[:, :, 0, 0] + ds2 * tv[:, :, 0, 1]                               # :175-176
+    g2 = ds1 * tv[:, :, 1, 0] + ds2 * tv[:, :, 1, 1]                               # :177-178
+    p1 = sp * (di[:, :, 0, 0] * g1 + di[:, :, 0, 1] * g2)                          # :147, spheremp(j,n)*vtemp(j,n,1)
+    p2 = sp * (di[:, :, 1, 0] * g1 + di[:, :, 1, 1] * g2)                          # :148, spheremp(m,j)*vtemp(m,j,2)
+    return (np.einsum("jnse,mj->mnse", p1, dvv) + np.einsum("mjse,nj->mnse", p2, dvv)) * rr   # :155-156 (without the sign)
+
+
+def biharmonic_hi(inp):
+    """biharmonic_wk_scalar (reference :109-200) restated in np.longdouble with einsum; shares no code with
+    bwk_oracle.c.  Returns (result, S), both shaped like qtens: S is the same computation on |dvv|, |elem|,
+    |qtens| with every subtraction turned into an addition, so that any fp64 evaluation `out` of the reference
+    expression satisfies |out - result| <= gamma(PATH_ROUNDINGS) * S elementwise."""
+    L = np.longdouble
+    assert np.finfo(L).nmant >= 63, "np.longdouble is not wider than double here"
+    rr = L(np.float64(np.float32(0.00000016666666666666)))                         # reference :14, fp32 literal widened
+    shape = inp["qtens"].shape
+    q = inp["qtens"].astype(L).reshape((4, 4, shape[2] * shape[3], shape[4]), order="F")
+    dvv, elem = inp["dvv"].astype(L), inp["elem"].astype(L)
+    hi = -_laplace_ld(q, dvv, elem, rr)
+    S = _laplace_ld(np.abs(q), np.abs(dvv), np.abs(elem), rr)
+    return hi.reshape(shape, order="F"), S.reshape(shape, order="F")
