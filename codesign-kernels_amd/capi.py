@@ -95,6 +95,12 @@ def lib():
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [vp]
+        L.mpdata_set_tall_columns.restype = ci
+        L.mpdata_set_tall_columns.argtypes = [ci]
+        L.mpdata_plan_level_windows.restype = ci
+        L.mpdata_plan_level_windows.argtypes = [vp]
+        L.mpdata_level_window.restype = ci
+        L.mpdata_level_window.argtypes = [ci, ci] + [ctypes.POINTER(ci)] * 4
         L.mpdata_set_plan_layout.restype = ci
         L.mpdata_set_plan_layout.argtypes = [ci]
         L.mpdata_plan_set_boundary.restype = ci
@@ -206,6 +212,22 @@ def set_tile(t):
 def set_plan_layout(layout):
     """Default device layout of new plans (LAYOUT_*); returns the previous one."""
     return lib().mpdata_set_plan_layout(int(layout))
+
+
+def set_tall_columns(on):
+    """Level windows for new plans (and device / host calls) with nz > 238 (include/mpdata_hip.h section 3e); returns
+    the previous setting.  Off by default; MPDATA_TALL_COLUMNS=1 in the environment presets it."""
+    return lib().mpdata_set_tall_columns(int(on))
+
+
+def level_window(nz, h):
+    """(W, k0, nz_w, own0, own1): window h of the W level windows of a column of nz levels (mpdata_level_window) --
+    a problem of nz_w levels on the tall levels k0+1 .. k0+nz_w-1 (+ its ghost level) that owns own0 .. own1."""
+    v = [ctypes.c_int() for _ in range(4)]
+    W = lib().mpdata_level_window(int(nz), int(h), *[ctypes.byref(x) for x in v])
+    if W < 1:
+        raise MpdataError(W, lib().mpdata_last_error().decode())
+    return (W,) + tuple(x.value for x in v)
 
 
 def shard_range(ncrms, ngpus, g):
@@ -393,7 +415,8 @@ class Plan:
     """Library-owned device state + stream (reference: `!$acc enter data`,
     `update device`, `wait`, `update host`; :105-110, :237-242).  Arrays cross
     the boundary in the reference layout; the plan keeps them in its own layout
-    (`layout`: LAYOUT_WAVEMAJOR for nz <= 238 -- fp32: an even ncrms --, include/mpdata_hip.h 3)."""
+    (`layout`: LAYOUT_WAVEMAJOR for nz <= 238 -- fp32: an even ncrms --, include/mpdata_hip.h 3; above 238 levels
+    with set_tall_columns(1): as `level_windows` overlapping windows of such a plan, 3e)."""
 
     def __init__(self, ncrms, nx, nz, ntracers=1, dtype=np.float64, ngpus=None, devices=None):
         """ngpus / devices: a multi-GPU plan (include/mpdata_hip.h section 3b) -- the problem
@@ -446,6 +469,11 @@ class Plan:
     @property
     def layout(self):
         return lib().mpdata_plan_layout(self._p)
+
+    @property
+    def level_windows(self):
+        """W: the level windows a column of the plan is cut into (set_tall_columns, nz > 238); 1 for any other plan"""
+        return lib().mpdata_plan_level_windows(self._p)
 
     @property
     def device(self):

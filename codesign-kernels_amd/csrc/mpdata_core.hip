@@ -395,6 +395,16 @@ int serpentine() {
   }
   return g_serpentine;
 }
+// Tall columns (include/mpdata_hip.h 3e): new plans with nz > 238 become windowed plans.  OFF by default;
+// MPDATA_TALL_COLUMNS=1 or mpdata_set_tall_columns(1) turns it on.
+int g_tall = -1;
+int tall_columns() {
+  if (g_tall < 0) {
+    const char* e = getenv("MPDATA_TALL_COLUMNS");
+    g_tall = (e && atoi(e) != 0) ? 1 : 0;
+  }
+  return g_tall;
+}
 // test switches of the wave-major launch (MPDATA_WMF_*): from the environment once, or set
 int g_wm_flags = -1;
 int wm_flags() {
@@ -523,6 +533,11 @@ int mpdata_set_wm_flags(int flags) {
 int mpdata_set_serpentine(int on) {
   const int prev = serpentine();
   if (on == 0 || on == 1) g_serpentine = on;
+  return prev;
+}
+int mpdata_set_tall_columns(int on) {
+  const int prev = tall_columns();
+  if (on == 0 || on == 1) g_tall = on;
   return prev;
 }
 int mpdata_set_tile(int tile) {

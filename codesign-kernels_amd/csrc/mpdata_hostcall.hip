@@ -206,7 +206,7 @@ int mpdata_advect_scalar2d(int64_t ncrms, int nx, int nz, int ntracers, double* 
     // (nz > 64: a device call may go through a plan kept per thread and SHAPE -- chunks of two widths would rebuild it
     //  twice per call, and the transfers bound this path anyway: only where nothing else runs the shape)
     rc = advect_device<double>(cw, nx, nz, ntracers, b.f, b.u, b.w, b.rho, b.rhow, b.adz, b.flux, (void*)s_in, -1,
-                               !piped || nx > 140);
+                               !piped || nx > 140 || (nz > 238 && tall_columns()));   // (level windows: include/mpdata_hip.h 3e)
     if (rc) break;
     if (c == 0) mark("first chunk: kernel queued");
     if (!piped) {

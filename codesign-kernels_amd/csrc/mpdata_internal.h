@@ -45,6 +45,7 @@ int variant();                 // MPDATA_VARIANT_*
 int tile_override();           // kernel tiling id forced by MPDATA_TILE / mpdata_set_tile; -1 = automatic
 int plan_layout_default();     // MPDATA_LAYOUT_* new plans get
 int serpentine();              // serpentine tile order of wave-major plans (off by default)
+int tall_columns();            // nz > 238 as windowed plans (mpdata_set_tall_columns; off by default)
 int wm_flags();                // MPDATA_WMF_* test switches of the wave-major launch
 int wm_wpb();                  // waves (tiles) per workgroup of the wave-major kernels
 unsigned long long* debug_buffer();   // diagnostic builds: per-wave stamp buffer (mpdata_set_debug_buffer), else null
@@ -89,8 +90,8 @@ extern template int advect_device<float>(int64_t, int, int, int, float*, const f
 
 // frees the calling thread's park buffers of the EXACT device calls (mpdata_core.hip: park_buffer)
 void park_buffers_release();
-// calls on reference-layout device arrays at 65 <= nz <= 238 through a wave-major plan kept per host thread
-// (mpdata_plan.hip); eb = bytes per real
+// calls on reference-layout device arrays at 65 <= nz <= 238 (nz > 238: with tall_columns() on, a windowed plan)
+// through a wave-major plan kept per host thread (mpdata_plan.hip); eb = bytes per real
 bool staged_call_applies(int64_t ncrms, int nz, int eb);
 int staged_device_call(int eb, int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* u, const void* w, const void* rho,
                        const void* rhow, const void* adz, void* flux, void* stream, int var);

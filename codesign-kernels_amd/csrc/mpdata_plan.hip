@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "mpdata_internal.h"
+#include "mpdata_windows.h"
 
 using namespace mpd;
 
@@ -89,6 +90,16 @@ struct mpdata_plan {
   // per tracer: f's halo columns hold copies of its interior (set by the halo kernel; cleared by an import of f and
   // by every run, whose kernels leave first-pass values there)
   unsigned char* halo_ok;
+  // windowed plans (include/mpdata_hip.h 3e; nz > 238): `inner` is an ordinary wave-major plan whose ncrms * W instances
+  // are the W level windows (mpdata_windows.h) of this plan's instances, window index fastest.  It runs on this plan's
+  // stream with this plan's boundary mode and shares halo_ok; of the fields above this plan itself uses the sizes,
+  // stage (tall reference-layout staging of host transfers), bstage, flux_ref (level nz), the stream, the events
+  // and the state flags.
+  mpdata_plan* inner;
+  int W;
+  // per tracer: every non-owned level of every window of f holds its owner's value (set by a whole import of f and by
+  // the seam refresh; cleared by every run, which leaves the 3 + 3 margin levels of a seam wrong)
+  unsigned char* seam_ok;
   mpdata_multi* multi;  // != null: a multi-GPU plan (mpdata_multi.hip); nothing else above is used
 };
 
@@ -139,6 +150,21 @@ int wm_lwt_for(int nz) {
   return need <= 16 ? 16 : need <= 32 ? 32 : 0;
 }
 
+// ---- windowed plans: the inner plan follows the outer one's stream and boundary mode
+mpdata_plan* win_inner(mpdata_plan* p) {
+  p->inner->stream = p->stream;
+  p->inner->boundary = p->boundary;
+  return p->inner;
+}
+// one array of instances [sl0, sl0 + n) between a tall reference-layout array of leading dimension n and the windows
+MpdataWindowJob win_job(const mpdata_plan* p, int which, void* ref, int64_t sl0, int64_t n, int first_tracer, int ntr) {
+  MpdataWindowJob b;
+  b.j = wm_job(p->inner, which, ref, first_tracer, ntr);
+  b.j.ref_tstride = which == 0 ? (long long)n * (p->nx + 6) * (p->nz - 1) : which == 6 ? (long long)n * p->nz : 0;
+  b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb; b.nz = p->nz;
+  return b;
+}
+
 int plan_check(const mpdata_plan* p, int eb) {
   if (!p) return set_err(MPDATA_EINVAL, "null plan");
   if (p->eb != eb) return set_err(MPDATA_ESTATE, "plan precision (%d-byte reals) does not match the call", p->eb);
@@ -165,6 +191,103 @@ bool legacy_convert() {
   return v;
 }
 
+// Windowed plans: tall reference-layout arrays of instances [sl0, sl0 + n) (leading dimension n; host arrays: the whole
+// plan only) -> the windows (split: every level every window holds, so a whole import of f leaves fresh seams; after a
+// block import the seams of the plan are as fresh as they were).  flux is also kept tall (level nz).
+int win_import(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w, const void* rho,
+               const void* rhow, const void* adz, const void* flux, int first, int count, bool dev) {
+  const int eb = p->eb;
+  const bool whole = n == p->ncrms;
+  const size_t f1 = (size_t)n * (p->nx + 6) * (p->nz - 1);   // elements of one tracer of f
+  win_inner(p);
+  if (!dev) {
+    const int rs = plan_stage(p);
+    if (rs) return rs;
+  }
+  auto one = [&](int which, const void* src, size_t elems, int tr, int ntr) -> int {
+    void* ref = const_cast<void*>(src);
+    if (!dev) {
+      HIP_TRY(hipMemcpyAsync(p->stage, src, elems * eb, hipMemcpyHostToDevice, p->stream));
+      ref = p->stage;
+    }
+    HIP_TRY(mpdata_window_convert(win_job(p, which, ref, sl0, n, tr, ntr), true, p->stream));
+    return 0;
+  };
+  int rc = 0;
+  if (f) {
+    memset(p->halo_ok + first, 0, (size_t)count);   // (imported halos are not trusted: a periodic plan wraps again)
+    if (dev) rc = one(0, f, 0, first, count);
+    else for (int t = 0; t < count && !rc; ++t) rc = one(0, (const char*)f + (size_t)t * f1 * eb, f1, first + t, 1);
+    if (!rc && whole) memset(p->seam_ok + first, 1, (size_t)count);
+  }
+  if (!rc && u) { rc = one(1, u, p->sz.u, 0, 1); if (!rc && whole) p->have_u = true; }
+  if (!rc && w) { rc = one(2, w, p->sz.w, 0, 1); if (!rc && whole) p->have_w = true; }
+  if (!rc && rho) rc = one(3, rho, p->sz.k, 0, 1);
+  if (!rc && rhow) rc = one(4, rhow, p->sz.kz, 0, 1);
+  if (!rc && adz) rc = one(5, adz, p->sz.k, 0, 1);
+  if (!rc && flux) {
+    char* fr = (char*)p->flux_ref + (size_t)first * p->sz.kz * eb;
+    if (whole) {
+      HIP_TRY(hipMemcpyAsync(fr, flux, p->sz.kz * count * eb, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, p->stream));
+      HIP_TRY(mpdata_window_convert(win_job(p, 6, fr, 0, n, first, count), true, p->stream));
+    } else {
+      HIP_TRY(mpdata_layout_copy_rows(fr + (size_t)sl0 * eb, flux, eb, n, (long long)p->nz * count, p->ncrms, n, p->stream));
+      HIP_TRY(mpdata_window_convert(win_job(p, 6, const_cast<void*>(flux), sl0, n, first, count), true, p->stream));
+    }
+  }
+  return rc;
+}
+
+// ... and back (merge: the owned levels of every window; flux level nz from the tall copy).  The caller has wrapped
+// the halos of a periodic plan.
+int win_export(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flux, int first, int count, bool dev) {
+  const int eb = p->eb, nz = p->nz, nzm = nz - 1;
+  const bool whole = n == p->ncrms;
+  const size_t f1 = (size_t)n * (p->nx + 6) * nzm;
+  win_inner(p);
+  if (f) {
+    if (dev) {
+      HIP_TRY(mpdata_window_convert(win_job(p, 0, f, sl0, n, first, count), false, p->stream));
+    } else {
+      const int rs = plan_stage(p);
+      if (rs) return rs;
+      for (int t = 0; t < count; ++t) {
+        HIP_TRY(mpdata_window_convert(win_job(p, 0, p->stage, sl0, n, first + t, 1), false, p->stream));
+        HIP_TRY(hipMemcpyAsync((char*)f + (size_t)t * f1 * eb, p->stage, f1 * eb, hipMemcpyDeviceToHost, p->stream));
+      }
+    }
+  }
+  if (flux) {
+    char* fr = (char*)p->flux_ref + (size_t)first * p->sz.kz * eb;
+    if (whole) {
+      HIP_TRY(mpdata_window_convert(win_job(p, 6, fr, 0, n, first, count), false, p->stream));
+      HIP_TRY(hipMemcpyAsync(flux, fr, p->sz.kz * count * eb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, p->stream));
+    } else {
+      HIP_TRY(mpdata_window_convert(win_job(p, 6, flux, sl0, n, first, count), false, p->stream));
+      HIP_TRY(mpdata_layout_copy_rows((char*)flux + (size_t)nzm * n * eb, fr + ((size_t)nzm * p->ncrms + (size_t)sl0) * eb, eb, n, count,
+                                      (long long)n * nz, (long long)p->ncrms * nz, p->stream));
+    }
+  }
+  return 0;
+}
+
+// Windowed plans: the seam refresh in front of a run -- one launch over the span of tracers [first, first + count)
+// whose seams a run has left stale; nothing right after an import.
+int plan_seams(mpdata_plan* p, int first, int count) {
+  if (!p->inner) return 0;
+#ifdef MPDATA_TALL_NOSEAMS   // diagnostic builds only: no refresh, WRONG results from the second run on (docs/EXPERIMENTS.md)
+  return 0;
+#endif
+  int lo = first, hi = first + count;
+  while (lo < hi && p->seam_ok[lo]) ++lo;
+  while (hi > lo && p->seam_ok[hi - 1]) --hi;
+  if (lo == hi) return 0;
+  win_inner(p);
+  HIP_TRY(mpdata_window_seams(win_job(p, 0, nullptr, 0, p->ncrms, lo, hi - lo), p->stream));
+  memset(p->seam_ok + lo, 1, (size_t)(hi - lo));
+  return 0;
+}
+
 // Arrays in the reference layout -> the plan.  `dev` says where the pointers live.  Null
 // pointers are skipped (the plan keeps what it has).  f / flux cover `count` tracers.
 int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, const void* rho,
@@ -172,6 +295,7 @@ int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, con
   const int eb = p->eb;
   const size_t f1 = p->sz.f / p->ntracers;  // elements of one tracer of f
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (p->inner) return win_import(p, 0, p->ncrms, f, u, w, rho, rhow, adz, flux, first, count, dev);
   if (f) memset(p->halo_ok + first, 0, (size_t)count);   // (imported halos are not trusted: a periodic plan wraps again)
   if (p->layout == MPDATA_LAYOUT_REFERENCE) {
     if (f) HIP_TRY(hipMemcpyAsync((char*)p->f + first * f1 * eb, f, f1 * count * eb, kind, p->stream));
@@ -244,6 +368,7 @@ int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, con
 // already (mpdata_layout_periodic_halo_*: one launch over the unmarked span of the range); a no-op in GIVEN mode.
 int plan_wrap_f(mpdata_plan* p, int first, int count) {
   if (p->boundary != MPDATA_BOUNDARY_PERIODIC) return 0;
+  if (p->inner) return plan_wrap_f(win_inner(p), first, count);   // (every window, every level it holds: halo_ok is shared)
   int lo = first, hi = first + count;
   while (lo < hi && p->halo_ok[lo]) ++lo;
   while (hi > lo && p->halo_ok[hi - 1]) --hi;
@@ -267,6 +392,7 @@ int plan_export(mpdata_plan* p, void* f, void* flux, int first, int count, bool 
   }
   const size_t f1 = p->sz.f / p->ntracers;
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (p->inner) return win_export(p, 0, p->ncrms, f, flux, first, count, dev);
   if (p->layout == MPDATA_LAYOUT_REFERENCE) {
     if (f) HIP_TRY(hipMemcpyAsync(f, (char*)p->f + first * f1 * eb, f1 * count * eb, kind, p->stream));
     if (flux) HIP_TRY(hipMemcpyAsync(flux, (char*)p->flux + first * p->sz.kz * eb, p->sz.kz * count * eb, kind, p->stream));
@@ -316,6 +442,7 @@ MpdataBlockJob wm_block_job(const mpdata_plan* p, int which, void* ref, int64_t 
 int plan_import_block(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w, const void* rho,
                       const void* rhow, const void* adz, const void* flux, int first, int count) {
   const int eb = p->eb, nx = p->nx, nz = p->nz, nzm = nz - 1;
+  if (p->inner) return win_import(p, sl0, n, f, u, w, rho, rhow, adz, flux, first, count, true);
   if (f) memset(p->halo_ok + first, 0, (size_t)count);   // (as a whole import: a periodic plan wraps these tracers again)
   // the slab of rows x n reals at instance sl0 of a reference-layout array of the plan
   auto slab = [&](void* dst, const void* src, long long rows) -> int {
@@ -359,7 +486,9 @@ int plan_export_block(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flu
     return 0;
   };
   int rc = 0;
-  if (p->layout == MPDATA_LAYOUT_REFERENCE) {
+  if (p->inner) {
+    rc = win_export(p, sl0, n, f, flux, first, count, true);
+  } else if (p->layout == MPDATA_LAYOUT_REFERENCE) {
     const size_t f1 = p->sz.f / p->ntracers;
     if (f) rc = slab(f, (char*)p->f + first * f1 * eb, (long long)(nx + 6) * nzm * count);
     if (!rc && flux) rc = slab(flux, (char*)p->flux + first * p->sz.kz * eb, (long long)nz * count);
@@ -411,8 +540,11 @@ static int plan_create(int64_t ncrms, int nx, int nz, int ntracers, mpdata_plan*
   // wave-major: fp64, and fp32 with an even ncrms (two adjacent instances per lane = 8-byte elements)
   const bool wmaj = (eb == 8 || (ncrms & 1) == 0) && wm_lps_for(nz) != 0 &&
                     plan_layout_default() == MPDATA_LAYOUT_WAVEMAJOR && tile_override() < 0;
+  // windowed (include/mpdata_hip.h 3e): above the tallest wave-major form, when switched on, under the same conditions
+  const bool windowed = tall_columns() && nz > MPDATA_WM_NZ_MAX && (eb == 8 || (ncrms & 1) == 0) &&
+                        plan_layout_default() == MPDATA_LAYOUT_WAVEMAJOR && tile_override() < 0;
   MpdataTileInfo t;
-  if (!wmaj) {
+  if (!wmaj && !windowed) {
     rc = choose_tile(var, ncrms, nx, nz, &t, eb);
     if (rc) return rc;
   }
@@ -420,7 +552,8 @@ static int plan_create(int64_t ncrms, int nx, int nz, int ntracers, mpdata_plan*
   if (!p) return set_err(MPDATA_EINVAL, "out of host memory");
   p->ncrms = ncrms; p->nx = nx; p->nz = nz; p->ntracers = ntracers; p->eb = eb;
   p->variant = var;
-  p->layout = wmaj ? MPDATA_LAYOUT_WAVEMAJOR : MPDATA_LAYOUT_REFERENCE;
+  p->layout = (wmaj || windowed) ? MPDATA_LAYOUT_WAVEMAJOR : MPDATA_LAYOUT_REFERENCE;
+  p->W = 1;
   p->sz = sizes_of(ncrms, nx, nz, ntracers);
   p->halo_ok = (unsigned char*)calloc((size_t)ntracers, 1);
   if (!p->halo_ok) {
@@ -428,7 +561,30 @@ static int plan_create(int64_t ncrms, int nx, int nz, int ntracers, mpdata_plan*
     return set_err(MPDATA_EINVAL, "out of host memory");
   }
   hipError_t e = hipGetDevice(&p->device);
-  if (e == hipSuccess && !wmaj) {
+  if (e == hipSuccess && windowed) {
+    int k0, nz_w, own0, own1;
+    p->W = mpd_level_window(nz, 0, &k0, &nz_w, &own0, &own1);
+    p->seam_ok = (unsigned char*)calloc((size_t)ntracers, 1);
+    if (!p->seam_ok) rc = set_err(MPDATA_EINVAL, "out of host memory");
+    if (!rc && ncrms > INT64_MAX / p->W) rc = set_err(MPDATA_EINVAL, "ncrms = %lld times %d level windows overflows", (long long)ncrms, p->W);
+    if (!rc) rc = plan_create(ncrms * p->W, nx, nz_w, ntracers, &p->inner, eb, var);
+    if (!rc && (p->inner->layout != MPDATA_LAYOUT_WAVEMAJOR || p->inner->slp != 1))
+      rc = set_err(MPDATA_EINVAL, "internal: the windows of a tall plan are not one-instance tiles of a wave-major plan");
+    if (rc) {
+      mpdata_plan_destroy(p);
+      return rc;
+    }
+    // the inner plan runs on this plan's stream, is timed by this plan's events and shares the halo bytes
+    (void)hipStreamDestroy(p->inner->stream);
+    p->inner->stream = nullptr; p->inner->own_stream = false; p->inner->timing = false;
+    free(p->inner->halo_ok);
+    p->inner->halo_ok = p->halo_ok;
+    const size_t f1 = p->sz.f / ntracers;
+    p->stage_elems = f1 > p->sz.w ? f1 : p->sz.w;
+    e = hipMalloc(&p->flux_ref, p->sz.kz * ntracers * eb);
+    if (e == hipSuccess) e = hipMemset(p->flux_ref, 0, p->sz.kz * ntracers * eb);
+  }
+  if (e == hipSuccess && !wmaj && !windowed) {
     const size_t nb[7] = {p->sz.f * eb, p->sz.u * eb, p->sz.w * eb, p->sz.k * eb, p->sz.kz * eb, p->sz.k * eb,
                           p->sz.kz * ntracers * eb};
     e = arena_alloc(p->arena, nb);
@@ -519,6 +675,7 @@ extern "C++" int mpdata_plan_zero_flux_internal(mpdata_plan* p) {
   DevGuard g(p->device);
   void* fl = p->layout == MPDATA_LAYOUT_REFERENCE ? p->flux : p->flux_ref;
   HIP_TRY(hipMemsetAsync(fl, 0, p->sz.kz * p->ntracers * p->eb, p->stream));
+  if (p->inner) return mpdata_plan_zero_flux_internal(win_inner(p));
   if (p->layout == MPDATA_LAYOUT_WAVEMAJOR)
     HIP_TRY(hipMemsetAsync(p->pflux, 0, (size_t)p->ntiles * p->chunk * p->ntracers * 8, p->stream));
   return 0;
@@ -678,6 +835,11 @@ static int plan_flux_finish(mpdata_plan* p, const MpdataWmArgs& a, int count) {
 static int plan_launch(mpdata_plan* p, int first, int count, const void* u_ref = nullptr, const void* w_ref = nullptr,
                        bool uw_conv = false) {
   int rc = 0;
+  if (p->inner) {   // windowed: the plan kernel on the windows; it leaves the margin levels of every seam wrong
+    if (u_ref) return set_err(MPDATA_EINVAL, "internal: a windowed plan takes u, w through the split");
+    memset(p->seam_ok + first, 0, (size_t)count);
+    return plan_launch(win_inner(p), first, count);
+  }
   if (p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
     MpdataWmArgs a;
     a.f = (double*)p->pf + (long long)first * p->ntiles * p->tile_elems;
@@ -755,7 +917,8 @@ int mpdata_plan_run_tracers(mpdata_plan* p, int first, int count) {
                                   "ran since -- it leaves none behind): import u and w first");
   DevGuard g(p->device);
   if (p->timing) HIP_TRY(hipEventRecord(p->ev0, p->stream));
-  rc = plan_wrap_f(p, first, count);
+  rc = plan_seams(p, first, count);   // (windowed plans; in front of the wrap: the two commute, the order is fixed)
+  if (!rc) rc = plan_wrap_f(p, first, count);
   memset(p->halo_ok + first, 0, (size_t)count);   // (the run leaves first-pass values in the halos)
   if (!rc) rc = plan_launch(p, first, count);
   if (rc) return rc;
@@ -796,7 +959,7 @@ int mpdata_plan_run_uw(mpdata_plan* p, int first, int count, const void* u, cons
   // (16-byte row pieces: even ncrms, 16-byte aligned bases; 32-bit offsets: arrays below 4 GiB);
   // MPDATA_RUN_UW=import forces the conversion path (tests, A/B)
   static const bool force_import = getenv("MPDATA_RUN_UW") && !strcmp(getenv("MPDATA_RUN_UW"), "import");
-  const bool ring = p->layout == MPDATA_LAYOUT_WAVEMAJOR && p->eb == 8 && (p->ncrms & 1) == 0 && p->lps <= 64 &&
+  const bool ring = p->layout == MPDATA_LAYOUT_WAVEMAJOR && !p->inner && p->eb == 8 && (p->ncrms & 1) == 0 && p->lps <= 64 &&
                     (((uintptr_t)u | (uintptr_t)w) & 15) == 0 &&
                     (double)p->ncrms * (p->nx + 5) * p->nz * 8.0 < 4294967000.0 && !force_import;
   // POST-CONDITION, the same on every path (which one runs depends on alignment, parity of ncrms, nz,
@@ -804,7 +967,8 @@ int mpdata_plan_run_uw(mpdata_plan* p, int first, int count, const void* u, cons
   // plan's u, w (they would be stale), the other paths overwrite them (they would be the new ones):
   // neither is promised, mpdata_plan_run returns MPDATA_ESTATE until u, w are imported again.
   p->have_u = p->have_w = false;
-  rc = plan_wrap_f(p, first, count);
+  rc = plan_seams(p, first, count);
+  if (!rc) rc = plan_wrap_f(p, first, count);
   if (rc) return rc;
   memset(p->halo_ok + first, 0, (size_t)count);
   if (ring && count == 1) {
@@ -887,6 +1051,22 @@ int mpdata_plan_set_timing(mpdata_plan* p, int on) {
   return 0;
 }
 int mpdata_plan_layout(const mpdata_plan* p) { return p ? p->layout : MPDATA_EINVAL; }
+// level windows (include/mpdata_hip.h 3e)
+int mpdata_plan_level_windows(const mpdata_plan* p) {
+  if (!p) return MPDATA_EINVAL;
+  if (p->multi) return mpdata_plan_level_windows(mpdata_multi_sub(p->multi, 0));
+  return p->inner ? p->W : 1;
+}
+int mpdata_level_window(int nz, int h, int* k0, int* nz_w, int* own0, int* own1) {
+  int a = 0, b = 0, c = 0, d = 0;
+  const int W = mpd_level_window(nz, h, &a, &b, &c, &d);
+  if (W < 1) return set_err(MPDATA_EINVAL, "mpdata_level_window: nz = %d, window %d", nz, h);
+  if (k0) *k0 = a;
+  if (nz_w) *nz_w = b;
+  if (own0) *own0 = c;
+  if (own1) *own1 = d;
+  return W;
+}
 int mpdata_plan_device(const mpdata_plan* p) { return p ? p->device : MPDATA_EINVAL; }
 
 // Lateral boundary mode.  PERIODIC: f's halo columns are refreshed from the interior in front of every run and every
@@ -995,7 +1175,13 @@ int mpdata_plan_transfer_stats(const mpdata_plan* p, double* scatter_s, double* 
 
 int mpdata_plan_destroy(mpdata_plan* p) {
   if (!p) return 0;
+  if (p->inner) {   // (shares halo_ok and the stream)
+    if (p->inner->halo_ok == p->halo_ok) p->inner->halo_ok = nullptr;
+    if (!p->inner->own_stream) p->inner->stream = nullptr;
+    mpdata_plan_destroy(p->inner);
+  }
   free(p->halo_ok);
+  free(p->seam_ok);
   if (p->multi) {
     const int rc = mpdata_multi_destroy(p->multi);
     free(p);
@@ -1037,7 +1223,7 @@ thread_local StagedPlan t_staged;
 extern "C++" void mpd::staged_plan_release() { t_staged.release(); }
 extern "C++" bool mpd::staged_call_applies(int64_t ncrms, int nz, int eb) {
   static const bool direct = getenv("MPDATA_DEVICE_CALL") && !strcmp(getenv("MPDATA_DEVICE_CALL"), "direct");
-  return !direct && nz > 64 && wm_lps_for(nz) != 0 && (eb == 8 || (ncrms & 1) == 0) &&
+  return !direct && nz > 64 && (wm_lps_for(nz) != 0 || tall_columns()) && (eb == 8 || (ncrms & 1) == 0) &&
          plan_layout_default() == MPDATA_LAYOUT_WAVEMAJOR && tile_override() < 0;
 }
 extern "C++" int mpd::staged_device_call(int eb, int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* u, const void* w,

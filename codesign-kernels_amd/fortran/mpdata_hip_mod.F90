@@ -22,6 +22,9 @@ module mpdata_hip_mod
   public :: MPDATA_BOUNDARY_GIVEN, MPDATA_BOUNDARY_PERIODIC
   public :: mpdata_plan_set_boundary_c, mpdata_plan_boundary_c, mpdata_periodic_halo_device_c
   integer(c_int), parameter :: MPDATA_BOUNDARY_GIVEN = 0, MPDATA_BOUNDARY_PERIODIC = 1
+  ! tall columns (include/mpdata_hip.h section 3e): plans with nz > 238 as overlapping level windows; the library also
+  ! reads MPDATA_TALL_COLUMNS=1 from the environment, so a driver needs no call
+  public :: mpdata_set_tall_columns_c, mpdata_plan_level_windows_c
 
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
@@ -180,6 +183,16 @@ module mpdata_hip_mod
       integer(c_int), value :: mode
     end function
     integer(c_int) function mpdata_plan_boundary_c(plan) bind(C, name="mpdata_plan_boundary")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: plan
+    end function
+    ! on = 1: new plans with nz > 238 become windowed plans; returns the previous setting
+    integer(c_int) function mpdata_set_tall_columns_c(on) bind(C, name="mpdata_set_tall_columns")
+      import :: c_int
+      integer(c_int), value :: on
+    end function
+    ! W, the level windows of a plan's columns (1: not a windowed plan)
+    integer(c_int) function mpdata_plan_level_windows_c(plan) bind(C, name="mpdata_plan_level_windows")
       import :: c_int, c_ptr
       type(c_ptr), value :: plan
     end function

@@ -102,7 +102,8 @@ int mpdata_release_host_buffers(void);
  * 65 <= nz <= 238: through a wave-major plan kept per host thread (import,
  * plan kernel, export, all on `stream`; the first call of a shape allocates;
  * MPDATA_DEVICE_CALL=direct: the k-marching kernel on the caller's arrays,
- * a third of the rate).  nz > 238: the k-marching kernel (fp64, nx <= 140). */
+ * a third of the rate).  nz > 238: the k-marching kernel (fp64, nx <= 140), or
+ * level windows (section 3e, when switched on). */
 int mpdata_advect_scalar2d_device(int64_t ncrms, int nx, int nz, int ntracers,
                                   double* f, const double* u, const double* w,
                                   const double* rho, const double* rhow,
@@ -119,7 +120,7 @@ int mpdata_advect_scalar2d_device(int64_t ncrms, int nx, int nz, int ntracers,
  * its own "wave-major" order -- [tile of 64/LPS adjacent instances][column]
  * [instance][level], LPS = 8/16/32/64 >= nz (nz > 64: one instance per tile, worked on by several waves) -- so that
  * every wave streams contiguous memory; upload / download / import / export
- * convert on the device.  Other plans (nz > 238; fp32 with an odd ncrms), MPDATA_PLAN_LAYOUT=
+ * convert on the device.  Other plans (nz > 238 unless section 3e is on; fp32 with an odd ncrms), MPDATA_PLAN_LAYOUT=
  * reference or mpdata_set_plan_layout(MPDATA_LAYOUT_REFERENCE) keep the
  * reference layout.  Results do not depend on the layout. */
 #define MPDATA_LAYOUT_REFERENCE 0
@@ -260,6 +261,28 @@ int mpdata_plan_export_instances_device(mpdata_plan* plan, int64_t sl0, int64_t 
                                         int first_tracer, int ntracers);
 int mpdata_plan_download_instances(mpdata_plan* plan, int64_t sl0, int64_t n, double* f, double* flux);
 int mpdata_plan_download_instances_f32(mpdata_plan* plan, int64_t sl0, int64_t n, float* f, float* flux);
+
+/* ---- 3e. Tall columns: plans with nz > 238 as overlapping windows of at most 64 levels.  The routine's dependency
+ * cone has radius 3 in k, so a window of levels computes the levels that lie 3 or more inside its artificial edges
+ * exactly, from its own levels alone.  With the switch ON, mpdata_plan_create[_f32] with nz > 238 (fp64; fp32 with an
+ * even ncrms) makes a WINDOWED plan: a wave-major plan of ncrms * W pseudo-instances of nz_w <= 64 levels (window index
+ * fastest; the overlap levels are stored twice, about 64/57 of the memory), which the plan kernel of nz <= 64 runs.
+ * mpdata_plan_layout() reports MPDATA_LAYOUT_WAVEMAJOR for it and every plan call keeps its contract: the arrays a
+ * caller passes stay tall reference-layout arrays (split on the way in, the OWNED levels of every window merged on
+ * the way out); between two runs one small kernel copies each window's non-owned levels of f from their owners (only
+ * for tracers whose seams a run has left stale, inside the run's event pair, in front of the periodic wrap).  Results
+ * are those of a tall plan (EXACT: bit-identical, flux included).  Also lifts the limits of the k-marching fall-back:
+ * fp32, nx > 140 and k-planes of 2 GiB and more work.  The device and host calls (sections 1, 2, 6) on nz > 238 go
+ * through such a plan kept per host thread while the switch is on.  nz <= 238, fp32 plans with an odd ncrms and
+ * MPDATA_PLAN_LAYOUT=reference / mpdata_set_plan_layout(MPDATA_LAYOUT_REFERENCE) are not affected.
+ * Default OFF: today's behaviour exactly (MPDATA_TALL_COLUMNS=1 in the environment presets ON). */
+int mpdata_set_tall_columns(int on);                 /* returns the previous setting */
+int mpdata_plan_level_windows(const mpdata_plan* plan); /* W; 1 for every plan that is not windowed; multi-GPU: of shard 0 */
+/* The geometry, pure arithmetic (no device): window h of the W = return value windows of a column of nz levels is a
+ * problem of *nz_w levels whose real levels 1 .. nz_w-1 are the tall levels k0+1 .. k0+nz_w-1, and whose results are
+ * used at the tall levels *own0 .. *own1 (1-based; the owned ranges tile 1 .. nz-1).  nz <= 64: W = 1, the whole
+ * column.  Any pointer may be NULL.  MPDATA_EINVAL: nz < 2, or h outside [0, W). */
+int mpdata_level_window(int nz, int h, int* k0, int* nz_w, int* own0, int* own1);
 
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
