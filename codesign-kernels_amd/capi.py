@@ -97,6 +97,8 @@ def lib():
             getattr(L, name).argtypes = [vp]
         L.mpdata_set_tall_columns.restype = ci
         L.mpdata_set_tall_columns.argtypes = [ci]
+        L.mpdata_set_f32_odd_ncrms.restype = ci
+        L.mpdata_set_f32_odd_ncrms.argtypes = [ci]
         L.mpdata_plan_level_windows.restype = ci
         L.mpdata_plan_level_windows.argtypes = [vp]
         L.mpdata_level_window.restype = ci
@@ -218,6 +220,13 @@ def set_tall_columns(on):
     """Level windows for new plans (and device / host calls) with nz > 238 (include/mpdata_hip.h section 3e); returns
     the previous setting.  Off by default; MPDATA_TALL_COLUMNS=1 in the environment presets it."""
     return lib().mpdata_set_tall_columns(int(on))
+
+
+def set_f32_odd_ncrms(on):
+    """fp32 with an odd ncrms on the packed two-instances-per-lane kernels (include/mpdata_hip.h section 3f): new fp32
+    plans at every nz the wave-major kernels cover, device / host calls from nz = 33 on; returns the previous setting.
+    Off by default; MPDATA_F32_ODD_NCRMS=1 in the environment presets it."""
+    return lib().mpdata_set_f32_odd_ncrms(int(on))
 
 
 def level_window(nz, h):
@@ -415,7 +424,8 @@ class Plan:
     """Library-owned device state + stream (reference: `!$acc enter data`,
     `update device`, `wait`, `update host`; :105-110, :237-242).  Arrays cross
     the boundary in the reference layout; the plan keeps them in its own layout
-    (`layout`: LAYOUT_WAVEMAJOR for nz <= 238 -- fp32: an even ncrms --, include/mpdata_hip.h 3; above 238 levels
+    (`layout`: LAYOUT_WAVEMAJOR for nz <= 238 -- fp32: an even ncrms, or any with set_f32_odd_ncrms(1), 3f --,
+    include/mpdata_hip.h 3; above 238 levels
     with set_tall_columns(1): as `level_windows` overlapping windows of such a plan, 3e)."""
 
     def __init__(self, ncrms, nx, nz, ntracers=1, dtype=np.float64, ngpus=None, devices=None):

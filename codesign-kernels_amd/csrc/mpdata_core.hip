@@ -290,7 +290,7 @@ int advect_device(int64_t ncrms, int nx, int nz, int ntracers, R* f, const R* u,
   if (!f || !u || !w || !rho || !rhow || !adz || !flux)
     return set_err(MPDATA_EINVAL, "null array pointer");
   if (var < 0) var = variant();
-  if (staged && staged_call_applies(ncrms, nz, (int)sizeof(R)))   // 65 <= nz <= 127: through a wave-major plan (mpdata_plan.hip)
+  if (staged && staged_call_applies(ncrms, nz, (int)sizeof(R)))   // 65 <= nz <= 238 (3f: odd fp32 from 33): through a wave-major plan (mpdata_plan.hip)
     return staged_device_call((int)sizeof(R), ncrms, nx, nz, ntracers, f, u, w, rho, rhow, adz, flux, stream, var);
   MpdataTileInfo t;
   rc = choose_tile(var, ncrms, nx, nz, &t, (int)sizeof(R));
@@ -404,6 +404,16 @@ int tall_columns() {
     g_tall = (e && atoi(e) != 0) ? 1 : 0;
   }
   return g_tall;
+}
+// fp32 with an odd ncrms on the packed kernels (include/mpdata_hip.h 3f): new fp32 plans and staged device calls pad the
+// last instance pair with a phantom half.  OFF by default; MPDATA_F32_ODD_NCRMS=1 or mpdata_set_f32_odd_ncrms(1) turns it on.
+int g_f32_odd = -1;
+int f32_odd_ncrms() {
+  if (g_f32_odd < 0) {
+    const char* e = getenv("MPDATA_F32_ODD_NCRMS");
+    g_f32_odd = (e && atoi(e) != 0) ? 1 : 0;
+  }
+  return g_f32_odd;
 }
 // test switches of the wave-major launch (MPDATA_WMF_*): from the environment once, or set
 int g_wm_flags = -1;
@@ -538,6 +548,11 @@ int mpdata_set_serpentine(int on) {
 int mpdata_set_tall_columns(int on) {
   const int prev = tall_columns();
   if (on == 0 || on == 1) g_tall = on;
+  return prev;
+}
+int mpdata_set_f32_odd_ncrms(int on) {
+  const int prev = f32_odd_ncrms();
+  if (on == 0 || on == 1) g_f32_odd = on;
   return prev;
 }
 int mpdata_set_tile(int tile) {

@@ -46,6 +46,7 @@ int tile_override();           // kernel tiling id forced by MPDATA_TILE / mpdat
 int plan_layout_default();     // MPDATA_LAYOUT_* new plans get
 int serpentine();              // serpentine tile order of wave-major plans (off by default)
 int tall_columns();            // nz > 238 as windowed plans (mpdata_set_tall_columns; off by default)
+int f32_odd_ncrms();           // fp32 with an odd ncrms on the packed kernels (mpdata_set_f32_odd_ncrms; off by default)
 int wm_flags();                // MPDATA_WMF_* test switches of the wave-major launch
 int wm_wpb();                  // waves (tiles) per workgroup of the wave-major kernels
 unsigned long long* debug_buffer();   // diagnostic builds: per-wave stamp buffer (mpdata_set_debug_buffer), else null

@@ -40,6 +40,16 @@ hipError_t mpdata_layout_convert_cols(const MpdataLayoutJob* jobs, int nj, bool 
 // met (odd ncrms, unaligned base, array of 4 GiB or more), take mpdata_layout_convert_cols
 hipError_t mpdata_layout_import_rows(const MpdataLayoutJob* jobs, int nj, hipStream_t stream);
 
+// fp32 plans with an odd ncrms (include/mpdata_hip.h 3f; (ncrms + 1) / 2 pairs, the upper half of the last one a phantom):
+// whole arrays in single reals.  The jobs are the plan side as above (8-byte elements: pairs) but j.ncrms and
+// j.ref_tstride count REALS of the reference side (leading dimension ncrms, odd).  Import fills the phantom and the
+// padding pairs of the last tile with copies of instance ncrms - 1; no access leaves the caller's ncrms * rows reals.
+// Any array (split or not); nj = 1, or 2 arrays of one plan in one launch.
+hipError_t mpdata_layout_convert_odd(const MpdataLayoutJob* jobs, int nj, bool to_private, hipStream_t stream);
+// the same invariant restored on the private side alone, after an import that moved single reals (blocks, windows):
+// every slot (real) behind slot `last` := slot `last`, in the columns and tracers of the job
+hipError_t mpdata_layout_refresh_phantom(const MpdataLayoutJob& j, long long last, hipStream_t stream);
+
 // periodic lateral boundaries: f's halo columns -2..0, nx+1..nx+3 := copies of columns 1 + ((i-1) mod nx).
 //   _wm: the plan layout, a job of f (wm_job(which = 0): ntr tracers, ncol_p = nx + 6), one wave per (tracer, tile);
 //   _ref: a reference-layout array of ncols columns (column i at slot i + coff) and nlev levels per tracer, halo

@@ -360,6 +360,134 @@ __global__ void __launch_bounds__(16 * LPS) wm_import_rows_kernel(const MpdataRo
   }
 }
 
+// ---- fp32 plans with an ODD ncrms (include/mpdata_hip.h 3f): the whole-plan conversion in single reals.  Such a plan
+// holds (ncrms + 1) / 2 instance pairs; the upper half of the last pair is a PHANTOM, a copy of instance ncrms - 1, and the
+// padding pairs of the last tile are copies of that pair.  The reference side has leading dimension ncrms, odd: every other
+// row starts 4 bytes off a pair boundary and the last pair of a row would reach into the next one, so the 8-byte forms
+// above do not apply.  Here a workgroup owns S = 64 / 32 / 16 adjacent SLOTS (reals; S/2 pairs) of one array and walks
+// its columns as wm_convert_cols_kernel does, through two LDS tiles [level][S + 2] of reals:
+//   reference side: lane -> slot, 4-byte accesses, a row segment of S reals per level (256 is a multiple of S: a thread
+//     keeps its slot and takes every (256/S)-th level).  The slot index is CLAMPED to ncrms - 1 on import -- that fills the
+//     phantom and the padding -- and a store happens only for a slot below ncrms: with level kk < nlev and column
+//     cs < ncols no address leaves [ref, ref + ncrms * rows) of the caller's array (j.ncrms, j.ref_tstride in REALS);
+//   private side: lane -> (pair, level), 8 bytes per lane assembled from two neighbouring reals of the LDS row (row stride
+//     S + 2: even, so a pair is 8-byte aligned, and 2 banks on from row to row), the contiguous chunks of the tiles; the
+//     streaming policy on the line-aligned main part of an import and on the row stores of an export.
+// Arrays without columns (rho, rhow, adz, flux: main_e = 0, one column) take the same kernel.  grid.y cuts the columns
+// into segments where the instance axis alone would not fill the device.
+template <bool TO_PRIVATE>
+__global__ void __launch_bounds__(256) wm_convert_odd_kernel(const MpdataLayoutJobs js, const int ls, const int cper) {
+  extern __shared__ double lds_raw[];
+  constexpr int NR = 16, NP = 8;   // reals / pairs per thread and column: nlev * S <= 16 * 256
+  const MpdataLayoutJob& j = js.j[blockIdx.z / js.ntr_max];
+  const int tr = blockIdx.z % js.ntr_max;
+  const int c_lo = blockIdx.y * cper, c_hi = min(j.ncols, c_lo + cper);
+  if (tr >= j.ntr || c_lo >= c_hi) return;   // (uniform for the workgroup: before any barrier)
+  const int S = 1 << ls, TP = S + 2;
+  unsigned* tile = reinterpret_cast<unsigned*>(lds_raw);   // [2][nlev][TP]
+  const int tid = threadIdx.x;
+  const int nlev = j.nlev, slp = j.slp;
+  const int npe = (nlev << ls) >> 1, tsz = nlev * TP;
+  const long long g0 = (long long)blockIdx.x << ls;        // first slot of this workgroup
+  const long long npair = (long long)j.ntiles * slp;       // pairs the private side holds (phantom, padding included)
+  unsigned* ref = static_cast<unsigned*>(j.ref) + (long long)tr * j.ref_tstride;
+  u32x2_t* prv = static_cast<u32x2_t*>(j.prv) + (long long)tr * j.prv_tstride;
+  const bool split = j.main_e > 0;
+  const long long me = split ? j.main_e : j.chunk, rem_e = j.chunk - me;
+
+  // reference side: this thread's slot, its first level and the stride of its levels
+  const int t = tid & (S - 1), kk0 = tid >> ls, kstep = 256 >> ls;
+  const bool real = g0 + t < j.ncrms;
+  const long long sl = real ? g0 + t : j.ncrms - 1;
+  const long long rlev = j.ncrms * j.ref_levmul * kstep, rcol = j.ncrms * j.ref_colmul;
+  unsigned* rp = ref + sl + j.ncrms * ((long long)c_lo * j.ref_colmul + (long long)kk0 * j.ref_levmul);
+  // private side: this thread's pairs (the same for every column; a column advances the pointer by a constant)
+  u32x2_t* pp[NP];
+  long long pstep[NP];
+  int pl[NP];        // LDS position of the pair's lower half; -1: nothing
+  bool pmain[NP];
+#pragma unroll
+  for (int e = 0; e < NP; ++e) {
+    const int i = tid + e * 256;
+    pl[e] = -1; pp[e] = prv; pstep[e] = 0; pmain[e] = false;
+    if (i < npe) {
+      const int pr = i / nlev, kk = i - pr * nlev;
+      const long long pair = (g0 >> 1) + pr;
+      if (pair < npair) {
+        const long long tl = pair / slp;
+        const long long el = (pair - tl * slp) * nlev + kk;
+        pl[e] = kk * TP + 2 * pr;
+        pmain[e] = el < me;
+        pstep[e] = pmain[e] ? me : rem_e;
+        pp[e] = prv + tl * j.prv_tile_stride + (pmain[e] ? el : (long long)j.ncol_p * me + (el - me)) +
+                (long long)(c_lo + j.prv_col0) * pstep[e];
+      }
+    }
+  }
+  for (int cs = c_lo; cs < c_hi; ++cs) {
+    unsigned* tb = tile + ((cs - c_lo) & 1) * tsz;   // (two tiles: the previous column's readers are past this column's predecessor's barrier)
+    if (TO_PRIVATE) {
+      unsigned v[NR];
+#pragma unroll
+      for (int e = 0; e < NR; ++e)
+        if (kk0 + e * kstep < nlev) v[e] = rp[e * rlev];
+#pragma unroll
+      for (int e = 0; e < NR; ++e)
+        if (kk0 + e * kstep < nlev) tb[(kk0 + e * kstep) * TP + t] = v[e];
+      __syncthreads();
+#pragma unroll
+      for (int e = 0; e < NP; ++e) {
+        if (pl[e] >= 0) {
+          const u32x2_t pv = *reinterpret_cast<const u32x2_t*>(tb + pl[e]);
+          if (split && pmain[e]) __builtin_nontemporal_store(pv, pp[e]);
+          else *pp[e] = pv;
+        }
+        pp[e] += pstep[e];
+      }
+    } else {
+      u32x2_t pv[NP];
+#pragma unroll
+      for (int e = 0; e < NP; ++e)
+        if (pl[e] >= 0) pv[e] = *pp[e];
+#pragma unroll
+      for (int e = 0; e < NP; ++e) {
+        if (pl[e] >= 0) *reinterpret_cast<u32x2_t*>(tb + pl[e]) = pv[e];
+        pp[e] += pstep[e];
+      }
+      __syncthreads();
+      if (real) {
+#pragma unroll
+        for (int e = 0; e < NR; ++e)
+          if (kk0 + e * kstep < nlev) __builtin_nontemporal_store(tb[(kk0 + e * kstep) * TP + t], rp + e * rlev);
+      }
+    }
+    rp += rcol;
+  }
+}
+
+// The phantom refresh behind an import that did not go through the kernel above (a block that contains the plan's last
+// instance, the split and the seam refresh of a windowed plan): on the private side alone, every slot behind slot `last`
+// (= ncrms - 1: the phantom and the padding pairs of the last tile) := slot `last`, all levels, one workgroup per
+// (column, tracer).  The source slot is never a destination: no ordering inside the kernel.
+__global__ void __launch_bounds__(256) wm_phantom_kernel(const MpdataLayoutJob j, const long long last) {
+  const int cs = blockIdx.x, tr = blockIdx.y;
+  const int nlev = j.nlev, slp = j.slp;
+  unsigned* prv = static_cast<unsigned*>(j.prv) + (long long)tr * j.prv_tstride * 2;
+  const long long c = cs + j.prv_col0, rem_e = j.chunk - j.main_e;
+  auto prv_at = [&](const long long q, const int kk) -> long long {
+    const long long inst = q >> 1, h = q & 1;
+    const long long t = inst / slp;
+    const long long e = (inst - t * slp) * nlev + kk;
+    const long long o = j.main_e == 0 ? c * j.chunk + e : (e < j.main_e ? c * j.main_e + e : j.ncol_p * j.main_e + c * rem_e + (e - j.main_e));
+    return (t * j.prv_tile_stride + o) * 2 + h;
+  };
+  const int npad = (int)((long long)j.ntiles * slp * 2 - 1 - last);
+  for (int i = threadIdx.x; i < npad * nlev; i += 256) {
+    const int d = i / nlev, kk = i - d * nlev;
+    prv[prv_at(last + 1 + d, kk)] = prv[prv_at(last, kk)];
+  }
+}
+
 // ---- Periodic lateral boundaries (mpdata_plan_set_boundary, mpdata_periodic_halo_device).  Halo column i in
 // {-2,-1,0,nx+1,nx+2,nx+3} of f takes column 1 + ((i-1) mod nx) -- always an interior column, never a halo one, so
 // every source is read before any store of the same wave can touch it and no ordering is needed between waves.
@@ -508,6 +636,52 @@ hipError_t mpdata_layout_import_rows(const MpdataLayoutJob* jobs, int nj, hipStr
     case 64: hipLaunchKernelGGL((wm_import_rows_kernel<64>), grid, dim3(1024), 0, stream, js); break;
     default: return hipErrorNotSupported;
   }
+  return hipGetLastError();
+}
+
+// whole arrays of an fp32 plan with an odd ncrms (wm_convert_odd_kernel): nj = 1, or 2 arrays of one plan in one launch
+hipError_t mpdata_layout_convert_odd(const MpdataLayoutJob* jobs, int nj, bool to_private, hipStream_t stream) {
+  if (nj < 1 || nj > 2) return hipErrorInvalidValue;
+  MpdataLayoutJobs js;
+  js.ntr_max = 1;
+  int maxcols = 1;
+  for (int i = 0; i < nj; ++i) {
+    const MpdataLayoutJob& j = jobs[i];
+    if (!j.ref || !j.prv || ((uintptr_t)j.ref & 3) || ((uintptr_t)j.prv & 7) || j.ncrms < 1 || (j.ncrms & 1) == 0 || j.ncols < 1 ||
+        j.ncols > 65535 || j.ntr < 1 || j.nlev < 1 || j.nlev > 256 || j.slp < 1 || j.ntiles < 1 || j.main_e < 0 || j.main_e > j.chunk ||
+        j.chunk != (long long)j.slp * j.nlev || j.ncrms + 1 > 2 * (long long)j.ntiles * j.slp ||
+        j.nlev != jobs[0].nlev || j.slp != jobs[0].slp || j.ntiles != jobs[0].ntiles || j.ncrms != jobs[0].ncrms)
+      return hipErrorInvalidValue;
+    js.j[i] = j;
+    js.ntr_max = j.ntr > js.ntr_max ? j.ntr : js.ntr_max;
+    maxcols = j.ncols > maxcols ? j.ncols : maxcols;
+  }
+  if (nj == 1) js.j[1] = js.j[0];
+  const int nlev = jobs[0].nlev;
+  // slots per workgroup: 16 reals / 8 pairs per thread and column; the two LDS tiles stay below 35 KB
+  const int ls = nlev <= 64 ? 6 : nlev <= 128 ? 5 : 4, S = 1 << ls;
+  const long long nslot = 2 * (long long)jobs[0].ntiles * jobs[0].slp;
+  const long long gx = (nslot + S - 1) >> ls, gz = (long long)nj * js.ntr_max;
+  if (gx > 2147483647LL || gz > 65535) return hipErrorInvalidValue;
+  // column segments: about 8 workgroups per CU where the instance axis and the tracers do not give them
+  const long long want = 2048, have = gx * gz;
+  const int cseg = have >= want ? 1 : (int)((want + have - 1) / have < maxcols ? (want + have - 1) / have : maxcols);
+  const int cper = (maxcols + cseg - 1) / cseg;
+  const dim3 grid((unsigned)gx, (unsigned)((maxcols + cper - 1) / cper), (unsigned)gz), block(256);
+  const size_t lds = (size_t)2 * nlev * (S + 2) * 4;
+  if (to_private) hipLaunchKernelGGL((wm_convert_odd_kernel<true>), grid, block, lds, stream, js, ls, cper);
+  else hipLaunchKernelGGL((wm_convert_odd_kernel<false>), grid, block, lds, stream, js, ls, cper);
+  return hipGetLastError();
+}
+
+// the phantom and the padding of the last tile := slot `last` of a job's array (wm_phantom_kernel); fp32 plans only
+hipError_t mpdata_layout_refresh_phantom(const MpdataLayoutJob& j, long long last, hipStream_t stream) {
+  const long long nslot = 2 * (long long)j.ntiles * j.slp;
+  if (!j.prv || j.ncols < 1 || j.ncols > 65535 || j.ntr < 1 || j.ntr > 65535 || j.nlev < 1 || j.slp < 1 || j.ntiles < 1 || j.main_e < 0 ||
+      j.main_e > j.chunk || last < 0 || last >= nslot || nslot - last > 2 * (long long)j.slp)
+    return hipErrorInvalidValue;
+  if (last + 1 == nslot) return hipSuccess;
+  hipLaunchKernelGGL(wm_phantom_kernel, dim3((unsigned)j.ncols, (unsigned)j.ntr), dim3(256), 0, stream, j, last);
   return hipGetLastError();
 }
 

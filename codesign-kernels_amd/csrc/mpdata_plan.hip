@@ -68,7 +68,12 @@ struct mpdata_plan {
   void *f, *u, *w, *rho, *rhow, *adz, *flux;  // = arena.p[0..6]
   // wave-major plans
   int lps, slp, wpb, ntiles;
-  int64_t wm_ncrms;  // instances as the wave-major side sees them: ncrms (fp64) or ncrms / 2 pairs (fp32)
+  int64_t wm_ncrms;  // instances as the wave-major side sees them: ncrms (fp64) or (ncrms + 1) / 2 pairs (fp32)
+  // fp32 plans with an odd ncrms (include/mpdata_hip.h 3f): the upper half of the last pair is a phantom.  INVARIANT: in
+  // every plan array it is a copy of instance ncrms - 1, and the padding pairs of the last tile are copies of that pair.
+  // Whole imports keep it themselves (mpdata_layout_convert_odd); plan_phantom restores it behind everything else that
+  // replaces instance ncrms - 1.  No export reads it.
+  bool odd;
   long long chunk, tile_elems, main_e;   // main_e: elements of the line-aligned part of a column chunk
   void *pf, *pu, *pw, *pkc, *pflux;  // private arrays
   void* stage;                       // reference-layout staging: one tracer of f (or u, w)
@@ -109,8 +114,10 @@ namespace {
 MpdataLayoutJob wm_job(const mpdata_plan* p, int which, void* ref, int first_tracer, int ntr) {
   MpdataLayoutJob j;
   const int nzm = p->nz - 1, nx = p->nx;
-  // (fp32 plans: every array seen as wm_ncrms = ncrms / 2 pairs of adjacent instances, 8 bytes each)
-  j.ref = ref; j.ncrms = p->wm_ncrms; j.nlev = nzm; j.ntr = 1; j.slp = p->slp; j.ntiles = p->ntiles;
+  // (fp32 plans: every array seen as wm_ncrms = ncrms / 2 pairs of adjacent instances, 8 bytes each; with an odd ncrms
+  //  the reference side is counted in reals instead -- lref -- and only mpdata_layout_convert_odd takes the job whole)
+  const long long lref = p->odd ? p->ncrms : p->wm_ncrms;
+  j.ref = ref; j.ncrms = lref; j.nlev = nzm; j.ntr = 1; j.slp = p->slp; j.ntiles = p->ntiles;
   j.chunk = p->chunk; j.ref_tstride = 0; j.prv_tstride = 0; j.prv_col0 = 0;
   j.main_e = which <= 2 ? p->main_e : 0;   // f, u, w are split into line-aligned part + rest
   j.ncol_p = nx + 6;
@@ -119,7 +126,7 @@ MpdataLayoutJob wm_job(const mpdata_plan* p, int which, void* ref, int first_tra
     case 0:
       j.prv = (double*)p->pf + (long long)first_tracer * p->ntiles * p->tile_elems;
       j.ncols = nx + 6; j.ref_levmul = nx + 6; j.prv_tile_stride = p->tile_elems;
-      j.ntr = ntr; j.ref_tstride = (long long)p->wm_ncrms * (nx + 6) * nzm; j.prv_tstride = (long long)p->ntiles * p->tile_elems;
+      j.ntr = ntr; j.ref_tstride = lref * (nx + 6) * nzm; j.prv_tstride = (long long)p->ntiles * p->tile_elems;
       break;
     case 1: j.prv = p->pu; j.ncols = nx + 5; j.ref_levmul = nx + 5; j.prv_col0 = 1; j.prv_tile_stride = p->tile_elems; break;
     case 2: j.prv = p->pw; j.ncols = nx + 4; j.ref_levmul = nx + 4; j.prv_col0 = 1; j.prv_tile_stride = p->tile_elems; break;
@@ -130,7 +137,7 @@ MpdataLayoutJob wm_job(const mpdata_plan* p, int which, void* ref, int first_tra
     default:
       j.prv = (double*)p->pflux + (long long)first_tracer * p->ntiles * p->chunk;
       j.ncols = 1; j.ref_colmul = 0; j.ref_levmul = 1; j.prv_tile_stride = p->chunk;
-      j.ntr = ntr; j.ref_tstride = (long long)p->wm_ncrms * p->nz; j.prv_tstride = (long long)p->ntiles * p->chunk;
+      j.ntr = ntr; j.ref_tstride = lref * p->nz; j.prv_tstride = (long long)p->ntiles * p->chunk;
       break;
   }
   return j;
@@ -191,13 +198,21 @@ bool legacy_convert() {
   return v;
 }
 
+// fp32 plans with an odd ncrms: the phantom half and the padding pairs of array `which` := the plan's last instance
+// (tracers [first, first + ntr) of f / flux).  Behind every import that replaced that instance in single reals.
+int plan_phantom(mpdata_plan* p, int which, int first, int ntr) {
+  if (!p->odd) return 0;
+  HIP_TRY(mpdata_layout_refresh_phantom(wm_job(p, which, nullptr, first, ntr), p->ncrms - 1, p->stream));
+  return 0;
+}
+
 // Windowed plans: tall reference-layout arrays of instances [sl0, sl0 + n) (leading dimension n; host arrays: the whole
 // plan only) -> the windows (split: every level every window holds, so a whole import of f leaves fresh seams; after a
 // block import the seams of the plan are as fresh as they were).  flux is also kept tall (level nz).
 int win_import(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w, const void* rho,
                const void* rhow, const void* adz, const void* flux, int first, int count, bool dev) {
   const int eb = p->eb;
-  const bool whole = n == p->ncrms;
+  const bool whole = n == p->ncrms, last = sl0 + n == p->ncrms;
   const size_t f1 = (size_t)n * (p->nx + 6) * (p->nz - 1);   // elements of one tracer of f
   win_inner(p);
   if (!dev) {
@@ -211,7 +226,7 @@ int win_import(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void
       ref = p->stage;
     }
     HIP_TRY(mpdata_window_convert(win_job(p, which, ref, sl0, n, tr, ntr), true, p->stream));
-    return 0;
+    return last ? plan_phantom(p->inner, which, tr, ntr) : 0;   // (an odd number of windows: the split moves real ones only)
   };
   int rc = 0;
   if (f) {
@@ -230,9 +245,11 @@ int win_import(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void
     if (whole) {
       HIP_TRY(hipMemcpyAsync(fr, flux, p->sz.kz * count * eb, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, p->stream));
       HIP_TRY(mpdata_window_convert(win_job(p, 6, fr, 0, n, first, count), true, p->stream));
+      rc = plan_phantom(p->inner, 6, first, count);
     } else {
       HIP_TRY(mpdata_layout_copy_rows(fr + (size_t)sl0 * eb, flux, eb, n, (long long)p->nz * count, p->ncrms, n, p->stream));
       HIP_TRY(mpdata_window_convert(win_job(p, 6, const_cast<void*>(flux), sl0, n, first, count), true, p->stream));
+      if (last) rc = plan_phantom(p->inner, 6, first, count);
     }
   }
   return rc;
@@ -284,6 +301,8 @@ int plan_seams(mpdata_plan* p, int first, int count) {
   if (lo == hi) return 0;
   win_inner(p);
   HIP_TRY(mpdata_window_seams(win_job(p, 0, nullptr, 0, p->ncrms, lo, hi - lo), p->stream));
+  const int rc = plan_phantom(p->inner, 0, lo, hi - lo);   // (the refresh acts on real windows: the phantom follows the last one)
+  if (rc) return rc;
   memset(p->seam_ok + lo, 1, (size_t)(hi - lo));
   return 0;
 }
@@ -316,7 +335,9 @@ int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, con
   // f, u, w (many columns, split chunks): the column-walking kernel; the small arrays: the per-column one
   auto conv = [&](int which, void* ref, int tr, int ntr) -> int {
     const MpdataLayoutJob j = wm_job(p, which, ref, tr, ntr);
-    if (which <= 2 && !legacy_convert()) {
+    if (p->odd) {
+      HIP_TRY(mpdata_layout_convert_odd(&j, 1, true, p->stream));
+    } else if (which <= 2 && !legacy_convert()) {
       const hipError_t e = mpdata_layout_import_rows(&j, 1, p->stream);   // (row segments through LDS-DMA where possible)
       if (e == hipErrorNotSupported) HIP_TRY(mpdata_layout_convert_cols(&j, 1, true, p->stream));
       else HIP_TRY(e);
@@ -343,7 +364,7 @@ int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, con
   }
   if (!rc && u && w && dev && !legacy_convert()) {   // u and w of a device import: ONE launch
     const MpdataLayoutJob j2[2] = {wm_job(p, 1, const_cast<void*>(u), 0, 1), wm_job(p, 2, const_cast<void*>(w), 0, 1)};
-    const hipError_t e = mpdata_layout_import_rows(j2, 2, p->stream);
+    const hipError_t e = p->odd ? mpdata_layout_convert_odd(j2, 2, true, p->stream) : mpdata_layout_import_rows(j2, 2, p->stream);
     if (e == hipErrorNotSupported) HIP_TRY(mpdata_layout_convert_cols(j2, 2, true, p->stream));
     else HIP_TRY(e);
     p->have_u = p->have_w = true;
@@ -359,7 +380,9 @@ int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, con
     // private array (a tracer that is never run exports what was imported)
     void* fr = (char*)p->flux_ref + (size_t)first * p->sz.kz * eb;
     HIP_TRY(hipMemcpyAsync(fr, flux, p->sz.kz * count * eb, kind, p->stream));
-    HIP_TRY(mpdata_layout_convert(wm_job(p, 6, fr, first, count), 8, true, p->stream));
+    const MpdataLayoutJob j = wm_job(p, 6, fr, first, count);
+    if (p->odd) HIP_TRY(mpdata_layout_convert_odd(&j, 1, true, p->stream));
+    else HIP_TRY(mpdata_layout_convert(j, 8, true, p->stream));
   }
   return rc;
 }
@@ -400,7 +423,8 @@ int plan_export(mpdata_plan* p, void* f, void* flux, int first, int count, bool 
   }
   auto conv_out = [&](void* ref, int tr, int ntr) -> int {
     const MpdataLayoutJob j = wm_job(p, 0, ref, tr, ntr);
-    if (!legacy_convert()) HIP_TRY(mpdata_layout_convert_cols(&j, 1, false, p->stream));
+    if (p->odd) HIP_TRY(mpdata_layout_convert_odd(&j, 1, false, p->stream));
+    else if (!legacy_convert()) HIP_TRY(mpdata_layout_convert_cols(&j, 1, false, p->stream));
     else HIP_TRY(mpdata_layout_convert(j, 8, false, p->stream));
     return 0;
   };
@@ -422,7 +446,9 @@ int plan_export(mpdata_plan* p, void* f, void* flux, int first, int count, bool 
     // levels 1..nzm from the kernel's result; level nz is whatever was uploaded (the reference
     // never writes it, :541, :624)
     void* fr = (char*)p->flux_ref + (size_t)first * p->sz.kz * eb;
-    HIP_TRY(mpdata_layout_convert(wm_job(p, 6, fr, first, count), 8, false, p->stream));
+    const MpdataLayoutJob j = wm_job(p, 6, fr, first, count);
+    if (p->odd) HIP_TRY(mpdata_layout_convert_odd(&j, 1, false, p->stream));
+    else HIP_TRY(mpdata_layout_convert(j, 8, false, p->stream));
     HIP_TRY(hipMemcpyAsync(flux, fr, p->sz.kz * count * eb, kind, p->stream));
   }
   return 0;
@@ -435,7 +461,9 @@ MpdataBlockJob wm_block_job(const mpdata_plan* p, int which, void* ref, int64_t 
   MpdataBlockJob b;
   b.j = wm_job(p, which, ref, first_tracer, ntr);
   b.j.ref_tstride = which == 0 ? (long long)n * (p->nx + 6) * (p->nz - 1) : which == 6 ? (long long)n * p->nz : 0;
-  b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
+  // (an odd fp32 plan: the phantom counts as an instance no block contains -- the kernel then neither fills nor exports
+  //  it, and its padding rule never writes a wrong half; plan_phantom restores the invariant behind the import)
+  b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms + (p->odd ? 1 : 0); b.ipe = 8 / p->eb;
   return b;
 }
 
@@ -463,7 +491,7 @@ int plan_import_block(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, con
   }
   auto conv = [&](int which, const void* ref, int tr, int ntr) -> int {
     HIP_TRY(mpdata_layout_convert_block(wm_block_job(p, which, const_cast<void*>(ref), sl0, n, tr, ntr), true, p->stream));
-    return 0;
+    return sl0 + n == p->ncrms ? plan_phantom(p, which, tr, ntr) : 0;
   };
   if (f) rc = conv(0, f, first, count);
   if (!rc && u) rc = conv(1, u, 0, 1);
@@ -537,11 +565,13 @@ static int plan_create(int64_t ncrms, int nx, int nz, int ntracers, mpdata_plan*
   int rc = validate(ncrms, nx, nz, ntracers);
   if (rc) return rc;
   const int var = var_in >= 0 ? var_in : variant();
-  // wave-major: fp64, and fp32 with an even ncrms (two adjacent instances per lane = 8-byte elements)
-  const bool wmaj = (eb == 8 || (ncrms & 1) == 0) && wm_lps_for(nz) != 0 &&
+  // wave-major: fp64, and fp32 with an even ncrms (two adjacent instances per lane = 8-byte elements) -- or, with the
+  // switch of include/mpdata_hip.h 3f on, an odd one: one more pair, whose upper half is a phantom
+  const bool pairs_ok = eb == 8 || (ncrms & 1) == 0 || f32_odd_ncrms();
+  const bool wmaj = pairs_ok && wm_lps_for(nz) != 0 &&
                     plan_layout_default() == MPDATA_LAYOUT_WAVEMAJOR && tile_override() < 0;
   // windowed (include/mpdata_hip.h 3e): above the tallest wave-major form, when switched on, under the same conditions
-  const bool windowed = tall_columns() && nz > MPDATA_WM_NZ_MAX && (eb == 8 || (ncrms & 1) == 0) &&
+  const bool windowed = tall_columns() && nz > MPDATA_WM_NZ_MAX && pairs_ok &&
                         plan_layout_default() == MPDATA_LAYOUT_WAVEMAJOR && tile_override() < 0;
   MpdataTileInfo t;
   if (!wmaj && !windowed) {
@@ -597,7 +627,8 @@ static int plan_create(int64_t ncrms, int nx, int nz, int ntracers, mpdata_plan*
   if (e == hipSuccess && wmaj) {
     const int nzm = nz - 1;
     const int web = 8;   // bytes of an element on the wave-major side (fp32: a pair of instances)
-    p->wm_ncrms = eb == 8 ? ncrms : ncrms / 2;
+    p->wm_ncrms = eb == 8 ? ncrms : (ncrms + 1) / 2;
+    p->odd = eb == 4 && (ncrms & 1);
     p->lps = wm_lps_for(nz); p->slp = p->lps >= 64 ? 1 : 64 / p->lps; p->wpb = wm_wpb();
     p->ntiles = (int)((p->wm_ncrms + p->slp - 1) / p->slp);
     p->chunk = (long long)p->slp * nzm;
@@ -1223,7 +1254,9 @@ thread_local StagedPlan t_staged;
 extern "C++" void mpd::staged_plan_release() { t_staged.release(); }
 extern "C++" bool mpd::staged_call_applies(int64_t ncrms, int nz, int eb) {
   static const bool direct = getenv("MPDATA_DEVICE_CALL") && !strcmp(getenv("MPDATA_DEVICE_CALL"), "direct");
-  return !direct && nz > 64 && (wm_lps_for(nz) != 0 || tall_columns()) && (eb == 8 || (ncrms & 1) == 0) &&
+  // (3f: fp32 with an odd ncrms has no direct kernel above 32 levels -- from 33 on through the plan, when switched on)
+  const bool odd = eb == 4 && (ncrms & 1);
+  return !direct && nz > (odd ? 32 : 64) && (wm_lps_for(nz) != 0 || tall_columns()) && (!odd || f32_odd_ncrms()) &&
          plan_layout_default() == MPDATA_LAYOUT_WAVEMAJOR && tile_override() < 0;
 }
 extern "C++" int mpd::staged_device_call(int eb, int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* u, const void* w,

@@ -98,7 +98,7 @@ int check(const MpdataWindowJob& b) {
   if (W < 2 || j.nlev != nz_w - 1 || j.slp != 1 || j.chunk != j.nlev || j.ntr < 1 || j.ntr > 65535 || j.ncols < 1 ||
       (b.ipe != 1 && b.ipe != 2) || j.main_e < 0 || j.main_e > j.chunk || !j.prv)
     return 0;
-  if (b.sl0 < 0 || b.n < 1 || b.sl0 + b.n > b.ncrms || b.ncrms * W != (long long)j.ntiles * b.ipe) return 0;
+  if (b.sl0 < 0 || b.n < 1 || b.sl0 + b.n > b.ncrms || (b.ncrms * W + b.ipe - 1) / b.ipe != j.ntiles) return 0;   // (fp32, an odd number of windows: one phantom half)
   return W;
 }
 

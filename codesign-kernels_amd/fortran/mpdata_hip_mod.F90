@@ -25,6 +25,9 @@ module mpdata_hip_mod
   ! tall columns (include/mpdata_hip.h section 3e): plans with nz > 238 as overlapping level windows; the library also
   ! reads MPDATA_TALL_COLUMNS=1 from the environment, so a driver needs no call
   public :: mpdata_set_tall_columns_c, mpdata_plan_level_windows_c
+  ! fp32 with an odd ncrms on the packed kernels (include/mpdata_hip.h section 3f); the library also reads
+  ! MPDATA_F32_ODD_NCRMS=1 from the environment, so a driver needs no call
+  public :: mpdata_set_f32_odd_ncrms_c
 
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
@@ -188,6 +191,11 @@ module mpdata_hip_mod
     end function
     ! on = 1: new plans with nz > 238 become windowed plans; returns the previous setting
     integer(c_int) function mpdata_set_tall_columns_c(on) bind(C, name="mpdata_set_tall_columns")
+      import :: c_int
+      integer(c_int), value :: on
+    end function
+    ! on = 1: fp32 plans and calls with an odd ncrms run on the packed kernels; returns the previous setting
+    integer(c_int) function mpdata_set_f32_odd_ncrms_c(on) bind(C, name="mpdata_set_f32_odd_ncrms")
       import :: c_int
       integer(c_int), value :: on
     end function

@@ -103,7 +103,7 @@ int mpdata_release_host_buffers(void);
  * plan kernel, export, all on `stream`; the first call of a shape allocates;
  * MPDATA_DEVICE_CALL=direct: the k-marching kernel on the caller's arrays,
  * a third of the rate).  nz > 238: the k-marching kernel (fp64, nx <= 140), or
- * level windows (section 3e, when switched on). */
+ * level windows (section 3e, when switched on).  fp32 with an odd ncrms: section 3f. */
 int mpdata_advect_scalar2d_device(int64_t ncrms, int nx, int nz, int ntracers,
                                   double* f, const double* u, const double* w,
                                   const double* rho, const double* rhow,
@@ -116,11 +116,11 @@ int mpdata_advect_scalar2d_device(int64_t ncrms, int nx, int nz, int ntracers,
  * fixes the kernel variant at creation.
  *
  * Device layout.  The arrays a caller passes are ALWAYS in the reference
- * layout above.  Inside a plan with nz <= 238 (fp64; fp32 with an even ncrms) the library keeps them in
+ * layout above.  Inside a plan with nz <= 238 (fp64; fp32 with an even ncrms, or any ncrms with section 3f on) the library keeps them in
  * its own "wave-major" order -- [tile of 64/LPS adjacent instances][column]
  * [instance][level], LPS = 8/16/32/64 >= nz (nz > 64: one instance per tile, worked on by several waves) -- so that
  * every wave streams contiguous memory; upload / download / import / export
- * convert on the device.  Other plans (nz > 238 unless section 3e is on; fp32 with an odd ncrms), MPDATA_PLAN_LAYOUT=
+ * convert on the device.  Other plans (nz > 238 unless section 3e is on; fp32 with an odd ncrms unless section 3f is on), MPDATA_PLAN_LAYOUT=
  * reference or mpdata_set_plan_layout(MPDATA_LAYOUT_REFERENCE) keep the
  * reference layout.  Results do not depend on the layout. */
 #define MPDATA_LAYOUT_REFERENCE 0
@@ -238,7 +238,8 @@ int mpdata_plan_transfer_stats(const mpdata_plan* plan, double* scatter_s, doubl
  * plan's precision that cover ONLY the block: exactly the arrays of a problem of n instances, leading dimension n,
  * not ncrms.  Any 0 <= sl0, 1 <= n, sl0 + n <= ncrms: a block need not respect the plan's tiles, the instance pairs
  * of fp32 plans (the partner of a split pair keeps its value), or any alignment beyond that of a real.  Both plan
- * layouts, both precisions.
+ * layouts, both precisions.  An fp32 plan with an odd ncrms on the packed kernels (section 3f) takes blocks like any other;
+ * one that ends on the plan's last instance, sl0 + n == ncrms, also refreshes the plan's phantom half.
  *   export / download: exactly the slice [sl0, sl0+n) along the instance axis of what mpdata_plan_export_device /
  *     _download of the whole plan would return at that moment -- every element of f (halo columns included; a
  *     PERIODIC plan hands them out wrapped) and all nz levels of flux.
@@ -273,8 +274,9 @@ int mpdata_plan_download_instances_f32(mpdata_plan* plan, int64_t sl0, int64_t n
  * for tracers whose seams a run has left stale, inside the run's event pair, in front of the periodic wrap).  Results
  * are those of a tall plan (EXACT: bit-identical, flux included).  Also lifts the limits of the k-marching fall-back:
  * fp32, nx > 140 and k-planes of 2 GiB and more work.  The device and host calls (sections 1, 2, 6) on nz > 238 go
- * through such a plan kept per host thread while the switch is on.  nz <= 238, fp32 plans with an odd ncrms and
- * MPDATA_PLAN_LAYOUT=reference / mpdata_set_plan_layout(MPDATA_LAYOUT_REFERENCE) are not affected.
+ * through such a plan kept per host thread while the switch is on.  nz <= 238, fp32 plans with an odd ncrms (unless
+ * section 3f is on as well: the inner plan of ncrms * W pseudo-instances is then padded by its rule when that product is
+ * odd) and MPDATA_PLAN_LAYOUT=reference / mpdata_set_plan_layout(MPDATA_LAYOUT_REFERENCE) are not affected.
  * Default OFF: today's behaviour exactly (MPDATA_TALL_COLUMNS=1 in the environment presets ON). */
 int mpdata_set_tall_columns(int on);                 /* returns the previous setting */
 int mpdata_plan_level_windows(const mpdata_plan* plan); /* W; 1 for every plan that is not windowed; multi-GPU: of shard 0 */
@@ -283,6 +285,26 @@ int mpdata_plan_level_windows(const mpdata_plan* plan); /* W; 1 for every plan t
  * used at the tall levels *own0 .. *own1 (1-based; the owned ranges tile 1 .. nz-1).  nz <= 64: W = 1, the whole
  * column.  Any pointer may be NULL.  MPDATA_EINVAL: nz < 2, or h outside [0, W). */
 int mpdata_level_window(int nz, int h, int* k0, int* nz_w, int* own0, int* own1);
+
+/* ---- 3f. fp32 with an odd ncrms on the packed kernels.  The fp32 kernels hold two adjacent instances per lane, so
+ * without this switch an odd ncrms gets a reference-layout plan on the one-instance-per-lane kernel at nz <= 32 and
+ * MPDATA_EUNSUPPORTED above.  No statement of the routine couples two instances (3b): a problem of ncrms + 1 instances
+ * whose last instance repeats instance ncrms - 1 computes instances 0 .. ncrms-1 of the odd problem bit for bit.  With
+ * the switch ON, mpdata_plan_create_f32 with an odd ncrms and 3 <= nz <= 238 makes a wave-major plan of (ncrms + 1) / 2
+ * pairs -- the same kernels and forms as an even plan (LPS 8 .. 64, several waves per instance above 64 levels) -- whose
+ * last pair has a PHANTOM upper half: always a copy of instance ncrms - 1 in every plan array (the padding pairs of the
+ * last tile are copies of that pair), refreshed by every import, whole or block, that replaces that instance, and never
+ * handed to the caller.  mpdata_plan_layout() reports MPDATA_LAYOUT_WAVEMAJOR and every plan call of sections 3, 3a, 3d
+ * keeps its contract on arrays of leading dimension ncrms: the whole-plan conversions of such a plan move single reals on
+ * the reference side (4-byte row accesses bounded by ncrms; no byte outside [array, array + ncrms * rows * 4) is loaded
+ * or stored, at any 4-byte aligned base) and whole pairs on the plan side.  With section 3e on as well, nz > 238 works
+ * for an odd ncrms.  mpdata_advect_scalar2d_f32_device / mpdata_advect_scalar2d_f32 with an odd ncrms: nz 33 .. 238 (and
+ * above with 3e) through the calling thread's staged plan, as nz 65 .. 238 of an even ncrms; nz <= 32 stays on the direct
+ * one-instance-per-lane kernel, which needs no second copy of the problem.  MPDATA_DEVICE_CALL=direct, MPDATA_PLAN_LAYOUT=
+ * reference, mpdata_set_plan_layout(MPDATA_LAYOUT_REFERENCE) and a tile override keep their meaning and their errors.
+ * fp64 and multi-GPU plans (fp64 only) are not affected.  Results: those of the odd problem (EXACT: bit-identical, flux
+ * included).  Default OFF: today's behaviour exactly (MPDATA_F32_ODD_NCRMS=1 in the environment presets ON). */
+int mpdata_set_f32_odd_ncrms(int on);                /* returns the previous setting */
 
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
@@ -322,7 +344,8 @@ int mpdata_unpack_shard_device(double* full, const double* shard, int64_t rows, 
  * `selected_real_kind(7)` it asks for is fp64 on conforming compilers -- IEEE single is
  * `selected_real_kind(6)`).  Same array contract with 4-byte reals.  Kernels cover nz <= 238
  * for even ncrms (two adjacent instances per lane, packed fp32 arithmetic; above 64 levels through
- * a wave-major plan, as the fp64 device call) and nz <= 32 for odd ncrms.  EXACT variant: f bit-identical to an fp32 build of the reference. */
+ * a wave-major plan, as the fp64 device call) and nz <= 32 for odd ncrms (section 3f, when switched on: the packed
+ * kernels at every nz they cover).  EXACT variant: f bit-identical to an fp32 build of the reference. */
 int mpdata_advect_scalar2d_f32(int64_t ncrms, int nx, int nz, int ntracers,
                                float* f, const float* u, const float* w,
                                const float* rho, const float* rhow,
