@@ -1074,11 +1074,19 @@ int mpdata_plan_set_stream(mpdata_plan* p, void* stream) {
 // switches it off (mpdata_plan_last_kernel_ms then reports MPDATA_ESTATE).
 int mpdata_plan_set_timing(mpdata_plan* p, int on) {
   if (!p) return set_err(MPDATA_EINVAL, "null plan");
+  // (switched off, the last recorded pair is forgotten: mpdata_plan_last_kernel_ms is a state error from this call on,
+  //  not only from the next run on, until a run has been recorded with the pair on again)
   if (p->multi) {
-    for (int g = 0; g < mpdata_multi_ngpus(p->multi); ++g) mpdata_multi_sub(p->multi, g)->timing = on != 0;
+    for (int g = 0; g < mpdata_multi_ngpus(p->multi); ++g) {
+      mpdata_plan* q = mpdata_multi_sub(p->multi, g);
+      q->timing = on != 0;
+      if (!on) q->ran = false;
+    }
+    if (!on) p->ran = false;
     return 0;
   }
   p->timing = on != 0;
+  if (!on) p->ran = false;
   return 0;
 }
 int mpdata_plan_layout(const mpdata_plan* p) { return p ? p->layout : MPDATA_EINVAL; }

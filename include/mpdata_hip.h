@@ -145,14 +145,16 @@ int mpdata_plan_run_tracers(mpdata_plan* plan, int first_tracer, int ntracers); 
  * own u, w were left alone or overwritten depends on the path and is not promised.
  * mpdata_plan_run / _run_tracers return MPDATA_ESTATE until u AND w have been handed over again
  * (mpdata_plan_upload, or mpdata_plan_import_device with u and w); further mpdata_plan_run_uw
- * calls need nothing. */
+ * calls need nothing.  u and w count separately: a whole import of u alone after mpdata_plan_run_uw hands back u only, and
+ * mpdata_plan_run stays at MPDATA_ESTATE until w has been imported whole as well (and the other way round). */
 int mpdata_plan_run_uw(mpdata_plan* plan, int first_tracer, int ntracers, const void* u, const void* w);
 int mpdata_plan_sync(mpdata_plan* plan);           /* the `!$acc wait` (:237) */
 int mpdata_plan_download(mpdata_plan* plan, double* f, double* flux);  /* host arrays */
 int mpdata_plan_last_kernel_ms(mpdata_plan* plan, double* ms); /* hipEvent time of the last run */
 /* The event pair behind mpdata_plan_last_kernel_ms is recorded around EVERY run (two marker packets
  * between consecutive launches of a stream, about 1.5 % of a 0.4-ms kernel).  on = 0 switches it
- * off for callers that time a whole loop themselves; last_kernel_ms then returns MPDATA_ESTATE. */
+ * off for callers that time a whole loop themselves; last_kernel_ms then returns MPDATA_ESTATE, from that call on and
+ * until a run has been recorded with the pair switched on again (as it does before the plan's first run). */
 int mpdata_plan_set_timing(mpdata_plan* plan, int on);
 int mpdata_plan_destroy(mpdata_plan* plan);
 /* Device-side exchange with a plan: reference-layout DEVICE arrays of the plan's precision on
@@ -250,7 +252,9 @@ int mpdata_plan_transfer_stats(const mpdata_plan* plan, double* scatter_s, doubl
  * The device forms are asynchronous on the plan's stream; the host forms cover all tracers and are synchronous.
  * State: a plan cannot be FIRST filled block by block -- "filled" and "holds velocities" stay facts about the whole
  * plan: MPDATA_ESTATE until one mpdata_plan_upload / whole mpdata_plan_import_device has run, for a u or w block
- * while the plan holds no velocities (after mpdata_plan_run_uw), and for a host form of the other precision.
+ * while the plan holds no velocities (after mpdata_plan_run_uw), and for a host form of the other precision.  A u block
+ * needs whole u to be held and a w block whole w, each on its own: while only w is held a u block returns MPDATA_ESTATE
+ * and a w block is taken.
  * MPDATA_EINVAL (before any device call): null plan, n < 1, a range outside [0, ncrms), a bad tracer range, all
  * pointers NULL.  A multi-GPU handle returns MPDATA_EUNSUPPORTED: take the single-device plan of a shard
  * (mpdata_plan_shard_plan) and a shard-local sl0. */
