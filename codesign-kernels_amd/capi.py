@@ -90,6 +90,14 @@ def lib():
         for name in ("mpdata_plan_download_instances", "mpdata_plan_download_instances_f32"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [vp, i64, i64, dp, dp]
+        L.mpdata_plan_level_stats_device.restype = ci
+        L.mpdata_plan_level_stats_device.argtypes = [vp, i64, i64, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_level_stats", "mpdata_plan_level_stats_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp, dp]
+        for name in ("mpdata_level_stats_device", "mpdata_level_stats_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, dp, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -603,6 +611,40 @@ class Plan:
         ptrs = _host_ptrs((("f", f), ("flux", flux)), (n, nx, nz, nt), self._dt, writable=("f", "flux"))
         _check(getattr(lib(), "mpdata_plan_download_instances" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def level_stats(self, sl0=0, n=None, sum=None, min=None, max=None, first_tracer=0):
+        """Horizontal sum / min / max per level of f over the interior columns 1 .. nx, instances [sl0, sl0+n) (default:
+        the rest of the plan from sl0) -> reference-layout DEVICE tensors ([ntr,] nzm, n) of the plan's precision, on the
+        plan's stream (mpdata_plan_level_stats_device).  None = not wanted; the tracers are first_tracer .. +ntr-1, ntr the
+        leading axis of a 3-d tensor.  Changes nothing of the plan."""
+        ncrms, _, nz, _ = self.dims
+        n = ncrms - int(sl0) if n is None else int(n)
+        given = [(k, t) for k, t in (("sum", sum), ("min", min), ("max", max)) if t is not None]
+        if not given:
+            raise MpdataError(-1, "level_stats: sum, min and max are all None")
+        ntr = int(given[0][1].shape[0]) if given[0][1].dim() == 3 else 1
+        sh = ((ntr,) if given[0][1].dim() == 3 else ()) + (nz - 1, n)
+        ptrs = [None if t is None else _dev_ptr(t, sh, k, self._tdt()) for k, t in (("sum", sum), ("min", min), ("max", max))]
+        _check(lib().mpdata_plan_level_stats_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
+
+    def level_stats_host(self, sl0=0, n=None, sum=None, min=None, max=None):
+        """The same for all tracers into HOST arrays (numpy, Fortran order, (n, nzm[, ntracers]); None = not wanted),
+        synchronous (mpdata_plan_level_stats[_f32])."""
+        ncrms, _, nz, nt = self.dims
+        n = ncrms - int(sl0) if n is None else int(n)
+        want = (n, nz - 1) + ((nt,) if nt > 1 else ())
+        ptrs = []
+        for k, a in (("sum", sum), ("min", min), ("max", max)):
+            if a is None:
+                ptrs.append(None)
+                continue
+            p = _host_ptr(a, k, True, self._dt)
+            if tuple(a.shape) != want and not (nt == 1 and tuple(a.shape) == want + (1,)):
+                raise MpdataError(-1, f"{k}: shape {tuple(a.shape)} != expected {want}")
+            ptrs.append(p)
+        if all(p is None for p in ptrs):
+            raise MpdataError(-1, "level_stats_host: sum, min and max are all None")
+        _check(getattr(lib(), "mpdata_plan_level_stats" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -668,6 +710,26 @@ def periodic_halo(f=None, u=None, w=None, stream=None):
     ptrs = [None if t is None else _dev_ptr(t, sh[k], k, dt) for k, t in (("f", f), ("u", u), ("w", w))]
     fn = lib().mpdata_periodic_halo_device if dt == torch.float64 else lib().mpdata_periodic_halo_f32_device
     _check(fn(ncrms, nx, nz, nt, *ptrs, _stream_handle(stream)))
+
+
+def level_stats(f, sum=None, min=None, max=None, stream=None):
+    """Horizontal sum / min / max per level over the interior columns 1 .. nx of a reference-layout DEVICE tensor f
+    ([ntr,] nzm, nx+6, ncrms), float64 or float32, into device tensors ([ntr,] nzm, ncrms) of the same dtype (None = not
+    wanted), asynchronous on `stream` (mpdata_level_stats_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"level_stats: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = tuple(f.shape[:-3]) + (nzm, ncrms)
+    ptrs = [None if t is None else _dev_ptr(t, sh, k, f.dtype) for k, t in (("sum", sum), ("min", min), ("max", max))]
+    if all(p is None for p in ptrs):
+        raise MpdataError(-1, "level_stats: sum, min and max are all None")
+    fn = lib().mpdata_level_stats_device if f.dtype == torch.float64 else lib().mpdata_level_stats_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, *ptrs, _stream_handle(stream)))
 
 
 def fill_synthetic(t, name, seed, dist, ncrms_global=None, sl0=0, stream=None):

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "mpdata_internal.h"
+#include "mpdata_stats.h"
 #include "mpdata_windows.h"
 
 using namespace mpd;
@@ -845,6 +846,93 @@ int mpdata_plan_download_instances(mpdata_plan* p, int64_t sl0, int64_t n, doubl
 }
 int mpdata_plan_download_instances_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* f, float* flux) {
   return plan_download_block(p, sl0, n, f, flux, 4);
+}
+
+// ---- 3g: horizontal sum / min / max per level of f.  Reads f, writes the outputs: no flag of the plan is touched (the
+// halo and seam marks stay -- halo columns are not read, owned levels are right whatever the seams hold), no event is
+// recorded, and a windowed plan's inner plan is read where it lies (its stream and boundary are not forwarded: nothing
+// of it runs).
+static int plan_level_stats(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int first, int count) {
+  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
+    MpdataStatsJob b;
+    b.j = wm_job(p->inner ? p->inner : p, 0, nullptr, first, count);
+    b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
+    b.W = p->inner ? p->W : 1; b.nz = p->nz;
+    b.sum = sum; b.mn = mn; b.mx = mx;
+    HIP_TRY(mpdata_stats_wm(b, p->stream));
+  } else {
+    const size_t f1 = p->sz.f / p->ntracers;
+    HIP_TRY(mpdata_stats_ref((const char*)p->f + (size_t)first * f1 * p->eb, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, sum, mn, mx,
+                             p->stream));
+  }
+  return 0;
+}
+int mpdata_plan_level_stats_device(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int first_tracer,
+                                   int ntracers) {
+  int rc = block_range("mpdata_plan_level_stats_device", p, sl0, n);
+  if (rc) return rc;
+  rc = tracer_range(p, first_tracer, ntracers);
+  if (rc) return rc;
+  if (!sum && !mn && !mx) return set_err(MPDATA_EINVAL, "mpdata_plan_level_stats_device: sum, min and max are all NULL");
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_stats_device before upload / import");
+  DevGuard g(p->device);
+  return plan_level_stats(p, sl0, n, sum, mn, mx, first_tracer, ntracers);
+}
+// host arrays, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
+static int plan_level_stats_host(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int eb) {
+  int rc = block_range("mpdata_plan_level_stats", p, sl0, n);
+  if (rc) return rc;
+  if (!sum && !mn && !mx) return set_err(MPDATA_EINVAL, "mpdata_plan_level_stats: sum, min and max are all NULL");
+  rc = plan_check(p, eb);
+  if (rc) return rc;
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_stats before upload / import");
+  DevGuard g(p->device);
+  const size_t one = (size_t)n * (p->nz - 1) * p->ntracers * eb;
+  void* host[3] = {sum, mn, mx};
+  size_t need = 0;
+  for (void* h : host) need += h ? one : 0;
+  if (p->bstage_bytes < need) {
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->bstage) (void)hipFree(p->bstage);
+    p->bstage = nullptr; p->bstage_bytes = 0;
+    HIP_TRY(hipMalloc(&p->bstage, need));
+    p->bstage_bytes = need;
+  }
+  void* dev[3] = {nullptr, nullptr, nullptr};
+  size_t off = 0;
+  for (int i = 0; i < 3; ++i)
+    if (host[i]) { dev[i] = (char*)p->bstage + off; off += one; }
+  rc = plan_level_stats(p, sl0, n, dev[0], dev[1], dev[2], 0, p->ntracers);
+  if (rc) return rc;
+  for (int i = 0; i < 3; ++i)
+    if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], one, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+int mpdata_plan_level_stats(mpdata_plan* p, int64_t sl0, int64_t n, double* sum, double* mn, double* mx) {
+  return plan_level_stats_host(p, sl0, n, sum, mn, mx, 8);
+}
+int mpdata_plan_level_stats_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* sum, float* mn, float* mx) {
+  return plan_level_stats_host(p, sl0, n, sum, mn, mx, 4);
+}
+// the same reduction on a reference-layout device array (arguments checked before any device call)
+static int level_stats_array(int64_t ncrms, int nx, int nz, int ntracers, const void* f, void* sum, void* mn, void* mx, void* stream,
+                             int eb) {
+  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
+    return set_err(MPDATA_EINVAL, "mpdata_level_stats_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
+                   (long long)ncrms, nx, nz, ntracers);
+  if (!f) return set_err(MPDATA_EINVAL, "mpdata_level_stats_device: null f");
+  if (!sum && !mn && !mx) return set_err(MPDATA_EINVAL, "mpdata_level_stats_device: sum, min and max are all NULL");
+  HIP_TRY(mpdata_stats_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, sum, mn, mx, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_level_stats_device(int64_t ncrms, int nx, int nz, int ntracers, const double* f, double* sum, double* mn, double* mx,
+                              void* stream) {
+  return level_stats_array(ncrms, nx, nz, ntracers, f, sum, mn, mx, stream, 8);
+}
+int mpdata_level_stats_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, float* sum, float* mn, float* mx,
+                                  void* stream) {
+  return level_stats_array(ncrms, nx, nz, ntracers, f, sum, mn, mx, stream, 4);
 }
 
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)

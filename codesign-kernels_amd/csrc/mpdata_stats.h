@@ -1,0 +1,39 @@
+// mpdata_stats.h -- host interface of the level-statistics kernels (mpdata_stats.hip; include/mpdata_hip.h 3g):
+// per tracer, instance and level the sum, the minimum and the maximum of f over the interior columns 1 .. nx.
+//   sum: s = +0.0; s = s + f(sl, i, k) for i = 1 .. nx, in this order, in the precision of f (no multiplication:
+//        the same bits in both variants); min / max: the bits of the chosen element.
+// Outputs are reference-layout arrays (n, nlev_out, ntr) of reals, instance index fastest, leading dimension n, the
+// block's first instance at index 0; any of the three may be NULL (skipped), not all.  Halo columns are never read.
+#ifndef MPDATA_STATS_H
+#define MPDATA_STATS_H
+#include <hip/hip_runtime.h>
+
+#include "mpdata_layout.h"
+
+// Plan layout.  j: the plan side of f exactly as wm_job(which = 0) makes it for tracers [first, first + j.ntr) (j.prv on
+// the first of them, strides in 8-byte elements; j.ref is not used).  The kernel needs the storage layout only: element
+// e = s * nlev + kk of column slot c of a tile, split into whole 128-byte lines and a rest (mpdata_layout.h).
+//   ipe: reals per 8-byte element -- 1 (fp64), 2 (fp32 plans: pairs of adjacent instances)
+//   sl0, n, ncrms: the block and the plan's size in REAL instances.  Slots that are no instance of the block -- the
+//     padding of the last tile, the phantom half of an odd fp32 plan, the partner of a pair the block's ends split --
+//     reach no output.
+//   W = 1: j describes the plan itself, nz = j.nlev + 1.
+//   W > 1: j describes the INNER plan of a windowed plan (mpdata_windows.h): slot q = sl * W + h is window h of
+//     instance sl, nz the levels of the tall column; every window writes its OWNED levels to the tall level they
+//     stand for (owned levels are right after a run whatever the seams hold).
+struct MpdataStatsJob {
+  MpdataLayoutJob j;
+  long long sl0, n, ncrms;
+  int ipe;
+  int W, nz;
+  void *sum, *mn, *mx;
+};
+// the grid covers the tiles the block touches
+hipError_t mpdata_stats_wm(const MpdataStatsJob& b, hipStream_t stream);
+
+// Reference layout: f(ld, -2:nx+3, nlev, ntr) with elem_bytes = 4 or 8, instances [sl0, sl0 + n) of its ld; one thread
+// per instance, 64-bit offsets.
+hipError_t mpdata_stats_ref(const void* f, int elem_bytes, long long ld, long long sl0, long long n, int nx, int nlev, int ntr,
+                            void* sum, void* mn, void* mx, hipStream_t stream);
+
+#endif

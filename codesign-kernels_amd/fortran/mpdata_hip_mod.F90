@@ -28,6 +28,8 @@ module mpdata_hip_mod
   ! fp32 with an odd ncrms on the packed kernels (include/mpdata_hip.h section 3f); the library also reads
   ! MPDATA_F32_ODD_NCRMS=1 from the environment, so a driver needs no call
   public :: mpdata_set_f32_odd_ncrms_c
+  ! horizontal sum / min / max per level of a resident plan's tracers (include/mpdata_hip.h section 3g)
+  public :: mpdata_plan_level_stats_device_c, mpdata_plan_level_stats_c, mpdata_level_stats_device_c
 
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
@@ -38,6 +40,8 @@ module mpdata_hip_mod
 #define MPDATA_C_PLAN_DOWNLOAD "mpdata_plan_download_f32"
 #define MPDATA_C_PERIODIC_HALO "mpdata_periodic_halo_f32_device"
 #define MPDATA_C_PLAN_DOWNLOAD_INSTANCES "mpdata_plan_download_instances_f32"
+#define MPDATA_C_PLAN_LEVEL_STATS "mpdata_plan_level_stats_f32"
+#define MPDATA_C_LEVEL_STATS_DEVICE "mpdata_level_stats_f32_device"
 #else
 #define MPDATA_C_ADVECT "mpdata_advect_scalar2d"
 #define MPDATA_C_PLAN_CREATE "mpdata_plan_create"
@@ -45,6 +49,8 @@ module mpdata_hip_mod
 #define MPDATA_C_PLAN_DOWNLOAD "mpdata_plan_download"
 #define MPDATA_C_PERIODIC_HALO "mpdata_periodic_halo_device"
 #define MPDATA_C_PLAN_DOWNLOAD_INSTANCES "mpdata_plan_download_instances"
+#define MPDATA_C_PLAN_LEVEL_STATS "mpdata_plan_level_stats"
+#define MPDATA_C_LEVEL_STATS_DEVICE "mpdata_level_stats_device"
 #endif
 
   interface
@@ -211,6 +217,31 @@ module mpdata_hip_mod
       integer(c_int64_t), value :: ncrms
       integer(c_int), value :: nx, nz, ntracers
       type(c_ptr), value :: f, u, w, stream
+    end function
+    ! section 3g: sum / min / max over the interior columns of f per instance, level and tracer; outputs (n, nzm [, ntracers]),
+    ! c_null_ptr (host form: not possible, pass all three) = skipped.  Device arrays of the plan's precision, asynchronous:
+    integer(c_int) function mpdata_plan_level_stats_device_c(plan, sl0, n, sum, mn, mx, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_level_stats_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: sum, mn, mx
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! host arrays, all tracers, synchronous
+    integer(c_int) function mpdata_plan_level_stats_c(plan, sl0, n, sum, mn, mx) bind(C, name=MPDATA_C_PLAN_LEVEL_STATS)
+      import :: c_int, c_int64_t, c_ptr, rp
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      real(rp) :: sum(*), mn(*), mx(*)
+    end function
+    ! the same reduction on a reference-layout device array f
+    integer(c_int) function mpdata_level_stats_device_c(ncrms, nx, nz, ntracers, f, sum, mn, mx, stream) &
+        bind(C, name=MPDATA_C_LEVEL_STATS_DEVICE)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      type(c_ptr), value :: f, sum, mn, mx, stream
     end function
   end interface
 

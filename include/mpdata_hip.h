@@ -310,6 +310,44 @@ int mpdata_level_window(int nz, int h, int* k0, int* nz_w, int* own0, int* own1)
  * included).  Default OFF: today's behaviour exactly (MPDATA_F32_ODD_NCRMS=1 in the environment presets ON). */
 int mpdata_set_f32_odd_ncrms(int on);                /* returns the previous setting */
 
+/* ---- 3g. Horizontal statistics of a resident plan's tracers: per tracer t, instance sl and level k = 1 .. nzm, over
+ * the INTERIOR columns i = 1 .. nx of f (what a host model takes back from its CRMs: the horizontal mean, the extrema):
+ *   sum(sl,k,t)   s = +0.0; do i = 1, nx: s = s + f(sl,i,k,t) -- in the plan's precision and exactly this order, the way
+ *                 the reference forms flux (:541-546); no multiplication, so EXACT and FAST plans give the same bits
+ *   min, max      the smallest / largest of those nx values, the bits of the chosen element (the sign of a zero result
+ *                 is unspecified when both +0 and -0 occur; NaN is outside the contract)
+ * Halo columns are never read: a PERIODIC plan needs no wrap, and nothing of a plan's state changes -- the calls read f
+ * and write the outputs, whether or not the plan holds velocities, outside the run's event pair (filled, have_u, have_w,
+ * halo and seam marks, the timing pair and last_kernel_ms stay as they are).  A kernel of its own on every kind of plan:
+ * not fused into the run, nothing kept between calls.  Wave-major plans are read in place (a wave walks the interior
+ * columns of its tile's chunk as a linear stream, the running values in registers); windowed plans (3e) write every
+ * window's OWNED levels to the tall level they stand for -- right after a run whatever the seams hold, so no refresh is
+ * launched; the phantom half of an odd fp32 plan (3f) and the padding of the last tile reach no output.
+ * Outputs: reference-layout arrays of the plan's precision, (n, nzm [, ntracers]), instance index fastest, leading
+ * dimension n, tightly packed, tracer slowest; any of the three may be NULL and is skipped.  No byte outside n * nzm *
+ * ntracers reals of an output is touched.
+ * MPDATA_EINVAL (before any device call): null plan, n < 1, a range outside [0, ncrms), a bad tracer range, all three
+ * outputs NULL; bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1) or a null f in the array forms.  MPDATA_ESTATE: a plan
+ * never filled (no upload and no whole import), a host form of the other precision.  A multi-GPU handle returns
+ * MPDATA_EUNSUPPORTED as in 3d: take mpdata_plan_shard_plan(plan, g) and a shard-local sl0.
+ * Time on the MI355X (docs/EXPERIMENTS.md J, tools/level_stats_bench.py): at ncrms = 65536, nx = 32, nz = 28, cold, one tracer,
+ * all three outputs: fp64 0.121 ms = 3.7 TB/s of the nx * nzm * ncrms * 8 bytes it has to read, 0.58 of the 0.208 ms that
+ * mpdata_plan_export_device of f alone takes; fp32 0.070 ms (3.2 TB/s), 0.63 of its export's 0.112 ms; 25 tracers: 2.91 ms
+ * fp64 (0.57), 1.65 ms fp32 (0.66); a block of 64 instances: 0.008 ms. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays on the plan's device,
+ * asynchronous on the plan's stream. */
+int mpdata_plan_level_stats_device(mpdata_plan* plan, int64_t sl0, int64_t n, void* sum, void* mn, void* mx,
+                                   int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (staging buffer owned by the plan, allocated by the first call, freed by destroy) */
+int mpdata_plan_level_stats(mpdata_plan* plan, int64_t sl0, int64_t n, double* sum, double* mn, double* mx);
+int mpdata_plan_level_stats_f32(mpdata_plan* plan, int64_t sl0, int64_t n, float* sum, float* mn, float* mx);
+/* the same reduction on a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm[,ntracers]), asynchronous on `stream`
+ * (one thread per instance, 64-bit offsets: arrays of 4 GiB and more) */
+int mpdata_level_stats_device(int64_t ncrms, int nx, int nz, int ntracers, const double* f,
+                              double* sum, double* mn, double* mx, void* stream);
+int mpdata_level_stats_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f,
+                                  float* sum, float* mn, float* mx, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
