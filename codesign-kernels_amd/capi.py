@@ -98,6 +98,14 @@ def lib():
         for name in ("mpdata_level_stats_device", "mpdata_level_stats_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, dp, dp, vp]
+        L.mpdata_plan_courant_device.restype = ci
+        L.mpdata_plan_courant_device.argtypes = [vp, i64, i64, vp, vp]
+        for name in ("mpdata_plan_courant", "mpdata_plan_courant_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp]
+        for name in ("mpdata_courant_device", "mpdata_courant_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, dp, dp, dp, dp, dp, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -645,6 +653,31 @@ class Plan:
             raise MpdataError(-1, "level_stats_host: sum, min and max are all None")
         _check(getattr(lib(), "mpdata_plan_level_stats" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def courant(self, sl0=0, n=None, clev=None, cinst=None):
+        """Outflow Courant number of the velocities the plan holds, instances [sl0, sl0+n) (default: the rest of the plan
+        from sl0) -> DEVICE tensors of the plan's precision on the plan's stream (mpdata_plan_courant_device): clev (nzm, n)
+        the max over the interior columns per level, cinst (n,) its max over the levels.  None = not wanted.  Changes
+        nothing of the plan."""
+        ncrms, _, nz, _ = self.dims
+        n = ncrms - int(sl0) if n is None else int(n)
+        if clev is None and cinst is None:
+            raise MpdataError(-1, "courant: clev and cinst are both None")
+        pl = None if clev is None else _dev_ptr(clev, (nz - 1, n), "clev", self._tdt())
+        pi = None if cinst is None else _dev_ptr(cinst, (n,), "cinst", self._tdt())
+        _check(lib().mpdata_plan_courant_device(self._p, int(sl0), n, pl, pi))
+
+    def courant_host(self, sl0=0, n=None):
+        """The same into new HOST arrays, synchronous (mpdata_plan_courant[_f32]) -> (clev (n, nzm) Fortran order, cinst (n,))"""
+        ncrms, _, nz, _ = self.dims
+        n = ncrms - int(sl0) if n is None else int(n)
+        if n < 1:
+            raise MpdataError(-1, f"courant_host: a block of n = {n} instances")
+        clev = np.zeros((n, nz - 1), self._dt, order="F")
+        cinst = np.zeros((n,), self._dt)
+        _check(getattr(lib(), "mpdata_plan_courant" + self._sfx)(self._p, int(sl0), n, ctypes.c_void_p(clev.ctypes.data),
+                                                                ctypes.c_void_p(cinst.ctypes.data)))
+        return clev, cinst
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -730,6 +763,26 @@ def level_stats(f, sum=None, min=None, max=None, stream=None):
         raise MpdataError(-1, "level_stats: sum, min and max are all None")
     fn = lib().mpdata_level_stats_device if f.dtype == torch.float64 else lib().mpdata_level_stats_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, *ptrs, _stream_handle(stream)))
+
+
+def courant(u, w, rho, adz, clev=None, cinst=None, stream=None):
+    """Outflow Courant number (include/mpdata_hip.h 3h) of reference-layout DEVICE tensors u (nzm, nx+5, ncrms), w (nz,
+    nx+4, ncrms), rho, adz (nzm, ncrms), float64 or float32, into device tensors clev (nzm, ncrms) and / or cinst (ncrms,)
+    of the same dtype (None = not wanted), asynchronous on `stream` (mpdata_courant_device)."""
+    import torch
+    if u.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"courant: dtype {u.dtype} is neither float64 nor float32")
+    if u.dim() != 3 or u.shape[1] < 6:
+        raise MpdataError(-1, f"u: shape {tuple(u.shape)} is no reference-layout u")
+    nzm, nxp5, ncrms = u.shape
+    sh = shapes(ncrms, nxp5 - 5, nzm + 1, 1)
+    ptrs = [_dev_ptr(t, sh[k], k, u.dtype) for k, t in (("u", u), ("w", w), ("rho", rho), ("adz", adz))]
+    if clev is None and cinst is None:
+        raise MpdataError(-1, "courant: clev and cinst are both None")
+    pl = None if clev is None else _dev_ptr(clev, (nzm, ncrms), "clev", u.dtype)
+    pi = None if cinst is None else _dev_ptr(cinst, (ncrms,), "cinst", u.dtype)
+    fn = lib().mpdata_courant_device if u.dtype == torch.float64 else lib().mpdata_courant_f32_device
+    _check(fn(ncrms, nxp5 - 5, nzm + 1, *ptrs, pl, pi, _stream_handle(stream)))
 
 
 def fill_synthetic(t, name, seed, dist, ncrms_global=None, sl0=0, stream=None):

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "mpdata_courant.h"
 #include "mpdata_internal.h"
 #include "mpdata_stats.h"
 #include "mpdata_windows.h"
@@ -933,6 +934,97 @@ int mpdata_level_stats_device(int64_t ncrms, int nx, int nz, int ntracers, const
 int mpdata_level_stats_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, float* sum, float* mn, float* mx,
                                   void* stream) {
   return level_stats_array(ncrms, nx, nz, ntracers, f, sum, mn, mx, stream, 4);
+}
+
+// ---- 3h: outflow Courant number of the plan's velocities per level (clev) and per instance (cinst).  Reads u, w, rho,
+// adz, writes the outputs: as the level statistics above no flag of the plan is touched, no event is recorded, and a
+// windowed plan's inner plan is read where it lies.
+static int plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst) {
+  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
+    const mpdata_plan* q = p->inner ? p->inner : p;
+    const MpdataLayoutJob jr = wm_job(q, 3, nullptr, 0, 1), ja = wm_job(q, 5, nullptr, 0, 1);
+    MpdataCourantJob b;
+    b.j = wm_job(q, 1, nullptr, 0, 1);
+    b.w = wm_job(q, 2, nullptr, 0, 1).prv;
+    b.rho = (const double*)jr.prv + jr.prv_col0 * jr.chunk;
+    b.adz = (const double*)ja.prv + ja.prv_col0 * ja.chunk;
+    b.kc_tile_stride = jr.prv_tile_stride;
+    b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
+    b.W = p->inner ? p->W : 1; b.nz = p->nz;
+    b.clev = clev; b.cinst = cinst;
+    HIP_TRY(mpdata_courant_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_courant_ref(p->u, p->w, p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, p->nz, clev, cinst, p->stream));
+  }
+  return 0;
+}
+static int plan_courant_state(const char* what, const mpdata_plan* p) {
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
+  if (!p->have_u || !p->have_w)
+    return set_err(MPDATA_ESTATE, "%s: the plan does not hold %s (mpdata_plan_run_uw used them up: import u and w)", what,
+                   !p->have_u ? "u" : "w");
+  return 0;
+}
+int mpdata_plan_courant_device(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst) {
+  int rc = block_range("mpdata_plan_courant_device", p, sl0, n);
+  if (rc) return rc;
+  if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_plan_courant_device: clev and cinst are both NULL");
+  rc = plan_courant_state("mpdata_plan_courant_device", p);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_courant(p, sl0, n, clev, cinst);
+}
+// host arrays, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
+static int plan_courant_host(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst, int eb) {
+  int rc = block_range("mpdata_plan_courant", p, sl0, n);
+  if (rc) return rc;
+  if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_plan_courant: clev and cinst are both NULL");
+  rc = plan_check(p, eb);
+  if (rc) return rc;
+  rc = plan_courant_state("mpdata_plan_courant", p);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t lb = clev ? (size_t)n * (p->nz - 1) * eb : 0, ib = cinst ? (size_t)n * eb : 0;
+  if (p->bstage_bytes < lb + ib) {
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->bstage) (void)hipFree(p->bstage);
+    p->bstage = nullptr; p->bstage_bytes = 0;
+    HIP_TRY(hipMalloc(&p->bstage, lb + ib));
+    p->bstage_bytes = lb + ib;
+  }
+  void* dl = clev ? p->bstage : nullptr;
+  void* di = cinst ? (char*)p->bstage + lb : nullptr;
+  rc = plan_courant(p, sl0, n, dl, di);
+  if (rc) return rc;
+  if (clev) HIP_TRY(hipMemcpyAsync(clev, dl, lb, hipMemcpyDeviceToHost, p->stream));
+  if (cinst) HIP_TRY(hipMemcpyAsync(cinst, di, ib, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+int mpdata_plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, double* clev, double* cinst) {
+  return plan_courant_host(p, sl0, n, clev, cinst, 8);
+}
+int mpdata_plan_courant_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* clev, float* cinst) {
+  return plan_courant_host(p, sl0, n, clev, cinst, 4);
+}
+// the same reduction on reference-layout device arrays (arguments checked before any device call)
+static int courant_array(int64_t ncrms, int nx, int nz, const void* u, const void* w, const void* rho, const void* adz, void* clev,
+                         void* cinst, void* stream, int eb) {
+  if (ncrms < 1 || nx < 1 || nz < 2)
+    return set_err(MPDATA_EINVAL, "mpdata_courant_device: bad sizes ncrms=%lld nx=%d nz=%d (need >=1,>=1,>=2)", (long long)ncrms, nx, nz);
+  if (!u || !w || !rho || !adz)
+    return set_err(MPDATA_EINVAL, "mpdata_courant_device: null %s", !u ? "u" : !w ? "w" : !rho ? "rho" : "adz");
+  if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_courant_device: clev and cinst are both NULL");
+  HIP_TRY(mpdata_courant_ref(u, w, rho, adz, eb, ncrms, 0, ncrms, nx, nz, clev, cinst, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_courant_device(int64_t ncrms, int nx, int nz, const double* u, const double* w, const double* rho, const double* adz,
+                          double* clev, double* cinst, void* stream) {
+  return courant_array(ncrms, nx, nz, u, w, rho, adz, clev, cinst, stream, 8);
+}
+int mpdata_courant_f32_device(int64_t ncrms, int nx, int nz, const float* u, const float* w, const float* rho, const float* adz,
+                              float* clev, float* cinst, void* stream) {
+  return courant_array(ncrms, nx, nz, u, w, rho, adz, clev, cinst, stream, 4);
 }
 
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)

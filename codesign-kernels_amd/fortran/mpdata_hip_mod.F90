@@ -31,6 +31,8 @@ module mpdata_hip_mod
   ! horizontal sum / min / max per level of a resident plan's tracers (include/mpdata_hip.h section 3g)
   public :: mpdata_plan_level_stats_device_c, mpdata_plan_level_stats_c, mpdata_level_stats_device_c
 
+  ! outflow Courant number of a resident plan's velocities (include/mpdata_hip.h section 3h)
+  public :: mpdata_plan_courant_device_c, mpdata_plan_courant_device
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -243,6 +245,15 @@ module mpdata_hip_mod
       integer(c_int), value :: nx, nz, ntracers
       type(c_ptr), value :: f, sum, mn, mx, stream
     end function
+    ! section 3h: outflow Courant number of the velocities the plan holds, instances [sl0, sl0+n): clev(n, nzm) the max over
+    ! the interior columns per level, cinst(n) its max over the levels; device arrays of the plan's precision, c_null_ptr =
+    ! skipped (not both), asynchronous on the plan's stream
+    integer(c_int) function mpdata_plan_courant_device_c(plan, sl0, n, clev, cinst) bind(C, name="mpdata_plan_courant_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: clev, cinst
+    end function
   end interface
 
   type(c_ptr), save :: resident_plan = c_null_ptr
@@ -268,6 +279,14 @@ contains
     write(*,*) 'libmpdata_hip: ', what, ' failed, rc=', rc, ': ', msg(1:n-1)
     error stop 1
   end subroutine mpdata_check
+
+  !> Outflow Courant number of the velocities a resident plan holds (include/mpdata_hip.h section 3h), whole plan:
+  !! clev(nslices, nzm) and cinst(nslices) are DEVICE addresses (c_null_ptr: skipped, not both); asynchronous on the
+  !! plan's stream.  A step is stable for the upwind pass where cinst <= 1; what SAM asks `kurant` for.
+  subroutine mpdata_plan_courant_device(plan, clev, cinst)
+    type(c_ptr), intent(in) :: plan, clev, cinst
+    call mpdata_check(mpdata_plan_courant_device_c(plan, 0_c_int64_t, nslices, clev, cinst), 'mpdata_plan_courant_device')
+  end subroutine mpdata_plan_courant_device
 
   !> Drop-in replacement of `call advect_scalar2D_openacc_N(f,u,w,rho,rhow,flux)`
   !! (reference :53, :57): synchronous, host arrays, transfers included (the

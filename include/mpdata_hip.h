@@ -348,6 +348,48 @@ int mpdata_level_stats_device(int64_t ncrms, int nx, int nz, int ntracers, const
 int mpdata_level_stats_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f,
                                   float* sum, float* mn, float* mx, void* stream);
 
+/* ---- 3h. Outflow Courant number of a plan's velocities (the question a time loop asks before every step: are these
+ * velocities stable for this step, or does it have to be subcycled -- SAM's kurant).  The routine's first pass, the
+ * upwind step (:528-560), updates a cell as f(i,k) - (uuu(i+1) - uuu(i) + (www(k+1) - www(k)) * iadz) * irho; the
+ * coefficient of f(i,k) in it is 1 - c, and the pass keeps the sign of f exactly where c <= 1.  For instance sl, interior
+ * column i = 1 .. nx and level k = 1 .. nzm:
+ *   a = max(0, u(sl,i+1,k)) - min(0, u(sl,i,k))
+ *   b = max(0, wk1) - min(0, w(sl,i,k))          wk1 = w(sl,i,k+1) for k < nzm, and +0 for k = nzm
+ *   c = (a + b * iadz) * irho                    iadz = 1 / adz(sl,k), irho = 1 / rho(sl,k)
+ * wk1 = +0 at k = nzm because the routine sets www(:,:,:,nz) = 0 (:511): the caller's w(:,:,:,nz) is never read.  Every
+ * operation is one correctly rounded operation in the plan's precision, in exactly this association and without
+ * contraction, the divides IEEE divides: EXACT and FAST plans give the same bits.  c is mathematically >= 0; a zero is
+ * stored as +0.0 whatever signed zeros u, w hold (the sign is cleared before anything is stored).  NaN or infinite
+ * inputs and rho or adz <= 0 are outside the contract.
+ *   clev(sl,k)   the max of c over i = 1 .. nx; reference layout (n, nzm), leading dimension n, tightly packed
+ *   cinst(sl)    the max of clev(sl,k) over k = 1 .. nzm; n reals
+ * Either output may be NULL (skipped), not both.  A max does not depend on the order, so both are defined bit for bit.
+ * Only the velocity columns 1 .. nx+1 of u and 1 .. nx of w are read, never the halos (a periodic caller's halo cells
+ * repeat interior ones).  A kernel of its own on every kind of plan (wave-major: a wave walks the column slots of u and
+ * w of its tile's chunk, u(i+1) carried over, w(k+1) through an address of its own; windowed plans (3e) write their
+ * OWNED levels; the phantom half of an odd fp32 plan (3f) and the padding reach no output); cinst is zeroed on the
+ * call's stream and formed by an unsigned atomic max on the bit pattern (c >= +0).  Nothing of a plan's state changes
+ * (filled, have_u, have_w, halo and seam marks, the timing pair and last_kernel_ms stay), outside the run's event pair.
+ * No byte outside n * nzm reals of clev and n reals of cinst is touched.
+ * MPDATA_EINVAL (before any device call): null plan, n < 1, a range outside [0, ncrms), both outputs NULL; bad sizes
+ * (ncrms < 1, nx < 1, nz < 2) or a null u, w, rho, adz in the array forms.  MPDATA_ESTATE: a plan never filled, a plan
+ * that does not hold both u and w (after mpdata_plan_run_uw, until both have been imported again), a host form of the
+ * other precision.  A multi-GPU handle returns MPDATA_EUNSUPPORTED as in 3d and 3g.
+ * Time on the MI355X (docs/EXPERIMENTS.md K, tools/courant_bench.py): not measured yet. */
+/* instances [sl0, sl0+n) of a resident plan, the velocities the plan holds; device arrays of the plan's precision on the
+ * plan's device, asynchronous on the plan's stream */
+int mpdata_plan_courant_device(mpdata_plan* plan, int64_t sl0, int64_t n, void* clev, void* cinst);
+/* host arrays, synchronous (the plan's block staging buffer, as the 3g host forms) */
+int mpdata_plan_courant(mpdata_plan* plan, int64_t sl0, int64_t n, double* clev, double* cinst);
+int mpdata_plan_courant_f32(mpdata_plan* plan, int64_t sl0, int64_t n, float* clev, float* cinst);
+/* the same reduction on reference-layout DEVICE arrays u(ncrms,-1:nx+3,1,nzm), w(ncrms,-1:nx+2,1,nz), rho(ncrms,nzm),
+ * adz(ncrms,nzm) -- the fresh u, w a caller is about to hand to mpdata_plan_run_uw, with the rho, adz it imported --
+ * asynchronous on `stream` (one thread per instance, 64-bit offsets: arrays of 4 GiB and more) */
+int mpdata_courant_device(int64_t ncrms, int nx, int nz, const double* u, const double* w, const double* rho,
+                          const double* adz, double* clev, double* cinst, void* stream);
+int mpdata_courant_f32_device(int64_t ncrms, int nx, int nz, const float* u, const float* w, const float* rho,
+                              const float* adz, float* clev, float* cinst, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
