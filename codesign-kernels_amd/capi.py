@@ -24,6 +24,7 @@ VARIANT_EXACT, VARIANT_FAST = 0, 1
 EINVAL, EUNSUPPORTED, ESTATE, ECOMM = -1, -2, -3, -4   # MPDATA_E* of include/mpdata_hip.h
 LAYOUT_REFERENCE, LAYOUT_WAVEMAJOR = 0, 1
 BOUNDARY_GIVEN, BOUNDARY_PERIODIC = 0, 1   # MPDATA_BOUNDARY_* (include/mpdata_hip.h section 3a)
+LEVEL_ADD, LEVEL_ADD_CLIP = 0, 1           # MPDATA_LEVEL_ADD* (include/mpdata_hip.h section 3i)
 
 _lib = None
 
@@ -106,6 +107,14 @@ def lib():
         for name in ("mpdata_courant_device", "mpdata_courant_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, dp, dp, dp, dp, dp, dp, vp]
+        L.mpdata_plan_level_add_device.restype = ci
+        L.mpdata_plan_level_add_device.argtypes = [vp, i64, i64, vp, ci, ci, ci]
+        for name in ("mpdata_plan_level_add", "mpdata_plan_level_add_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, ci]
+        for name in ("mpdata_level_add_device", "mpdata_level_add_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, ci, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -678,6 +687,28 @@ class Plan:
                                                                 ctypes.c_void_p(cinst.ctypes.data)))
         return clev, cinst
 
+    def level_add(self, d, sl0=0, n=None, mode=LEVEL_ADD, first_tracer=0):
+        """f(sl, i, k, t) += d(sl, k, t) on EVERY column i (halos included) of instances [sl0, sl0+n) (default: the rest of the
+        plan from sl0), in place, on the plan's stream (mpdata_plan_level_add_device); mode LEVEL_ADD_CLIP: max(0, .) of the
+        sum.  d: a reference-layout DEVICE tensor ([ntr,] nzm, n) of the plan's precision -- the shape of a level_stats
+        output; the tracers are first_tracer .. +ntr-1, ntr the leading axis of a 3-d tensor.  d is only read."""
+        ncrms, _, nz, _ = self.dims
+        n = ncrms - int(sl0) if n is None else int(n)
+        ntr = int(d.shape[0]) if d.dim() == 3 else 1
+        pd = _dev_ptr(d, ((ntr,) if d.dim() == 3 else ()) + (nz - 1, n), "d", self._tdt())
+        _check(lib().mpdata_plan_level_add_device(self._p, int(sl0), n, pd, int(mode), int(first_tracer), ntr))
+
+    def level_add_host(self, d, sl0=0, n=None, mode=LEVEL_ADD):
+        """The same for all tracers from a HOST array d (numpy, Fortran order, (n, nzm[, ntracers])), synchronous
+        (mpdata_plan_level_add[_f32])."""
+        ncrms, _, nz, nt = self.dims
+        n = ncrms - int(sl0) if n is None else int(n)
+        want = (n, nz - 1) + ((nt,) if nt > 1 else ())
+        pd = _host_ptr(d, "d", False, self._dt)
+        if tuple(d.shape) != want and not (nt == 1 and tuple(d.shape) == want + (1,)):
+            raise MpdataError(-1, f"d: shape {tuple(d.shape)} != expected {want}")
+        _check(getattr(lib(), "mpdata_plan_level_add" + self._sfx)(self._p, int(sl0), n, pd, int(mode)))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -763,6 +794,23 @@ def level_stats(f, sum=None, min=None, max=None, stream=None):
         raise MpdataError(-1, "level_stats: sum, min and max are all None")
     fn = lib().mpdata_level_stats_device if f.dtype == torch.float64 else lib().mpdata_level_stats_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, *ptrs, _stream_handle(stream)))
+
+
+def level_add(f, d, mode=LEVEL_ADD, stream=None):
+    """f(sl, i, k, t) += d(sl, k, t) on every column of a reference-layout DEVICE tensor f ([ntr,] nzm, nx+6, ncrms), float64
+    or float32, in place; d ([ntr,] nzm, ncrms) of the same dtype; mode LEVEL_ADD_CLIP: max(0, .) of the sum.  Asynchronous
+    on `stream` (mpdata_level_add_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"level_add: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    pd = _dev_ptr(d, tuple(f.shape[:-3]) + (nzm, ncrms), "d", f.dtype)
+    fn = lib().mpdata_level_add_device if f.dtype == torch.float64 else lib().mpdata_level_add_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, pd, int(mode), _stream_handle(stream)))
 
 
 def courant(u, w, rho, adz, clev=None, cinst=None, stream=None):

@@ -15,6 +15,7 @@
 
 #include "mpdata_courant.h"
 #include "mpdata_internal.h"
+#include "mpdata_level_add.h"
 #include "mpdata_stats.h"
 #include "mpdata_windows.h"
 
@@ -1025,6 +1026,95 @@ int mpdata_courant_device(int64_t ncrms, int nx, int nz, const double* u, const 
 int mpdata_courant_f32_device(int64_t ncrms, int nx, int nz, const float* u, const float* w, const float* rho, const float* adz,
                               float* clev, float* cinst, void* stream) {
   return courant_array(ncrms, nx, nz, u, w, rho, adz, clev, cinst, stream, 4);
+}
+
+// ---- 3i: per-level increments of f, in place.  Reads d, rewrites f on every column slot of the block's instances: no
+// flag of the plan is touched and no event is recorded.  The hidden invariants hold by construction, not by a refresh:
+//   halo marks  the increment is uniform in i, so halo columns that are wrapped copies stay wrapped copies (same bits in,
+//               same operation) and stale ones stay stale -- halo_ok is right as it stands;
+//   seam marks  every level a window stores takes the increment of the tall level it stands for, so fresh seams stay
+//               fresh and stale ones stay stale -- seam_ok is right as it stands;
+//   phantom     follows the plan's last instance inside the kernel (mpdata_level_add.h).
+// A windowed plan's inner plan is rewritten where it lies (its stream and boundary are not forwarded: nothing of it runs).
+static int plan_level_add(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int first, int count) {
+  const int clip = mode == MPDATA_LEVEL_ADD_CLIP;
+  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
+    MpdataLevelAddJob b;
+    b.j = wm_job(p->inner ? p->inner : p, 0, nullptr, first, count);
+    b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
+    b.W = p->inner ? p->W : 1; b.nz = p->nz;
+    b.d = d; b.clip = clip;
+    HIP_TRY(mpdata_level_add_wm(b, p->stream));
+  } else {
+    const size_t f1 = p->sz.f / p->ntracers;
+    HIP_TRY(mpdata_level_add_ref((char*)p->f + (size_t)first * f1 * p->eb, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, d, clip,
+                                 p->stream));
+  }
+  return 0;
+}
+static int level_add_mode(const char* what, int mode) {
+  if (mode != MPDATA_LEVEL_ADD && mode != MPDATA_LEVEL_ADD_CLIP) return set_err(MPDATA_EINVAL, "%s: unknown mode %d", what, mode);
+  return 0;
+}
+int mpdata_plan_level_add_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int first_tracer, int ntracers) {
+  int rc = block_range("mpdata_plan_level_add_device", p, sl0, n);
+  if (rc) return rc;
+  rc = tracer_range(p, first_tracer, ntracers);
+  if (rc) return rc;
+  if (!d) return set_err(MPDATA_EINVAL, "mpdata_plan_level_add_device: null d");
+  rc = level_add_mode("mpdata_plan_level_add_device", mode);
+  if (rc) return rc;
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_add_device before upload / import");
+  DevGuard g(p->device);
+  return plan_level_add(p, sl0, n, d, mode, first_tracer, ntracers);
+}
+// host d, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
+static int plan_level_add_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int eb) {
+  int rc = block_range("mpdata_plan_level_add", p, sl0, n);
+  if (rc) return rc;
+  if (!d) return set_err(MPDATA_EINVAL, "mpdata_plan_level_add: null d");
+  rc = level_add_mode("mpdata_plan_level_add", mode);
+  if (rc) return rc;
+  rc = plan_check(p, eb);
+  if (rc) return rc;
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_add before upload / import");
+  DevGuard g(p->device);
+  const size_t need = (size_t)n * (p->nz - 1) * p->ntracers * eb;
+  if (p->bstage_bytes < need) {
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->bstage) (void)hipFree(p->bstage);
+    p->bstage = nullptr; p->bstage_bytes = 0;
+    HIP_TRY(hipMalloc(&p->bstage, need));
+    p->bstage_bytes = need;
+  }
+  HIP_TRY(hipMemcpyAsync(p->bstage, d, need, hipMemcpyHostToDevice, p->stream));
+  rc = plan_level_add(p, sl0, n, p->bstage, mode, 0, p->ntracers);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+int mpdata_plan_level_add(mpdata_plan* p, int64_t sl0, int64_t n, const double* d, int mode) {
+  return plan_level_add_host(p, sl0, n, d, mode, 8);
+}
+int mpdata_plan_level_add_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* d, int mode) {
+  return plan_level_add_host(p, sl0, n, d, mode, 4);
+}
+// the same on a reference-layout device array (arguments checked before any device call)
+static int level_add_array(int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* d, int mode, void* stream, int eb) {
+  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
+    return set_err(MPDATA_EINVAL, "mpdata_level_add_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
+                   (long long)ncrms, nx, nz, ntracers);
+  if (!f || !d) return set_err(MPDATA_EINVAL, "mpdata_level_add_device: null %s", !f ? "f" : "d");
+  const int rc = level_add_mode("mpdata_level_add_device", mode);
+  if (rc) return rc;
+  HIP_TRY(mpdata_level_add_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, d, mode == MPDATA_LEVEL_ADD_CLIP, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_level_add_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* d, int mode, void* stream) {
+  return level_add_array(ncrms, nx, nz, ntracers, f, d, mode, stream, 8);
+}
+int mpdata_level_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* d, int mode, void* stream) {
+  return level_add_array(ncrms, nx, nz, ntracers, f, d, mode, stream, 4);
 }
 
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)

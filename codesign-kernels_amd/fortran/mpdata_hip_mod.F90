@@ -33,6 +33,9 @@ module mpdata_hip_mod
 
   ! outflow Courant number of a resident plan's velocities (include/mpdata_hip.h section 3h)
   public :: mpdata_plan_courant_device_c, mpdata_plan_courant_device
+  ! per-level increments of a resident plan's tracers, in place (include/mpdata_hip.h section 3i)
+  public :: mpdata_plan_level_add_device_c, mpdata_plan_level_add_c, mpdata_level_add_device_c
+  integer(c_int), parameter, public :: MPDATA_LEVEL_ADD = 0, MPDATA_LEVEL_ADD_CLIP = 1
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -44,6 +47,8 @@ module mpdata_hip_mod
 #define MPDATA_C_PLAN_DOWNLOAD_INSTANCES "mpdata_plan_download_instances_f32"
 #define MPDATA_C_PLAN_LEVEL_STATS "mpdata_plan_level_stats_f32"
 #define MPDATA_C_LEVEL_STATS_DEVICE "mpdata_level_stats_f32_device"
+#define MPDATA_C_PLAN_LEVEL_ADD "mpdata_plan_level_add_f32"
+#define MPDATA_C_LEVEL_ADD_DEVICE "mpdata_level_add_f32_device"
 #else
 #define MPDATA_C_ADVECT "mpdata_advect_scalar2d"
 #define MPDATA_C_PLAN_CREATE "mpdata_plan_create"
@@ -53,6 +58,8 @@ module mpdata_hip_mod
 #define MPDATA_C_PLAN_DOWNLOAD_INSTANCES "mpdata_plan_download_instances"
 #define MPDATA_C_PLAN_LEVEL_STATS "mpdata_plan_level_stats"
 #define MPDATA_C_LEVEL_STATS_DEVICE "mpdata_level_stats_device"
+#define MPDATA_C_PLAN_LEVEL_ADD "mpdata_plan_level_add"
+#define MPDATA_C_LEVEL_ADD_DEVICE "mpdata_level_add_device"
 #endif
 
   interface
@@ -253,6 +260,35 @@ module mpdata_hip_mod
       type(c_ptr), value :: plan
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: clev, cinst
+    end function
+    ! section 3i: f(sl,i,k,t) = f(sl,i,k,t) + d(sl,k,t) on every column i = -2 .. nx+3 of instances [sl0, sl0+n), in place
+    ! (mode MPDATA_LEVEL_ADD_CLIP: max(0, .) of the sum); d(n, nzm [, ntracers]) -- the shape of a 3g output -- is only read.
+    ! d a device array of the plan's precision, asynchronous on the plan's stream:
+    integer(c_int) function mpdata_plan_level_add_device_c(plan, sl0, n, d, mode, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_level_add_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: d
+      integer(c_int), value :: mode, first_tracer, ntracers
+    end function
+    ! host d, all tracers, synchronous
+    integer(c_int) function mpdata_plan_level_add_c(plan, sl0, n, d, mode) bind(C, name=MPDATA_C_PLAN_LEVEL_ADD)
+      import :: c_int, c_int64_t, c_ptr, rp
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      real(rp), intent(in) :: d(*)
+      integer(c_int), value :: mode
+    end function
+    ! the same on a reference-layout device array f with a device array d(ncrms, nzm [, ntracers])
+    integer(c_int) function mpdata_level_add_device_c(ncrms, nx, nz, ntracers, f, d, mode, stream) &
+        bind(C, name=MPDATA_C_LEVEL_ADD_DEVICE)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      type(c_ptr), value :: f, d
+      integer(c_int), value :: mode
+      type(c_ptr), value :: stream
     end function
   end interface
 

@@ -390,6 +390,50 @@ int mpdata_courant_device(int64_t ncrms, int nx, int nz, const double* u, const 
 int mpdata_courant_f32_device(int64_t ncrms, int nx, int nz, const float* u, const float* w, const float* rho,
                               const float* adz, float* clev, float* cinst, void* stream);
 
+/* ---- 3i. Per-level increments of a resident plan's tracers, in place (the write side of 3g: what a host model hands
+ * its CRMs every step -- SAM's large-scale forcing f(i,k) = f(i,k) + dt * tend(k), relaxation, surface sources, the
+ * correction of the mean after a GCM step: horizontally uniform, one value per instance, level and tracer).  For tracer
+ * t in [first_tracer, first_tracer + ntracers), instance sl in [sl0, sl0 + n), level k = 1 .. nzm and EVERY column
+ * i = -2 .. nx+3 (halo columns included):
+ *   MPDATA_LEVEL_ADD        f(sl,i,k,t) = f(sl,i,k,t) + d(sl,k,t)
+ *   MPDATA_LEVEL_ADD_CLIP   f(sl,i,k,t) = max(0, f(sl,i,k,t) + d(sl,k,t))      (the routine's own last statement, :634)
+ * Each result is one correctly rounded add in the plan's precision, then the max; nothing multiplies, so EXACT and FAST
+ * plans give the same bits.  ADD keeps the IEEE sign of a zero sum; in ADD_CLIP the sign of a zero result is unspecified
+ * (hardware max); NaN and infinities are outside the contract.
+ * d: a reference-layout array of the plan's precision, (n, nzm [, ntracers]), instance index fastest, leading dimension
+ * n, tightly packed, tracer slowest -- exactly an output of 3g, so the two calls close the loop: mean out, tendency in.
+ * It is only read, and no byte outside its n * nzm * ntracers reals is.
+ * Afterwards the plan behaves exactly as if all of f had been exported, changed as above and imported again.  GIVEN
+ * plans: the halos get the increment like any column.  PERIODIC plans: the increment is uniform in i, so wrapped halos
+ * stay wrapped copies and an export hands out the wrapped result (the kernel writes every column slot; the halo marks
+ * stay as they are).  Windowed plans (3e): every level a window stores, owned or not, takes the increment of the tall
+ * level it stands for, so all stored copies of a tall level stay consistent and a run right after gives the tall
+ * problem's bits.  Odd fp32 plans (3f): the phantom half follows instance ncrms - 1.  An fp32 block that splits a pair
+ * leaves the partner's bits alone (no + 0.0, no clip: a -0.0 or a negative value there stays).  Every instance and tracer
+ * outside the ranges, and flux, u, w, rho, rhow, adz, stay bit-identical.  Nothing else of a plan's state changes
+ * (filled, have_u, have_w, the boundary mode, halo and seam marks, the timing pair and last_kernel_ms stay), outside the
+ * run's event pair.  A kernel of its own on every kind of plan (wave-major: a wave walks all nx + 6 column slots of its
+ * tile's chunk as a linear read-modify-write stream, its increment in a register); the plan kernels are not touched.
+ * MPDATA_EINVAL (before any device call): null plan, null d, n < 1, a range outside [0, ncrms), a bad tracer range, an
+ * unknown mode; bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1) or a null f in the array forms.  MPDATA_ESTATE: a plan
+ * never filled, a host form of the other precision.  A multi-GPU handle returns MPDATA_EUNSUPPORTED as in 3d and 3g: take
+ * mpdata_plan_shard_plan(plan, g) and a shard-local sl0.  A failed call changes nothing.
+ * Time on the MI355X (docs/EXPERIMENTS.md L, tools/level_add_bench.py): not measured yet; the yardstick is
+ * mpdata_plan_export_device + mpdata_plan_import_device of f alone, expected traffic 2 (nx+6) nzm ncrms elem bytes. */
+#define MPDATA_LEVEL_ADD 0
+#define MPDATA_LEVEL_ADD_CLIP 1
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  d: a device array on the plan's device;
+ * asynchronous on the plan's stream. */
+int mpdata_plan_level_add_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* d, int mode, int first_tracer,
+                                 int ntracers);
+/* host d, all tracers, synchronous (the plan's block staging buffer, as the 3g / 3h host forms) */
+int mpdata_plan_level_add(mpdata_plan* plan, int64_t sl0, int64_t n, const double* d, int mode);
+int mpdata_plan_level_add_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* d, int mode);
+/* the same on a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm[,ntracers]) with d (ncrms, nzm [, ntracers]),
+ * asynchronous on `stream` (one thread per instance, 64-bit offsets: arrays of 4 GiB and more) */
+int mpdata_level_add_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* d, int mode, void* stream);
+int mpdata_level_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* d, int mode, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
