@@ -115,6 +115,14 @@ def lib():
         for name in ("mpdata_level_add_device", "mpdata_level_add_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, ci, vp]
+        L.mpdata_plan_scale_uw_device.restype = ci
+        L.mpdata_plan_scale_uw_device.argtypes = [vp, i64, i64, vp, vp]
+        for name in ("mpdata_plan_scale_uw", "mpdata_plan_scale_uw_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp]
+        for name in ("mpdata_scale_uw_device", "mpdata_scale_uw_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, dp, dp, dp, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -709,6 +717,28 @@ class Plan:
             raise MpdataError(-1, f"d: shape {tuple(d.shape)} != expected {want}")
         _check(getattr(lib(), "mpdata_plan_level_add" + self._sfx)(self._p, int(sl0), n, pd, int(mode)))
 
+    def scale_uw(self, su=None, sw=None, sl0=0, n=None):
+        """u(sl, :, :) *= su(sl - sl0), w(sl, :, :) *= sw(sl - sl0) on every column and level of instances [sl0, sl0+n)
+        (default: the rest of the plan from sl0), in place, on the plan's stream (mpdata_plan_scale_uw_device).  su, sw:
+        DEVICE tensors (n,) of the plan's precision, only read; None leaves that array as it is.  One rounded multiply
+        per element; no state of the plan changes."""
+        ncrms = self.dims[0]
+        n = ncrms - int(sl0) if n is None else int(n)
+        pu = None if su is None else _dev_ptr(su, (n,), "su", self._tdt())
+        pw = None if sw is None else _dev_ptr(sw, (n,), "sw", self._tdt())
+        _check(lib().mpdata_plan_scale_uw_device(self._p, int(sl0), n, pu, pw))
+
+    def scale_uw_host(self, su=None, sw=None, sl0=0, n=None):
+        """The same from HOST arrays su, sw (numpy, (n,)), synchronous (mpdata_plan_scale_uw[_f32])."""
+        ncrms = self.dims[0]
+        n = ncrms - int(sl0) if n is None else int(n)
+        ptrs = []
+        for name, a in (("su", su), ("sw", sw)):
+            ptrs.append(None if a is None else _host_ptr(a, name, False, self._dt))
+            if a is not None and tuple(a.shape) != (n,):
+                raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {(n,)}")
+        _check(getattr(lib(), "mpdata_plan_scale_uw" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -811,6 +841,27 @@ def level_add(f, d, mode=LEVEL_ADD, stream=None):
     pd = _dev_ptr(d, tuple(f.shape[:-3]) + (nzm, ncrms), "d", f.dtype)
     fn = lib().mpdata_level_add_device if f.dtype == torch.float64 else lib().mpdata_level_add_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, pd, int(mode), _stream_handle(stream)))
+
+
+def scale_uw(u, w, su=None, sw=None, stream=None):
+    """u(sl, :, :) *= su(sl), w(sl, :, :) *= sw(sl) on reference-layout DEVICE tensors u (nzm, nx+5, ncrms), w (nz, nx+4,
+    ncrms), float64 or float32, in place -- every column and level, level nz of w included; su, sw (ncrms,) of the same
+    dtype.  u or w may be None together with its factor.  Asynchronous on `stream` (mpdata_scale_uw_device)."""
+    import torch
+    a = u if u is not None else w
+    if a is None:
+        raise MpdataError(-1, "scale_uw: u and w are both None")
+    if a.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"scale_uw: dtype {a.dtype} is neither float64 nor float32")
+    if a.dim() != 3 or (u is not None and w is not None and w.dim() != 3):
+        raise MpdataError(-1, f"scale_uw: shape {tuple(a.shape)} is no reference-layout u or w")
+    ncrms = a.shape[-1]
+    nx = u.shape[1] - 5 if u is not None else w.shape[1] - 4
+    nz = u.shape[0] + 1 if u is not None else w.shape[0]
+    ptrs = [None if t is None else _dev_ptr(t, sh, k, a.dtype)
+            for k, t, sh in (("u", u, (nz - 1, nx + 5, ncrms)), ("w", w, (nz, nx + 4, ncrms)), ("su", su, (ncrms,)), ("sw", sw, (ncrms,)))]
+    fn = lib().mpdata_scale_uw_device if a.dtype == torch.float64 else lib().mpdata_scale_uw_f32_device
+    _check(fn(ncrms, nx, nz, *ptrs, _stream_handle(stream)))
 
 
 def courant(u, w, rho, adz, clev=None, cinst=None, stream=None):

@@ -16,6 +16,7 @@
 #include "mpdata_courant.h"
 #include "mpdata_internal.h"
 #include "mpdata_level_add.h"
+#include "mpdata_scale_uw.h"
 #include "mpdata_stats.h"
 #include "mpdata_windows.h"
 
@@ -1115,6 +1116,94 @@ int mpdata_level_add_device(int64_t ncrms, int nx, int nz, int ntracers, double*
 }
 int mpdata_level_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* d, int mode, void* stream) {
   return level_add_array(ncrms, nx, nz, ntracers, f, d, mode, stream, 4);
+}
+
+// ---- 3j: one factor per instance on the plan's u and / or w, in place.  Reads su, sw, rewrites every column and level
+// the plan stores of the block's instances: no flag of the plan is touched and no event is recorded.  f, flux, rho, rhow,
+// adz are not looked at, so halo and seam marks are right as they stand; every window of an instance and every level it
+// stores takes the instance's factor, so all stored copies of a tall level change alike; the phantom half follows the
+// plan's last instance inside the kernel (mpdata_scale_uw.h).  A windowed plan's inner plan is rewritten where it lies.
+static int plan_scale_uw(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw) {
+  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
+    const mpdata_plan* q = p->inner ? p->inner : p;
+    MpdataScaleUwJob b;
+    b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
+    b.W = p->inner ? p->W : 1;
+    if (su) { b.j = wm_job(q, 1, nullptr, 0, 1); b.s = su; HIP_TRY(mpdata_scale_uw_wm(b, p->stream)); }
+    if (sw) { b.j = wm_job(q, 2, nullptr, 0, 1); b.s = sw; HIP_TRY(mpdata_scale_uw_wm(b, p->stream)); }
+  } else {
+    if (su) HIP_TRY(mpdata_scale_uw_ref(p->u, p->eb, p->ncrms, sl0, n, p->nx + 5, p->nz - 1, su, p->stream));
+    if (sw) HIP_TRY(mpdata_scale_uw_ref(p->w, p->eb, p->ncrms, sl0, n, p->nx + 4, p->nz, sw, p->stream));
+  }
+  return 0;
+}
+// (the wording of plan_courant_state; only the arrays asked for are tested)
+static int plan_scale_uw_state(const char* what, const mpdata_plan* p, bool u, bool w) {
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
+  if ((u && !p->have_u) || (w && !p->have_w))
+    return set_err(MPDATA_ESTATE, "%s: the plan does not hold %s (mpdata_plan_run_uw used them up: import u and w)", what,
+                   (u && !p->have_u) ? "u" : "w");
+  return 0;
+}
+int mpdata_plan_scale_uw_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw) {
+  int rc = block_range("mpdata_plan_scale_uw_device", p, sl0, n);
+  if (rc) return rc;
+  if (!su && !sw) return set_err(MPDATA_EINVAL, "mpdata_plan_scale_uw_device: su and sw are both NULL");
+  rc = plan_scale_uw_state("mpdata_plan_scale_uw_device", p, su != nullptr, sw != nullptr);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_scale_uw(p, sl0, n, su, sw);
+}
+// host factors, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
+static int plan_scale_uw_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw, int eb) {
+  int rc = block_range("mpdata_plan_scale_uw", p, sl0, n);
+  if (rc) return rc;
+  if (!su && !sw) return set_err(MPDATA_EINVAL, "mpdata_plan_scale_uw: su and sw are both NULL");
+  rc = plan_check(p, eb);
+  if (rc) return rc;
+  rc = plan_scale_uw_state("mpdata_plan_scale_uw", p, su != nullptr, sw != nullptr);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t one = (size_t)n * eb, need = 2 * one;
+  if (p->bstage_bytes < need) {
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->bstage) (void)hipFree(p->bstage);
+    p->bstage = nullptr; p->bstage_bytes = 0;
+    HIP_TRY(hipMalloc(&p->bstage, need));
+    p->bstage_bytes = need;
+  }
+  void* du = su ? p->bstage : nullptr;
+  void* dw = sw ? (char*)p->bstage + one : nullptr;
+  if (su) HIP_TRY(hipMemcpyAsync(du, su, one, hipMemcpyHostToDevice, p->stream));
+  if (sw) HIP_TRY(hipMemcpyAsync(dw, sw, one, hipMemcpyHostToDevice, p->stream));
+  rc = plan_scale_uw(p, sl0, n, du, dw);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+int mpdata_plan_scale_uw(mpdata_plan* p, int64_t sl0, int64_t n, const double* su, const double* sw) {
+  return plan_scale_uw_host(p, sl0, n, su, sw, 8);
+}
+int mpdata_plan_scale_uw_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* su, const float* sw) {
+  return plan_scale_uw_host(p, sl0, n, su, sw, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call)
+static int scale_uw_array(int64_t ncrms, int nx, int nz, void* u, void* w, const void* su, const void* sw, void* stream, int eb) {
+  if (ncrms < 1 || nx < 1 || nz < 2)
+    return set_err(MPDATA_EINVAL, "mpdata_scale_uw_device: bad sizes ncrms=%lld nx=%d nz=%d (need >=1,>=1,>=2)", (long long)ncrms, nx, nz);
+  if (!u && !w) return set_err(MPDATA_EINVAL, "mpdata_scale_uw_device: u and w are both NULL");
+  if (!u != !su || !w != !sw)
+    return set_err(MPDATA_EINVAL, "mpdata_scale_uw_device: %s without %s", !u != !su ? (u ? "u" : "su") : (w ? "w" : "sw"),
+                   !u != !su ? (u ? "su" : "u") : (w ? "sw" : "w"));
+  if (u) HIP_TRY(mpdata_scale_uw_ref(u, eb, ncrms, 0, ncrms, nx + 5, nz - 1, su, (hipStream_t)stream));
+  if (w) HIP_TRY(mpdata_scale_uw_ref(w, eb, ncrms, 0, ncrms, nx + 4, nz, sw, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_scale_uw_device(int64_t ncrms, int nx, int nz, double* u, double* w, const double* su, const double* sw, void* stream) {
+  return scale_uw_array(ncrms, nx, nz, u, w, su, sw, stream, 8);
+}
+int mpdata_scale_uw_f32_device(int64_t ncrms, int nx, int nz, float* u, float* w, const float* su, const float* sw, void* stream) {
+  return scale_uw_array(ncrms, nx, nz, u, w, su, sw, stream, 4);
 }
 
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)

@@ -36,6 +36,8 @@ module mpdata_hip_mod
   ! per-level increments of a resident plan's tracers, in place (include/mpdata_hip.h section 3i)
   public :: mpdata_plan_level_add_device_c, mpdata_plan_level_add_c, mpdata_level_add_device_c
   integer(c_int), parameter, public :: MPDATA_LEVEL_ADD = 0, MPDATA_LEVEL_ADD_CLIP = 1
+  ! one factor per instance on a resident plan's u and w, in place (include/mpdata_hip.h section 3j)
+  public :: mpdata_plan_scale_uw_device_c, mpdata_plan_scale_uw_c, mpdata_scale_uw_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -49,6 +51,8 @@ module mpdata_hip_mod
 #define MPDATA_C_LEVEL_STATS_DEVICE "mpdata_level_stats_f32_device"
 #define MPDATA_C_PLAN_LEVEL_ADD "mpdata_plan_level_add_f32"
 #define MPDATA_C_LEVEL_ADD_DEVICE "mpdata_level_add_f32_device"
+#define MPDATA_C_PLAN_SCALE_UW "mpdata_plan_scale_uw_f32"
+#define MPDATA_C_SCALE_UW_DEVICE "mpdata_scale_uw_f32_device"
 #else
 #define MPDATA_C_ADVECT "mpdata_advect_scalar2d"
 #define MPDATA_C_PLAN_CREATE "mpdata_plan_create"
@@ -60,6 +64,8 @@ module mpdata_hip_mod
 #define MPDATA_C_LEVEL_STATS_DEVICE "mpdata_level_stats_device"
 #define MPDATA_C_PLAN_LEVEL_ADD "mpdata_plan_level_add"
 #define MPDATA_C_LEVEL_ADD_DEVICE "mpdata_level_add_device"
+#define MPDATA_C_PLAN_SCALE_UW "mpdata_plan_scale_uw"
+#define MPDATA_C_SCALE_UW_DEVICE "mpdata_scale_uw_device"
 #endif
 
   interface
@@ -288,6 +294,31 @@ module mpdata_hip_mod
       integer(c_int), value :: nx, nz, ntracers
       type(c_ptr), value :: f, d
       integer(c_int), value :: mode
+      type(c_ptr), value :: stream
+    end function
+    ! section 3j: u(sl,:,:) = u(sl,:,:) * su(sl-sl0+1), w(sl,:,:) = w(sl,:,:) * sw(sl-sl0+1) on every column and level of
+    ! instances [sl0, sl0+n), in place; su(n), sw(n) are only read, c_null_ptr leaves that array as it is.
+    ! su, sw device arrays of the plan's precision, asynchronous on the plan's stream:
+    integer(c_int) function mpdata_plan_scale_uw_device_c(plan, sl0, n, su, sw) bind(C, name="mpdata_plan_scale_uw_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: su, sw
+    end function
+    ! host su, sw (c_loc of an array of the module's precision, or c_null_ptr), synchronous
+    integer(c_int) function mpdata_plan_scale_uw_c(plan, sl0, n, su, sw) bind(C, name=MPDATA_C_PLAN_SCALE_UW)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: su, sw
+    end function
+    ! the same on reference-layout device arrays u, w with device arrays su(ncrms), sw(ncrms); u or w may be c_null_ptr
+    ! together with its factor
+    integer(c_int) function mpdata_scale_uw_device_c(ncrms, nx, nz, u, w, su, sw, stream) bind(C, name=MPDATA_C_SCALE_UW_DEVICE)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz
+      type(c_ptr), value :: u, w, su, sw
       type(c_ptr), value :: stream
     end function
   end interface

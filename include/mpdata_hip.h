@@ -434,6 +434,45 @@ int mpdata_plan_level_add_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const f
 int mpdata_level_add_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* d, int mode, void* stream);
 int mpdata_level_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* d, int mode, void* stream);
 
+/* ---- 3j. Scale a resident plan's velocities in place, one factor per instance (the write side of 3h: SAM's kurant turns
+ * the Courant number into ncycle and advects ncycle times on u / ncycle, w / ncycle; a plan's u and w have no export, so
+ * the factor is applied where they lie).  For every instance sl in [sl0, sl0 + n):
+ *   u(sl, :, :) = u(sl, :, :) * su(sl - sl0)        every column -1 .. nx+3 and level the plan stores
+ *   w(sl, :, :) = w(sl, :, :) * sw(sl - sl0)        every column -1 .. nx+2 and level the plan stores
+ * Each element takes one correctly rounded multiply in the plan's precision; a single multiply leaves nothing to
+ * contract, so EXACT and FAST plans get the same bits.  su, sw: arrays of n reals of the plan's precision, only read;
+ * either may be NULL, which leaves that array as it is.  The factors are used as given: they are not validated, and a
+ * zero, negative or non-finite factor does what IEEE says.  A factor of 1 leaves every bit, and the results of a run, as
+ * they were.  Scaling by 1/m and later by m is NOT the identity unless m is a power of two (two roundings): a caller
+ * that wants the unscaled velocities back imports them again.
+ * Nothing is fused into the run and nothing is kept between calls.  No plan state changes (filled, have_u, have_w, halo
+ * and seam marks, the boundary mode, the stream, the timing pair and last_kernel_ms stay), outside the run's event pair;
+ * f, flux, rho, rhow, adz and every instance outside the range keep every bit.  Windowed plans (3e): every window of an
+ * instance, and every level a window stores whether owned or not, takes that instance's factor, so all stored copies of a
+ * tall level change alike.  Odd fp32 plans (3f): the phantom half follows instance ncrms - 1.  An fp32 block that splits
+ * a pair stores the partner's half back exactly as loaded (no multiply by 1).  A kernel of its own on every kind of plan
+ * (wave-major: a wave walks the column slots of its tile's chunk as a linear read-modify-write stream, eight columns in
+ * flight, its factor in a register; one launch per array); the plan kernels are not touched.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms); su and sw both NULL; in the array forms bad sizes
+ * (ncrms < 1, nx < 1, nz < 2), no array at all, a factor without its array or an array without its factor.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3i: take mpdata_plan_shard_plan(plan, g) and a shard-local sl0.
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled; a plan that does not hold the array being
+ * scaled (after mpdata_plan_run_uw it holds neither; only the arrays asked for are tested).
+ * Time on the MI355X (docs/EXPERIMENTS.md M, tools/scale_uw_bench.py): not measured yet; the yardstick is
+ * mpdata_plan_import_device of u and w alone, expected traffic about 4 (nx+6) nzm ncrms elem bytes. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  su, sw: device arrays on the plan's device;
+ * asynchronous on the plan's stream. */
+int mpdata_plan_scale_uw_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* su, const void* sw);
+/* host su, sw, synchronous (the plan's block staging buffer, as the 3g - 3i host forms) */
+int mpdata_plan_scale_uw(mpdata_plan* plan, int64_t sl0, int64_t n, const double* su, const double* sw);
+int mpdata_plan_scale_uw_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* su, const float* sw);
+/* the same on reference-layout DEVICE arrays u(ncrms,-1:nx+3,1,nzm), w(ncrms,-1:nx+2,1,nz) with su, sw (ncrms) -- for
+ * callers of mpdata_plan_run_uw.  Every column and every level the shapes hold is scaled, level nz of w included.  u or w
+ * may be NULL together with its factor.  Asynchronous on `stream` (one thread per instance, 64-bit offsets). */
+int mpdata_scale_uw_device(int64_t ncrms, int nx, int nz, double* u, double* w, const double* su, const double* sw, void* stream);
+int mpdata_scale_uw_f32_device(int64_t ncrms, int nx, int nz, float* u, float* w, const float* su, const float* sw, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
