@@ -636,36 +636,46 @@ class Plan:
         ptrs = _host_ptrs((("f", f), ("flux", flux)), (n, nx, nz, nt), self._dt, writable=("f", "flux"))
         _check(getattr(lib(), "mpdata_plan_download_instances" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def _block_n(self, sl0, n):
+        """n of a block call: as given, or the rest of the plan from sl0"""
+        return self.dims[0] - int(sl0) if n is None else int(n)
+
+    def _block_dev_shape(self, t, n):
+        """(shape, ntr) of a device tensor ([ntr,] nzm, n) of a block call: ntr the leading axis of a 3-d tensor"""
+        ntr = int(t.shape[0]) if t.dim() == 3 else 1
+        return ((ntr,) if t.dim() == 3 else ()) + (self.dims[2] - 1, n), ntr
+
+    def _block_host_shape(self, a, name, n):
+        """a host array of a block call is (n, nzm[, ntracers]) (one tracer: with or without the last axis)"""
+        nt = self.dims[3]
+        want = (n, self.dims[2] - 1) + ((nt,) if nt > 1 else ())
+        if tuple(a.shape) != want and not (nt == 1 and tuple(a.shape) == want + (1,)):
+            raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {want}")
+
     def level_stats(self, sl0=0, n=None, sum=None, min=None, max=None, first_tracer=0):
         """Horizontal sum / min / max per level of f over the interior columns 1 .. nx, instances [sl0, sl0+n) (default:
         the rest of the plan from sl0) -> reference-layout DEVICE tensors ([ntr,] nzm, n) of the plan's precision, on the
         plan's stream (mpdata_plan_level_stats_device).  None = not wanted; the tracers are first_tracer .. +ntr-1, ntr the
         leading axis of a 3-d tensor.  Changes nothing of the plan."""
-        ncrms, _, nz, _ = self.dims
-        n = ncrms - int(sl0) if n is None else int(n)
+        n = self._block_n(sl0, n)
         given = [(k, t) for k, t in (("sum", sum), ("min", min), ("max", max)) if t is not None]
         if not given:
             raise MpdataError(-1, "level_stats: sum, min and max are all None")
-        ntr = int(given[0][1].shape[0]) if given[0][1].dim() == 3 else 1
-        sh = ((ntr,) if given[0][1].dim() == 3 else ()) + (nz - 1, n)
+        sh, ntr = self._block_dev_shape(given[0][1], n)
         ptrs = [None if t is None else _dev_ptr(t, sh, k, self._tdt()) for k, t in (("sum", sum), ("min", min), ("max", max))]
         _check(lib().mpdata_plan_level_stats_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
 
     def level_stats_host(self, sl0=0, n=None, sum=None, min=None, max=None):
         """The same for all tracers into HOST arrays (numpy, Fortran order, (n, nzm[, ntracers]); None = not wanted),
         synchronous (mpdata_plan_level_stats[_f32])."""
-        ncrms, _, nz, nt = self.dims
-        n = ncrms - int(sl0) if n is None else int(n)
-        want = (n, nz - 1) + ((nt,) if nt > 1 else ())
+        n = self._block_n(sl0, n)
         ptrs = []
         for k, a in (("sum", sum), ("min", min), ("max", max)):
             if a is None:
                 ptrs.append(None)
                 continue
-            p = _host_ptr(a, k, True, self._dt)
-            if tuple(a.shape) != want and not (nt == 1 and tuple(a.shape) == want + (1,)):
-                raise MpdataError(-1, f"{k}: shape {tuple(a.shape)} != expected {want}")
-            ptrs.append(p)
+            ptrs.append(_host_ptr(a, k, True, self._dt))
+            self._block_host_shape(a, k, n)
         if all(p is None for p in ptrs):
             raise MpdataError(-1, "level_stats_host: sum, min and max are all None")
         _check(getattr(lib(), "mpdata_plan_level_stats" + self._sfx)(self._p, int(sl0), n, *ptrs))
@@ -675,8 +685,8 @@ class Plan:
         from sl0) -> DEVICE tensors of the plan's precision on the plan's stream (mpdata_plan_courant_device): clev (nzm, n)
         the max over the interior columns per level, cinst (n,) its max over the levels.  None = not wanted.  Changes
         nothing of the plan."""
-        ncrms, _, nz, _ = self.dims
-        n = ncrms - int(sl0) if n is None else int(n)
+        nz = self.dims[2]
+        n = self._block_n(sl0, n)
         if clev is None and cinst is None:
             raise MpdataError(-1, "courant: clev and cinst are both None")
         pl = None if clev is None else _dev_ptr(clev, (nz - 1, n), "clev", self._tdt())
@@ -685,8 +695,8 @@ class Plan:
 
     def courant_host(self, sl0=0, n=None):
         """The same into new HOST arrays, synchronous (mpdata_plan_courant[_f32]) -> (clev (n, nzm) Fortran order, cinst (n,))"""
-        ncrms, _, nz, _ = self.dims
-        n = ncrms - int(sl0) if n is None else int(n)
+        nz = self.dims[2]
+        n = self._block_n(sl0, n)
         if n < 1:
             raise MpdataError(-1, f"courant_host: a block of n = {n} instances")
         clev = np.zeros((n, nz - 1), self._dt, order="F")
@@ -700,21 +710,17 @@ class Plan:
         plan from sl0), in place, on the plan's stream (mpdata_plan_level_add_device); mode LEVEL_ADD_CLIP: max(0, .) of the
         sum.  d: a reference-layout DEVICE tensor ([ntr,] nzm, n) of the plan's precision -- the shape of a level_stats
         output; the tracers are first_tracer .. +ntr-1, ntr the leading axis of a 3-d tensor.  d is only read."""
-        ncrms, _, nz, _ = self.dims
-        n = ncrms - int(sl0) if n is None else int(n)
-        ntr = int(d.shape[0]) if d.dim() == 3 else 1
-        pd = _dev_ptr(d, ((ntr,) if d.dim() == 3 else ()) + (nz - 1, n), "d", self._tdt())
+        n = self._block_n(sl0, n)
+        sh, ntr = self._block_dev_shape(d, n)
+        pd = _dev_ptr(d, sh, "d", self._tdt())
         _check(lib().mpdata_plan_level_add_device(self._p, int(sl0), n, pd, int(mode), int(first_tracer), ntr))
 
     def level_add_host(self, d, sl0=0, n=None, mode=LEVEL_ADD):
         """The same for all tracers from a HOST array d (numpy, Fortran order, (n, nzm[, ntracers])), synchronous
         (mpdata_plan_level_add[_f32])."""
-        ncrms, _, nz, nt = self.dims
-        n = ncrms - int(sl0) if n is None else int(n)
-        want = (n, nz - 1) + ((nt,) if nt > 1 else ())
+        n = self._block_n(sl0, n)
         pd = _host_ptr(d, "d", False, self._dt)
-        if tuple(d.shape) != want and not (nt == 1 and tuple(d.shape) == want + (1,)):
-            raise MpdataError(-1, f"d: shape {tuple(d.shape)} != expected {want}")
+        self._block_host_shape(d, "d", n)
         _check(getattr(lib(), "mpdata_plan_level_add" + self._sfx)(self._p, int(sl0), n, pd, int(mode)))
 
     def scale_uw(self, su=None, sw=None, sl0=0, n=None):
@@ -722,16 +728,14 @@ class Plan:
         (default: the rest of the plan from sl0), in place, on the plan's stream (mpdata_plan_scale_uw_device).  su, sw:
         DEVICE tensors (n,) of the plan's precision, only read; None leaves that array as it is.  One rounded multiply
         per element; no state of the plan changes."""
-        ncrms = self.dims[0]
-        n = ncrms - int(sl0) if n is None else int(n)
+        n = self._block_n(sl0, n)
         pu = None if su is None else _dev_ptr(su, (n,), "su", self._tdt())
         pw = None if sw is None else _dev_ptr(sw, (n,), "sw", self._tdt())
         _check(lib().mpdata_plan_scale_uw_device(self._p, int(sl0), n, pu, pw))
 
     def scale_uw_host(self, su=None, sw=None, sl0=0, n=None):
         """The same from HOST arrays su, sw (numpy, (n,)), synchronous (mpdata_plan_scale_uw[_f32])."""
-        ncrms = self.dims[0]
-        n = ncrms - int(sl0) if n is None else int(n)
+        n = self._block_n(sl0, n)
         ptrs = []
         for name, a in (("su", su), ("sw", sw)):
             ptrs.append(None if a is None else _host_ptr(a, name, False, self._dt))

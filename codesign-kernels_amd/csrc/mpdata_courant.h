@@ -12,21 +12,18 @@
 #define MPDATA_COURANT_H
 #include <hip/hip_runtime.h>
 
-#include "mpdata_layout.h"
+#include "mpdata_wm_walk.h"
 
 // Plan layout.  j: the plan side of u exactly as wm_job(which = 1) makes it (strides in 8-byte elements, j.prv_col0 = 1;
 // j.ref is not used); w: the plan side of w (the same geometry, another base); rho, adz: that array's slab in the plan's
 // unsplit [tile][3][instance][level] array, element e of tile t at base + t * kc_tile_stride + e.
-//   ipe, sl0, n, ncrms, W, nz: as in MpdataStatsJob (mpdata_stats.h) -- W > 1: j describes the INNER plan of a windowed
-//   plan, slot q = sl * W + h is window h of instance sl, and only OWNED levels reach the outputs (an owned level's k + 1
+//   sel: the block (mpdata_wm_walk.h).  Only OWNED levels of a windowed plan reach the outputs (an owned level's k + 1
 //   lies inside its window; the last window's top is the real level nz, the +0).
 struct MpdataCourantJob {
   MpdataLayoutJob j;
   const void *w, *rho, *adz;
   long long kc_tile_stride;
-  long long sl0, n, ncrms;
-  int ipe;
-  int W, nz;
+  MpdataBlockSel sel;
   void *clev, *cinst;
 };
 // the grid covers the tiles the block touches; cinst (if given) is zeroed first

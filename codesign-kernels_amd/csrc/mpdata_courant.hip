@@ -1,8 +1,8 @@
 // mpdata_courant.hip -- outflow Courant number of the velocities per level and per instance (include/mpdata_hip.h 3h,
 // mpdata_courant.h): the coefficient 1 - c of f(i,k) in the routine's upwind pass, a reduction over the interior columns
 // 1 .. nx in a kernel of its own outside the run (nothing is fused into the plan kernels, nothing is kept between calls).
-//   plan layout: as the level statistics (mpdata_stats.hip) a wave owns 64 elements of a tile's column chunk and walks
-//     the column slots as linear streams -- here of two arrays, u and w; u(i+1) is the lane's next column and is carried
+//   plan layout: the walk of mpdata_wm_walk.h, as the level statistics (mpdata_stats.hip) -- here the linear streams
+//     of two arrays, u and w; u(i+1) is the lane's next column and is carried
 //     over, w(k+1) is element e + 1 of the same column, loaded through an address of its own (e and e + 1 can lie on
 //     different sides of the main / rest split of a chunk; the lines are the ones the wave has just asked for).
 //   reference layout: one thread per instance, coalesced along sl, the loop over i.
@@ -11,11 +11,10 @@
 #include <cstdint>
 
 #include "mpdata_courant.h"
-#include "mpdata_windows.h"
 
 namespace {
 
-constexpr int NB = 8;   // columns in flight per lane
+using namespace wm_walk;
 
 template <typename R> struct Real;
 template <> struct Real<double> {
@@ -31,23 +30,6 @@ template <> struct Real<float> {
   __device__ static float hi(float a, float b) { return fmaxf(a, b); }
   __device__ static float abs(float a) { return fabsf(a); }
   __device__ static U bits(float a) { return __float_as_uint(a); }
-};
-
-template <typename R2> struct Elem;
-template <> struct Elem<double> {
-  typedef double R;
-  static constexpr int N = 1;
-  __device__ static double get(const double& v, int) { return v; }
-};
-template <> struct Elem<float2> {
-  typedef float R;
-  static constexpr int N = 2;
-  __device__ static float get(const float2& v, int h) { return h ? v.y : v.x; }
-};
-template <> struct Elem<float> {
-  typedef float R;
-  static constexpr int N = 1;
-  __device__ static float get(const float& v, int) { return v; }
 };
 
 // the definition; the sign is cleared last (a, b and c can come out as -0.0 from signed zeros in u, w)
@@ -130,24 +112,24 @@ __global__ void __launch_bounds__(256) wm_courant_kernel(const MpdataCourantJob 
   }
   march<R2>(static_cast<const R2*>(j.prv) + o0, static_cast<const R2*>(b.w) + o0, static_cast<const R2*>(b.w) + o1, su, sw1, nx, top,
             iadz, irho, m);
-  const int nlev_out = b.nz - 1;
+  const int nlev_out = b.sel.nz - 1;
 #pragma unroll
   for (int h = 0; h < E::N; ++h) {
     const long long q = (tile * j.slp + s) * E::N + h;   // slot: instance, or pseudo-instance of a windowed plan
     long long sl = q;
     int k = kk;
     bool inst = act, owned = true;
-    if (b.W > 1) {
-      sl = q / b.W;
+    if (b.sel.W > 1) {
+      sl = q / b.sel.W;
       int k0 = 0, nz_w, own0 = 1, own1 = 0;
-      if (mpd_level_window(b.nz, (int)(q - sl * b.W), &k0, &nz_w, &own0, &own1) != b.W) inst = false;
+      if (mpd_level_window(b.sel.nz, (int)(q - sl * b.sel.W), &k0, &nz_w, &own0, &own1) != b.sel.W) inst = false;
       k = k0 + kk;
       owned = k + 1 >= own0 && k + 1 <= own1;
     }
     // padding, phantom, the partner of a split pair, a neighbour in the tile: no output
-    if (sl < b.sl0 || sl >= b.sl0 + b.n) inst = false;
+    if (sl < b.sel.sl0 || sl >= b.sel.sl0 + b.sel.n) inst = false;
     const bool st = inst && owned;
-    if (st && b.clev) static_cast<R*>(b.clev)[(sl - b.sl0) + b.n * k] = m[h];
+    if (st && b.clev) static_cast<R*>(b.clev)[(sl - b.sel.sl0) + b.sel.n * k] = m[h];
     if (b.cinst) {
       // the lanes of one instance are consecutive: a suffix max inside the instance, then one atomic by its first lane
       R v = st ? m[h] : (R)0;
@@ -156,7 +138,7 @@ __global__ void __launch_bounds__(256) wm_courant_kernel(const MpdataCourantJob 
         const R o = __shfl_down(v, d, 64);
         if (lane + d < 64 && kk + d < nlev) v = Real<R>::hi(v, o);
       }
-      if (inst && (lane == 0 || kk == 0)) atomicMax(static_cast<U*>(b.cinst) + (sl - b.sl0), Real<R>::bits(v));
+      if (inst && (lane == 0 || kk == 0)) atomicMax(static_cast<U*>(b.cinst) + (sl - b.sel.sl0), Real<R>::bits(v));
     }
   }
 }
@@ -186,27 +168,11 @@ __global__ void __launch_bounds__(256) ref_courant_kernel(const R* u, const R* w
 }  // namespace
 
 hipError_t mpdata_courant_wm(const MpdataCourantJob& b, hipStream_t stream) {
-  const MpdataLayoutJob& j = b.j;
-  if (!j.prv || !b.w || !b.rho || !b.adz || j.nlev < 1 || j.slp < 1 || j.ntiles < 1 || j.ncol_p < 7 || j.prv_col0 != 1 ||
-      j.chunk != (long long)j.slp * j.nlev || j.main_e < 0 || j.main_e > j.chunk || b.kc_tile_stride < j.chunk ||
-      (b.ipe != 1 && b.ipe != 2) || b.W < 1 || (!b.clev && !b.cinst))
-    return hipErrorInvalidValue;
-  if (b.sl0 < 0 || b.n < 1 || b.sl0 + b.n > b.ncrms) return hipErrorInvalidValue;
-  const long long spt = (long long)j.slp * b.ipe;   // slots per tile
-  if (b.ncrms * b.W > (long long)j.ntiles * spt) return hipErrorInvalidValue;
-  if (b.W == 1 ? b.nz != j.nlev + 1 : (j.slp != 1 || b.nz <= j.nlev + 1)) return hipErrorInvalidValue;
-  const long long t0 = b.sl0 * b.W / spt, t1 = ((b.sl0 + b.n) * b.W - 1) / spt;
-  const int nslice = (int)((j.chunk + 63) / 64);
-  const long long waves = (t1 - t0 + 1) * nslice;
-  if (t1 - t0 + 1 > 2147483647LL || (waves + 3) / 4 > 2147483647LL) return hipErrorInvalidValue;
-  if (b.cinst) {
-    const hipError_t e = hipMemsetAsync(b.cinst, 0, (size_t)b.n * (8 / b.ipe), stream);
-    if (e != hipSuccess) return e;
-  }
-  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  if (b.ipe == 1) hipLaunchKernelGGL((wm_courant_kernel<double>), grid, block, 0, stream, b, t0, (int)(t1 - t0 + 1), nslice);
-  else hipLaunchKernelGGL((wm_courant_kernel<float2>), grid, block, 0, stream, b, t0, (int)(t1 - t0 + 1), nslice);
-  return hipGetLastError();
+  WmGrid g;
+  if (!b.w || !b.rho || !b.adz || b.j.prv_col0 != 1 || b.kc_tile_stride < b.j.chunk || (!b.clev && !b.cinst)) return hipErrorInvalidValue;
+  hipError_t e = wm_block_grid(b.j, b.sel, 1, &g);
+  if (e == hipSuccess && b.cinst) e = hipMemsetAsync(b.cinst, 0, (size_t)b.sel.n * (8 / b.sel.ipe), stream);
+  return e != hipSuccess ? e : wm_block_launch(wm_courant_kernel<double>, wm_courant_kernel<float2>, b, g, stream);
 }
 
 hipError_t mpdata_courant_ref(const void* u, const void* w, const void* rho, const void* adz, int elem_bytes, long long ld,
@@ -214,14 +180,13 @@ hipError_t mpdata_courant_ref(const void* u, const void* w, const void* rho, con
   if (!u || !w || !rho || !adz || ld < 1 || sl0 < 0 || n < 1 || sl0 + n > ld || nx < 1 || nz < 2 || (!clev && !cinst) ||
       (elem_bytes != 4 && elem_bytes != 8))
     return hipErrorInvalidValue;
-  const long long gx = (n + 255) / 256;
-  if (gx > 2147483647LL) return hipErrorInvalidValue;
+  const int nzm = nz - 1;
+  dim3 grid, block(256);
+  if (ref_block_grid(n, nzm, &grid) != hipSuccess) return hipErrorInvalidValue;
   if (cinst) {
     const hipError_t e = hipMemsetAsync(cinst, 0, (size_t)n * elem_bytes, stream);
     if (e != hipSuccess) return e;
   }
-  const int nzm = nz - 1;
-  const dim3 grid((unsigned)gx, (unsigned)(nzm < 65535 ? nzm : 65535)), block(256);
   if (elem_bytes == 8)
     hipLaunchKernelGGL((ref_courant_kernel<double>), grid, block, 0, stream, static_cast<const double*>(u), static_cast<const double*>(w),
                        static_cast<const double*>(rho), static_cast<const double*>(adz), ld, sl0, n, nx, nzm, static_cast<double*>(clev),

@@ -8,26 +8,19 @@
 #define MPDATA_LEVEL_ADD_H
 #include <hip/hip_runtime.h>
 
-#include "mpdata_layout.h"
+#include "mpdata_wm_walk.h"
 
 // Plan layout.  j: the plan side of f exactly as wm_job(which = 0) makes it for tracers [first, first + j.ntr) (j.prv on
 // the first of them, strides in 8-byte elements; j.ref is not used).  The kernel needs the storage layout only: element
 // e = s * nlev + kk of column slot c of a tile, split into whole 128-byte lines and a rest (mpdata_layout.h).
-//   ipe: reals per 8-byte element -- 1 (fp64), 2 (fp32 plans: pairs of adjacent instances)
-//   sl0, n, ncrms: the block and the plan's size in REAL instances.  A slot that is no instance of the block -- the
-//     padding of the last tile, a neighbour in the tile, the partner of a pair the block's ends split -- keeps its bits
-//     (the partner half of a split pair is stored back as it was loaded).  The one exception: with ipe = 2 and an odd
-//     number of slots in use the slot behind the last one is the PHANTOM (include/mpdata_hip.h 3f); it takes the
-//     increment of the last instance whenever the block holds that instance, and so stays its copy.
-//   W = 1: j describes the plan itself, nz = j.nlev + 1.
-//   W > 1: j describes the INNER plan of a windowed plan (mpdata_windows.h): slot q = sl * W + h is window h of
-//     instance sl, nz the levels of the tall column; EVERY level a window stores (owned or not) takes the increment of
-//     the tall level it stands for, so that all stored copies of a tall level stay as consistent as they were.
+//   sel: the block (mpdata_wm_walk.h).  A slot that is no instance of it keeps its bits (the partner half of a split
+//     pair is stored back as it was loaded).  The one exception is the PHANTOM of an odd fp32 plan (include/mpdata_hip.h 3f):
+//     it takes the increment of the last instance whenever the block holds that instance, and so stays its copy.
+//     EVERY level a window of a windowed plan stores (owned or not) takes the increment of the tall level it stands
+//     for, so that all stored copies of a tall level stay as consistent as they were.
 struct MpdataLevelAddJob {
   MpdataLayoutJob j;
-  long long sl0, n, ncrms;
-  int ipe;
-  int W, nz;
+  MpdataBlockSel sel;
   const void* d;
   int clip;
 };

@@ -2,43 +2,21 @@
 // f(sl, i, k, t) = f(sl, i, k, t) + d(sl, k, t) on EVERY column slot i = -2 .. nx+3, optionally clipped at zero -- the
 // large-scale forcing of a host model, the write side of the level statistics (mpdata_stats.hip).  A kernel of its own
 // outside the run: nothing is fused into the plan kernels.
-//   plan layout: a column chunk of a tile is contiguous ([tile][column][instance][level], the whole 128-byte lines of
-//     every column first, the rests behind them), so a wave that owns 64 elements of a chunk and walks all nx + 6 column
-//     slots reads and writes f once as a linear stream -- 512 bytes per wave and column, eight columns in flight -- with
-//     its increment in a register.  The kernel knows the storage layout only: LPS 8 .. 64, the one-instance-per-tile
-//     forms above 64 levels (several 64-element slices per tile) and the windows of tall plans are the same code with
-//     other constants.
+//   plan layout: the walk of mpdata_wm_walk.h over all nx + 6 column slots reads and writes f once as a linear stream
+//     -- 512 bytes per wave and column, eight columns in flight -- with its increment in a register.
 //   reference layout: one thread per instance, coalesced along sl, the loop over the columns.
 // Built with -ffp-contract=off; every result is one rounded add (and the hardware max), nothing here multiplies.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "mpdata_level_add.h"
-#include "mpdata_windows.h"
 
 namespace {
 
-constexpr int NB = 8;   // columns in flight per lane
+using namespace wm_walk;
 
-template <typename R2> struct Elem;
-template <> struct Elem<double> {
-  typedef double R;
-  static constexpr int N = 1;
-  __device__ static double& at(double& v, int) { return v; }
-  __device__ static double pos(double a) { return fmax(a, 0.0); }
-};
-template <> struct Elem<float2> {
-  typedef float R;
-  static constexpr int N = 2;
-  __device__ static float& at(float2& v, int h) { return h ? v.y : v.x; }
-  __device__ static float pos(float a) { return fmaxf(a, 0.0f); }
-};
-template <> struct Elem<float> {
-  typedef float R;
-  static constexpr int N = 1;
-  __device__ static float& at(float& v, int) { return v; }
-  __device__ static float pos(float a) { return fmaxf(a, 0.0f); }
-};
+__device__ inline double pos(double a) { return fmax(a, 0.0); }
+__device__ inline float pos(float a) { return fmaxf(a, 0.0f); }
 
 // ncol elements p[0], p[step], ... of a lane := element + dv (clipped): all NB loads of a batch are issued before the
 // first store (the index is clamped, not predicated: a conditional load would be waited for on its own; the clamped
@@ -64,7 +42,7 @@ __device__ inline void march_add(R2* p, const long long step, const int ncol, co
           for (int h = 0; h < E::N; ++h) {
             typename E::R& x = E::at(v[u], h);
             const typename E::R y = x + dv[h];
-            x = on[h] ? (clip ? E::pos(y) : y) : x;
+            x = on[h] ? (clip ? pos(y) : y) : x;
           }
           p[(long long)(c + u) * step] = v[u];
         }
@@ -97,8 +75,8 @@ __global__ void __launch_bounds__(256) wm_level_add_kernel(const MpdataLevelAddJ
   R2* p = static_cast<R2*>(j.prv) + (long long)tr * j.prv_tstride + tile * j.prv_tile_stride +
           (in_main ? e : (long long)j.ncol_p * j.main_e + (e - j.main_e));   // column slot 0
   // the increment of every half: the instance and the tall level the slot stands for
-  const int nlev_d = b.nz - 1;
-  const long long nslots = b.ncrms * b.W;   // slots that are an instance (a window of one)
+  const int nlev_d = b.sel.nz - 1;
+  const long long nslots = b.sel.ncrms * b.sel.W;   // slots that are an instance (a window of one)
   R dv[E::N];
   bool on[E::N];
 #pragma unroll
@@ -108,15 +86,15 @@ __global__ void __launch_bounds__(256) wm_level_add_kernel(const MpdataLevelAddJ
     long long sl = q;
     int k = kk;
     bool ok = act;
-    if (b.W > 1) {
-      sl = q / b.W;
+    if (b.sel.W > 1) {
+      sl = q / b.sel.W;
       int k0 = 0, nz_w, own0, own1;
-      ok = ok && mpd_level_window(b.nz, (int)(q - sl * b.W), &k0, &nz_w, &own0, &own1) == b.W;
+      ok = ok && mpd_level_window(b.sel.nz, (int)(q - sl * b.sel.W), &k0, &nz_w, &own0, &own1) == b.sel.W;
       k = k0 + kk;
     }
-    ok = ok && sl >= b.sl0 && sl < b.sl0 + b.n && k < nlev_d;   // else: padding, the partner of a split pair, a neighbour in the tile
+    ok = ok && sl >= b.sel.sl0 && sl < b.sel.sl0 + b.sel.n && k < nlev_d;   // else: padding, the partner of a split pair, a neighbour in the tile
     on[h] = ok;
-    dv[h] = ok ? static_cast<const R*>(b.d)[(sl - b.sl0) + b.n * (k + (long long)nlev_d * tr)] : (R)0;
+    dv[h] = ok ? static_cast<const R*>(b.d)[(sl - b.sel.sl0) + b.sel.n * (k + (long long)nlev_d * tr)] : (R)0;
   }
   bool any = false;
 #pragma unroll
@@ -142,31 +120,18 @@ __global__ void __launch_bounds__(256) ref_level_add_kernel(R* f, const long lon
 }  // namespace
 
 hipError_t mpdata_level_add_wm(const MpdataLevelAddJob& b, hipStream_t stream) {
-  const MpdataLayoutJob& j = b.j;
-  if (!j.prv || j.ntr < 1 || j.nlev < 1 || j.slp < 1 || j.ntiles < 1 || j.ncol_p < 7 || j.chunk != (long long)j.slp * j.nlev ||
-      j.main_e < 0 || j.main_e > j.chunk || (b.ipe != 1 && b.ipe != 2) || b.W < 1 || !b.d)
-    return hipErrorInvalidValue;
-  if (b.sl0 < 0 || b.n < 1 || b.sl0 + b.n > b.ncrms) return hipErrorInvalidValue;
-  const long long spt = (long long)j.slp * b.ipe;   // slots per tile
-  if (b.ncrms * b.W > (long long)j.ntiles * spt) return hipErrorInvalidValue;
-  if (b.W == 1 ? b.nz != j.nlev + 1 : (j.slp != 1 || b.nz <= j.nlev + 1)) return hipErrorInvalidValue;
-  // (the phantom shares its 8-byte element, hence its tile, with the last slot)
-  const long long t0 = b.sl0 * b.W / spt, t1 = ((b.sl0 + b.n) * b.W - 1) / spt;
-  const int nslice = (int)((j.chunk + 63) / 64);
-  const long long waves = (long long)j.ntr * (t1 - t0 + 1) * nslice;
-  if (t1 >= j.ntiles || t1 - t0 + 1 > 2147483647LL || (waves + 3) / 4 > 2147483647LL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  if (b.ipe == 1) hipLaunchKernelGGL((wm_level_add_kernel<double>), grid, block, 0, stream, b, t0, (int)(t1 - t0 + 1), nslice);
-  else hipLaunchKernelGGL((wm_level_add_kernel<float2>), grid, block, 0, stream, b, t0, (int)(t1 - t0 + 1), nslice);
-  return hipGetLastError();
+  WmGrid g;
+  if (!b.d) return hipErrorInvalidValue;
+  const hipError_t e = wm_block_grid(b.j, b.sel, b.j.ntr, &g);
+  return e != hipSuccess ? e : wm_block_launch(wm_level_add_kernel<double>, wm_level_add_kernel<float2>, b, g, stream);
 }
 
 hipError_t mpdata_level_add_ref(void* f, int elem_bytes, long long ld, long long sl0, long long n, int nx, int nlev, int ntr,
                                 const void* d, int clip, hipStream_t stream) {
   if (!f || !d || ld < 1 || sl0 < 0 || n < 1 || sl0 + n > ld || nx < 1 || nlev < 1 || ntr < 1) return hipErrorInvalidValue;
-  const long long rows = (long long)nlev * ntr, gx = (n + 255) / 256;
-  if (gx > 2147483647LL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)gx, (unsigned)(rows < 65535 ? rows : 65535)), block(256);
+  const long long rows = (long long)nlev * ntr;
+  dim3 grid, block(256);
+  if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
   if (elem_bytes == 8)
     hipLaunchKernelGGL((ref_level_add_kernel<double>), grid, block, 0, stream, static_cast<double*>(f), ld, sl0, n, nx, rows,
                        static_cast<const double*>(d), clip);

@@ -558,6 +558,34 @@ int block_range(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n) 
                    (long long)p->ncrms);
   return 0;
 }
+// the plan's block staging buffer (device memory the host forms of the block calls go through): at least `need` bytes
+int plan_bstage(mpdata_plan* p, size_t need) {
+  if (p->bstage_bytes >= need) return 0;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (p->bstage) (void)hipFree(p->bstage);
+  p->bstage = nullptr; p->bstage_bytes = 0;
+  HIP_TRY(hipMalloc(&p->bstage, need));
+  p->bstage_bytes = need;
+  return 0;
+}
+// a block of a plan for the kernels that walk its plan layout (mpdata_wm_walk.h), with wm_plan(p) the plan the layout
+// jobs are made of: a windowed plan's inner plan, read and rewritten where it lies (its stream and boundary are not
+// forwarded: nothing of it runs)
+MpdataBlockSel block_sel(const mpdata_plan* p, int64_t sl0, int64_t n) {
+  MpdataBlockSel b;
+  b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
+  b.W = p->inner ? p->W : 1; b.nz = p->nz;
+  return b;
+}
+const mpdata_plan* wm_plan(const mpdata_plan* p) { return p->inner ? p->inner : p; }
+// the state a call on the plan's velocities needs: filled once, and the arrays asked for still held
+int plan_uw_state(const char* what, const mpdata_plan* p, bool need_u, bool need_w) {
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
+  if ((need_u && !p->have_u) || (need_w && !p->have_w))
+    return set_err(MPDATA_ESTATE, "%s: the plan does not hold %s (mpdata_plan_run_uw used them up: import u and w)", what,
+                   (need_u && !p->have_u) ? "u" : "w");
+  return 0;
+}
 
 }  // namespace
 
@@ -828,13 +856,8 @@ static int plan_download_block(mpdata_plan* p, int64_t sl0, int64_t n, void* f, 
   DevGuard g(p->device);
   const size_t fb = f ? (size_t)n * (p->nx + 6) * (p->nz - 1) * p->ntracers * eb : 0;
   const size_t lb = flux ? (size_t)n * p->nz * p->ntracers * eb : 0;
-  if (p->bstage_bytes < fb + lb) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->bstage) (void)hipFree(p->bstage);
-    p->bstage = nullptr; p->bstage_bytes = 0;
-    HIP_TRY(hipMalloc(&p->bstage, fb + lb));
-    p->bstage_bytes = fb + lb;
-  }
+  rc = plan_bstage(p, fb + lb);
+  if (rc) return rc;
   void* df = f ? p->bstage : nullptr;
   void* dl = flux ? (char*)p->bstage + fb : nullptr;
   rc = plan_export_block(p, sl0, n, df, dl, 0, p->ntracers);
@@ -858,9 +881,8 @@ int mpdata_plan_download_instances_f32(mpdata_plan* p, int64_t sl0, int64_t n, f
 static int plan_level_stats(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int first, int count) {
   if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
     MpdataStatsJob b;
-    b.j = wm_job(p->inner ? p->inner : p, 0, nullptr, first, count);
-    b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
-    b.W = p->inner ? p->W : 1; b.nz = p->nz;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
     b.sum = sum; b.mn = mn; b.mx = mx;
     HIP_TRY(mpdata_stats_wm(b, p->stream));
   } else {
@@ -894,13 +916,8 @@ static int plan_level_stats_host(mpdata_plan* p, int64_t sl0, int64_t n, void* s
   void* host[3] = {sum, mn, mx};
   size_t need = 0;
   for (void* h : host) need += h ? one : 0;
-  if (p->bstage_bytes < need) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->bstage) (void)hipFree(p->bstage);
-    p->bstage = nullptr; p->bstage_bytes = 0;
-    HIP_TRY(hipMalloc(&p->bstage, need));
-    p->bstage_bytes = need;
-  }
+  rc = plan_bstage(p, need);
+  if (rc) return rc;
   void* dev[3] = {nullptr, nullptr, nullptr};
   size_t off = 0;
   for (int i = 0; i < 3; ++i)
@@ -943,7 +960,7 @@ int mpdata_level_stats_f32_device(int64_t ncrms, int nx, int nz, int ntracers, c
 // windowed plan's inner plan is read where it lies.
 static int plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst) {
   if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
-    const mpdata_plan* q = p->inner ? p->inner : p;
+    const mpdata_plan* q = wm_plan(p);
     const MpdataLayoutJob jr = wm_job(q, 3, nullptr, 0, 1), ja = wm_job(q, 5, nullptr, 0, 1);
     MpdataCourantJob b;
     b.j = wm_job(q, 1, nullptr, 0, 1);
@@ -951,8 +968,7 @@ static int plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void
     b.rho = (const double*)jr.prv + jr.prv_col0 * jr.chunk;
     b.adz = (const double*)ja.prv + ja.prv_col0 * ja.chunk;
     b.kc_tile_stride = jr.prv_tile_stride;
-    b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
-    b.W = p->inner ? p->W : 1; b.nz = p->nz;
+    b.sel = block_sel(p, sl0, n);
     b.clev = clev; b.cinst = cinst;
     HIP_TRY(mpdata_courant_wm(b, p->stream));
   } else {
@@ -960,18 +976,11 @@ static int plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void
   }
   return 0;
 }
-static int plan_courant_state(const char* what, const mpdata_plan* p) {
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
-  if (!p->have_u || !p->have_w)
-    return set_err(MPDATA_ESTATE, "%s: the plan does not hold %s (mpdata_plan_run_uw used them up: import u and w)", what,
-                   !p->have_u ? "u" : "w");
-  return 0;
-}
 int mpdata_plan_courant_device(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst) {
   int rc = block_range("mpdata_plan_courant_device", p, sl0, n);
   if (rc) return rc;
   if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_plan_courant_device: clev and cinst are both NULL");
-  rc = plan_courant_state("mpdata_plan_courant_device", p);
+  rc = plan_uw_state("mpdata_plan_courant_device", p, true, true);
   if (rc) return rc;
   DevGuard g(p->device);
   return plan_courant(p, sl0, n, clev, cinst);
@@ -983,17 +992,12 @@ static int plan_courant_host(mpdata_plan* p, int64_t sl0, int64_t n, void* clev,
   if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_plan_courant: clev and cinst are both NULL");
   rc = plan_check(p, eb);
   if (rc) return rc;
-  rc = plan_courant_state("mpdata_plan_courant", p);
+  rc = plan_uw_state("mpdata_plan_courant", p, true, true);
   if (rc) return rc;
   DevGuard g(p->device);
   const size_t lb = clev ? (size_t)n * (p->nz - 1) * eb : 0, ib = cinst ? (size_t)n * eb : 0;
-  if (p->bstage_bytes < lb + ib) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->bstage) (void)hipFree(p->bstage);
-    p->bstage = nullptr; p->bstage_bytes = 0;
-    HIP_TRY(hipMalloc(&p->bstage, lb + ib));
-    p->bstage_bytes = lb + ib;
-  }
+  rc = plan_bstage(p, lb + ib);
+  if (rc) return rc;
   void* dl = clev ? p->bstage : nullptr;
   void* di = cinst ? (char*)p->bstage + lb : nullptr;
   rc = plan_courant(p, sl0, n, dl, di);
@@ -1041,9 +1045,8 @@ static int plan_level_add(mpdata_plan* p, int64_t sl0, int64_t n, const void* d,
   const int clip = mode == MPDATA_LEVEL_ADD_CLIP;
   if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
     MpdataLevelAddJob b;
-    b.j = wm_job(p->inner ? p->inner : p, 0, nullptr, first, count);
-    b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
-    b.W = p->inner ? p->W : 1; b.nz = p->nz;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
     b.d = d; b.clip = clip;
     HIP_TRY(mpdata_level_add_wm(b, p->stream));
   } else {
@@ -1081,13 +1084,8 @@ static int plan_level_add_host(mpdata_plan* p, int64_t sl0, int64_t n, const voi
   if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_add before upload / import");
   DevGuard g(p->device);
   const size_t need = (size_t)n * (p->nz - 1) * p->ntracers * eb;
-  if (p->bstage_bytes < need) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->bstage) (void)hipFree(p->bstage);
-    p->bstage = nullptr; p->bstage_bytes = 0;
-    HIP_TRY(hipMalloc(&p->bstage, need));
-    p->bstage_bytes = need;
-  }
+  rc = plan_bstage(p, need);
+  if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(p->bstage, d, need, hipMemcpyHostToDevice, p->stream));
   rc = plan_level_add(p, sl0, n, p->bstage, mode, 0, p->ntracers);
   if (rc) return rc;
@@ -1125,10 +1123,9 @@ int mpdata_level_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, flo
 // plan's last instance inside the kernel (mpdata_scale_uw.h).  A windowed plan's inner plan is rewritten where it lies.
 static int plan_scale_uw(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw) {
   if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
-    const mpdata_plan* q = p->inner ? p->inner : p;
+    const mpdata_plan* q = wm_plan(p);
     MpdataScaleUwJob b;
-    b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
-    b.W = p->inner ? p->W : 1;
+    b.sel = block_sel(p, sl0, n);
     if (su) { b.j = wm_job(q, 1, nullptr, 0, 1); b.s = su; HIP_TRY(mpdata_scale_uw_wm(b, p->stream)); }
     if (sw) { b.j = wm_job(q, 2, nullptr, 0, 1); b.s = sw; HIP_TRY(mpdata_scale_uw_wm(b, p->stream)); }
   } else {
@@ -1137,19 +1134,11 @@ static int plan_scale_uw(mpdata_plan* p, int64_t sl0, int64_t n, const void* su,
   }
   return 0;
 }
-// (the wording of plan_courant_state; only the arrays asked for are tested)
-static int plan_scale_uw_state(const char* what, const mpdata_plan* p, bool u, bool w) {
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
-  if ((u && !p->have_u) || (w && !p->have_w))
-    return set_err(MPDATA_ESTATE, "%s: the plan does not hold %s (mpdata_plan_run_uw used them up: import u and w)", what,
-                   (u && !p->have_u) ? "u" : "w");
-  return 0;
-}
 int mpdata_plan_scale_uw_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw) {
   int rc = block_range("mpdata_plan_scale_uw_device", p, sl0, n);
   if (rc) return rc;
   if (!su && !sw) return set_err(MPDATA_EINVAL, "mpdata_plan_scale_uw_device: su and sw are both NULL");
-  rc = plan_scale_uw_state("mpdata_plan_scale_uw_device", p, su != nullptr, sw != nullptr);
+  rc = plan_uw_state("mpdata_plan_scale_uw_device", p, su != nullptr, sw != nullptr);
   if (rc) return rc;
   DevGuard g(p->device);
   return plan_scale_uw(p, sl0, n, su, sw);
@@ -1161,17 +1150,12 @@ static int plan_scale_uw_host(mpdata_plan* p, int64_t sl0, int64_t n, const void
   if (!su && !sw) return set_err(MPDATA_EINVAL, "mpdata_plan_scale_uw: su and sw are both NULL");
   rc = plan_check(p, eb);
   if (rc) return rc;
-  rc = plan_scale_uw_state("mpdata_plan_scale_uw", p, su != nullptr, sw != nullptr);
+  rc = plan_uw_state("mpdata_plan_scale_uw", p, su != nullptr, sw != nullptr);
   if (rc) return rc;
   DevGuard g(p->device);
   const size_t one = (size_t)n * eb, need = 2 * one;
-  if (p->bstage_bytes < need) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->bstage) (void)hipFree(p->bstage);
-    p->bstage = nullptr; p->bstage_bytes = 0;
-    HIP_TRY(hipMalloc(&p->bstage, need));
-    p->bstage_bytes = need;
-  }
+  rc = plan_bstage(p, need);
+  if (rc) return rc;
   void* du = su ? p->bstage : nullptr;
   void* dw = sw ? (char*)p->bstage + one : nullptr;
   if (su) HIP_TRY(hipMemcpyAsync(du, su, one, hipMemcpyHostToDevice, p->stream));

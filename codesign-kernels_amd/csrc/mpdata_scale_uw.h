@@ -7,26 +7,20 @@
 #define MPDATA_SCALE_UW_H
 #include <hip/hip_runtime.h>
 
-#include "mpdata_layout.h"
+#include "mpdata_wm_walk.h"
 
 // Plan layout.  j: the plan side of the array exactly as wm_job(which = 1 or 2) makes it (strides in 8-byte elements;
 // j.ref is not used).  The kernel needs the storage layout only: element e = s * nlev + kk of column slot c of a tile,
 // split into whole 128-byte lines and a rest (mpdata_layout.h); it walks the column slots the array stores,
 // c = j.prv_col0 .. j.prv_col0 + j.ncols - 1.
-//   ipe: reals per 8-byte element -- 1 (fp64), 2 (fp32 plans: pairs of adjacent instances)
-//   sl0, n, ncrms: the block and the plan's size in REAL instances.  A slot that is no instance of the block -- the
-//     padding of the last tile, a neighbour in the tile, the partner of a pair the block's ends split -- keeps its bits
-//     (the partner half of a split pair is stored back as it was loaded).  The one exception: with ipe = 2 and an odd
-//     number of slots in use the slot behind the last one is the PHANTOM (include/mpdata_hip.h 3f); it takes the factor
-//     of the last instance whenever the block holds that instance, and so stays its copy.
-//   W = 1: j describes the plan itself.
-//   W > 1: j describes the INNER plan of a windowed plan (mpdata_windows.h): slot q = sl * W + h is window h of
-//     instance sl; every window, and every level it stores (owned or not), takes the factor of its instance.
+//   sel: the block (mpdata_wm_walk.h; the launcher checks sel.nz with the rest, the kernel does not look at it).  A
+//     slot that is no instance of the block keeps its bits (the partner half of a split pair is stored back as it was
+//     loaded).  The one exception is the PHANTOM of an odd fp32 plan (include/mpdata_hip.h 3f): it takes the factor of the
+//     last instance whenever the block holds that instance, and so stays its copy.  Every window of a windowed plan,
+//     and every level it stores (owned or not), takes the factor of its instance.
 struct MpdataScaleUwJob {
   MpdataLayoutJob j;
-  long long sl0, n, ncrms;
-  int ipe;
-  int W;
+  MpdataBlockSel sel;
   const void* s;
 };
 // the grid covers the tiles the block touches

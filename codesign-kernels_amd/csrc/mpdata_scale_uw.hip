@@ -2,12 +2,8 @@
 // mpdata_scale_uw.h): a(sl, :, :) = a(sl, :, :) * s(sl - sl0) -- what a subcycled step needs (SAM's kurant: ncycle from
 // the Courant number, then ncycle advections on u / ncycle, w / ncycle), the write side of mpdata_courant.hip.  A kernel
 // of its own outside the run: nothing is fused into the plan kernels.
-//   plan layout: a column chunk of a tile is contiguous ([tile][column][instance][level], the whole 128-byte lines of
-//     every column first, the rests behind them), so a wave that owns 64 elements of a chunk and walks the column slots
-//     the array stores reads and writes it once as a linear stream -- 512 bytes per wave and column, eight columns in
-//     flight -- with its factor in a register.  The kernel knows the storage layout only: LPS 8 .. 64, the
-//     one-instance-per-tile forms above 64 levels (several 64-element slices per tile) and the windows of tall plans are
-//     the same code with other constants.
+//   plan layout: the walk of mpdata_wm_walk.h over the column slots the array stores reads and writes it once as a
+//     linear stream -- 512 bytes per wave and column, eight columns in flight -- with its factor in a register.
 //   reference layout: one thread per instance, coalesced along sl, the loop over the columns.
 // Built with -ffp-contract=off and IEEE NaN handling; every result is one rounded multiply, nothing here adds.
 #include <hip/hip_runtime.h>
@@ -17,24 +13,7 @@
 
 namespace {
 
-constexpr int NB = 8;   // columns in flight per lane
-
-template <typename R2> struct Elem;
-template <> struct Elem<double> {
-  typedef double R;
-  static constexpr int N = 1;
-  __device__ static double& at(double& v, int) { return v; }
-};
-template <> struct Elem<float2> {
-  typedef float R;
-  static constexpr int N = 2;
-  __device__ static float& at(float2& v, int h) { return h ? v.y : v.x; }
-};
-template <> struct Elem<float> {
-  typedef float R;
-  static constexpr int N = 1;
-  __device__ static float& at(float& v, int) { return v; }
-};
+using namespace wm_walk;
 
 // ncol elements p[0], p[step], ... of a lane := element * fv: all NB loads of a batch are issued before the first
 // store (the index is clamped, not predicated: a conditional load would be waited for on its own; the clamped
@@ -90,17 +69,17 @@ __global__ void __launch_bounds__(256) wm_scale_uw_kernel(const MpdataScaleUwJob
   R2* p = static_cast<R2*>(j.prv) + tile * j.prv_tile_stride +
           (in_main ? e : (long long)j.ncol_p * j.main_e + (e - j.main_e)) + j.prv_col0 * cstep;   // the array's first column
   // the factor of every half: the instance the slot stands for
-  const long long nslots = b.ncrms * b.W;   // slots that are an instance (a window of one)
+  const long long nslots = b.sel.ncrms * b.sel.W;   // slots that are an instance (a window of one)
   R fv[E::N];
   bool on[E::N];
 #pragma unroll
   for (int h = 0; h < E::N; ++h) {
     long long q = (tile * j.slp + s) * E::N + h;
     if (E::N == 2 && (nslots & 1) && q == nslots) q = nslots - 1;   // the phantom half follows the plan's last slot
-    const long long sl = b.W > 1 ? q / b.W : q;
-    const bool ok = act && sl >= b.sl0 && sl < b.sl0 + b.n;   // else: padding, the partner of a split pair, a neighbour in the tile
+    const long long sl = b.sel.W > 1 ? q / b.sel.W : q;
+    const bool ok = act && sl >= b.sel.sl0 && sl < b.sel.sl0 + b.sel.n;   // else: padding, the partner of a split pair, a neighbour in the tile
     on[h] = ok;
-    fv[h] = ok ? static_cast<const R*>(b.s)[sl - b.sl0] : (R)1;
+    fv[h] = ok ? static_cast<const R*>(b.s)[sl - b.sel.sl0] : (R)1;
   }
   bool any = false;
 #pragma unroll
@@ -124,31 +103,17 @@ __global__ void __launch_bounds__(256) ref_scale_uw_kernel(R* a, const long long
 }  // namespace
 
 hipError_t mpdata_scale_uw_wm(const MpdataScaleUwJob& b, hipStream_t stream) {
-  const MpdataLayoutJob& j = b.j;
-  if (!j.prv || !b.s || j.nlev < 1 || j.slp < 1 || j.ntiles < 1 || j.ncols < 1 || j.prv_col0 < 0 || j.prv_col0 + j.ncols > j.ncol_p ||
-      j.chunk != (long long)j.slp * j.nlev || j.main_e < 0 || j.main_e > j.chunk || j.prv_tile_stride < (long long)j.ncol_p * j.chunk ||
-      (b.ipe != 1 && b.ipe != 2) || b.W < 1)
-    return hipErrorInvalidValue;
-  if (b.sl0 < 0 || b.n < 1 || b.sl0 + b.n > b.ncrms) return hipErrorInvalidValue;
-  const long long spt = (long long)j.slp * b.ipe;   // slots per tile
-  if (b.ncrms * b.W > (long long)j.ntiles * spt) return hipErrorInvalidValue;
-  // (the phantom shares its 8-byte element, hence its tile, with the last slot)
-  const long long t0 = b.sl0 * b.W / spt, t1 = ((b.sl0 + b.n) * b.W - 1) / spt;
-  const int nslice = (int)((j.chunk + 63) / 64);
-  const long long waves = (t1 - t0 + 1) * nslice;
-  if (t1 >= j.ntiles || t1 - t0 + 1 > 2147483647LL || (waves + 3) / 4 > 2147483647LL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  if (b.ipe == 1) hipLaunchKernelGGL((wm_scale_uw_kernel<double>), grid, block, 0, stream, b, t0, (int)(t1 - t0 + 1), nslice);
-  else hipLaunchKernelGGL((wm_scale_uw_kernel<float2>), grid, block, 0, stream, b, t0, (int)(t1 - t0 + 1), nslice);
-  return hipGetLastError();
+  WmGrid g;
+  if (!b.s) return hipErrorInvalidValue;
+  const hipError_t e = wm_block_grid(b.j, b.sel, 1, &g);
+  return e != hipSuccess ? e : wm_block_launch(wm_scale_uw_kernel<double>, wm_scale_uw_kernel<float2>, b, g, stream);
 }
 
 hipError_t mpdata_scale_uw_ref(void* a, int elem_bytes, long long ld, long long sl0, long long n, int ncols, int nlevs,
                                const void* s, hipStream_t stream) {
   if (!a || !s || ld < 1 || sl0 < 0 || n < 1 || sl0 + n > ld || ncols < 1 || nlevs < 1) return hipErrorInvalidValue;
-  const long long gx = (n + 255) / 256;
-  if (gx > 2147483647LL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)gx, (unsigned)(nlevs < 65535 ? nlevs : 65535)), block(256);
+  dim3 grid, block(256);
+  if (ref_block_grid(n, nlevs, &grid) != hipSuccess) return hipErrorInvalidValue;
   if (elem_bytes == 8)
     hipLaunchKernelGGL((ref_scale_uw_kernel<double>), grid, block, 0, stream, static_cast<double*>(a), ld, sl0, n, ncols, (long long)nlevs,
                        static_cast<const double*>(s));

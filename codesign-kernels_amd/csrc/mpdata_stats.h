@@ -8,24 +8,17 @@
 #define MPDATA_STATS_H
 #include <hip/hip_runtime.h>
 
-#include "mpdata_layout.h"
+#include "mpdata_wm_walk.h"
 
 // Plan layout.  j: the plan side of f exactly as wm_job(which = 0) makes it for tracers [first, first + j.ntr) (j.prv on
 // the first of them, strides in 8-byte elements; j.ref is not used).  The kernel needs the storage layout only: element
 // e = s * nlev + kk of column slot c of a tile, split into whole 128-byte lines and a rest (mpdata_layout.h).
-//   ipe: reals per 8-byte element -- 1 (fp64), 2 (fp32 plans: pairs of adjacent instances)
-//   sl0, n, ncrms: the block and the plan's size in REAL instances.  Slots that are no instance of the block -- the
-//     padding of the last tile, the phantom half of an odd fp32 plan, the partner of a pair the block's ends split --
-//     reach no output.
-//   W = 1: j describes the plan itself, nz = j.nlev + 1.
-//   W > 1: j describes the INNER plan of a windowed plan (mpdata_windows.h): slot q = sl * W + h is window h of
-//     instance sl, nz the levels of the tall column; every window writes its OWNED levels to the tall level they
-//     stand for (owned levels are right after a run whatever the seams hold).
+//   sel: the block (mpdata_wm_walk.h).  Slots that are no instance of it reach no output; every window of a windowed
+//     plan writes its OWNED levels to the tall level they stand for (owned levels are right after a run whatever the
+//     seams hold).
 struct MpdataStatsJob {
   MpdataLayoutJob j;
-  long long sl0, n, ncrms;
-  int ipe;
-  int W, nz;
+  MpdataBlockSel sel;
   void *sum, *mn, *mx;
 };
 // the grid covers the tiles the block touches

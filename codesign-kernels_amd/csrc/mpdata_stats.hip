@@ -1,12 +1,9 @@
 // mpdata_stats.hip -- horizontal sum, minimum and maximum per level of f (include/mpdata_hip.h 3g, mpdata_stats.h):
 // a reduction over the interior columns 1 .. nx, a kernel of its own outside the run (nothing is fused into the plan
 // kernels, nothing is kept between calls, the result is a function of f alone).
-//   plan layout: a column chunk of a tile is contiguous ([tile][column][instance][level], the whole 128-byte lines of
-//     every column first, the rests behind them), so a wave that owns 64 elements of a chunk and walks the column
-//     slots 3 .. nx+2 reads f once as a linear stream -- 512 bytes per wave and column, eight columns in flight -- and
-//     keeps the three running values of every lane in registers.  The kernel knows the storage layout only: LPS 8 ..
-//     64, the one-instance-per-tile forms above 64 levels (several 64-element slices per tile) and the windows of tall
-//     plans are the same code with other constants.
+//   plan layout: the walk of mpdata_wm_walk.h over the column slots 3 .. nx+2 reads f once as a linear stream -- 512
+//     bytes per wave and column, eight columns in flight -- and keeps the three running values of every lane in
+//     registers.
 //   reference layout: one thread per instance, coalesced along sl, the loop over i.
 // Built with -ffp-contract=off; the sum is the sequential one of the definition (s = +0.0; s = s + f_i), and nothing
 // here multiplies.
@@ -14,33 +11,18 @@
 #include <cstdint>
 
 #include "mpdata_stats.h"
-#include "mpdata_windows.h"
 
 namespace {
 
-constexpr int NB = 8;   // columns in flight per lane
+using namespace wm_walk;
 
-template <typename R2> struct Elem;
-template <> struct Elem<double> {
-  typedef double R;
-  static constexpr int N = 1;
-  __device__ static double get(const double& v, int) { return v; }
+template <typename R> struct Real;
+template <> struct Real<double> {
   __device__ static double inf() { return __builtin_huge_val(); }
   __device__ static double lo(double a, double b) { return fmin(a, b); }
   __device__ static double hi(double a, double b) { return fmax(a, b); }
 };
-template <> struct Elem<float2> {
-  typedef float R;
-  static constexpr int N = 2;
-  __device__ static float get(const float2& v, int h) { return h ? v.y : v.x; }
-  __device__ static float inf() { return __builtin_huge_valf(); }
-  __device__ static float lo(float a, float b) { return fminf(a, b); }
-  __device__ static float hi(float a, float b) { return fmaxf(a, b); }
-};
-template <> struct Elem<float> {
-  typedef float R;
-  static constexpr int N = 1;
-  __device__ static float get(const float& v, int) { return v; }
+template <> struct Real<float> {
   __device__ static float inf() { return __builtin_huge_valf(); }
   __device__ static float lo(float a, float b) { return fminf(a, b); }
   __device__ static float hi(float a, float b) { return fmaxf(a, b); }
@@ -53,8 +35,9 @@ template <typename R2>
 __device__ inline void march(const R2* p, const long long step, const int nx, typename Elem<R2>::R (&s)[Elem<R2>::N],
                              typename Elem<R2>::R (&lo)[Elem<R2>::N], typename Elem<R2>::R (&hi)[Elem<R2>::N]) {
   typedef Elem<R2> E;
+  typedef Real<typename E::R> T;
 #pragma unroll
-  for (int h = 0; h < E::N; ++h) { s[h] = 0; lo[h] = E::inf(); hi[h] = -E::inf(); }
+  for (int h = 0; h < E::N; ++h) { s[h] = 0; lo[h] = T::inf(); hi[h] = -T::inf(); }
   for (int i = 0; i < nx; i += NB) {
     R2 v[NB];
 #pragma unroll
@@ -66,8 +49,8 @@ __device__ inline void march(const R2* p, const long long step, const int nx, ty
         for (int h = 0; h < E::N; ++h) {
           const typename E::R x = E::get(v[u], h);
           s[h] = s[h] + x;
-          lo[h] = E::lo(lo[h], x);
-          hi[h] = E::hi(hi[h], x);
+          lo[h] = T::lo(lo[h], x);
+          hi[h] = T::hi(hi[h], x);
         }
       }
     }
@@ -100,21 +83,21 @@ __global__ void __launch_bounds__(256) wm_level_stats_kernel(const MpdataStatsJo
   R acc[E::N], lo[E::N], hi[E::N];
   march<R2>(p, cstep, nx, acc, lo, hi);
   if (!act) return;
-  const int nlev_out = b.nz - 1;
+  const int nlev_out = b.sel.nz - 1;
 #pragma unroll
   for (int h = 0; h < E::N; ++h) {
     const long long q = (tile * j.slp + s) * E::N + h;   // slot: instance, or pseudo-instance of a windowed plan
     long long sl = q;
     int k = kk;
-    if (b.W > 1) {
-      sl = q / b.W;
+    if (b.sel.W > 1) {
+      sl = q / b.sel.W;
       int k0, nz_w, own0, own1;
-      if (mpd_level_window(b.nz, (int)(q - sl * b.W), &k0, &nz_w, &own0, &own1) != b.W) continue;
+      if (mpd_level_window(b.sel.nz, (int)(q - sl * b.sel.W), &k0, &nz_w, &own0, &own1) != b.sel.W) continue;
       k = k0 + kk;
       if (k + 1 < own0 || k + 1 > own1) continue;
     }
-    if (sl < b.sl0 || sl >= b.sl0 + b.n) continue;   // padding, phantom, the partner of a split pair, a neighbour in the tile
-    const long long o = (sl - b.sl0) + b.n * (k + (long long)nlev_out * tr);
+    if (sl < b.sel.sl0 || sl >= b.sel.sl0 + b.sel.n) continue;   // padding, phantom, the partner of a split pair, a neighbour in the tile
+    const long long o = (sl - b.sel.sl0) + b.sel.n * (k + (long long)nlev_out * tr);
     if (b.sum) static_cast<R*>(b.sum)[o] = acc[h];
     if (b.mn) static_cast<R*>(b.mn)[o] = lo[h];
     if (b.mx) static_cast<R*>(b.mx)[o] = hi[h];
@@ -126,7 +109,6 @@ __global__ void __launch_bounds__(256) wm_level_stats_kernel(const MpdataStatsJo
 template <typename R>
 __global__ void __launch_bounds__(256) ref_level_stats_kernel(const R* f, const long long ld, const long long sl0, const long long n,
                                                              const int nx, const long long rows, R* sum, R* mn, R* mx) {
-  typedef Elem<R> E;
   const long long bi = (long long)blockIdx.x * 256 + threadIdx.x;
   if (bi >= n) return;
   for (long long r = blockIdx.y; r < rows; r += gridDim.y) {
@@ -142,30 +124,18 @@ __global__ void __launch_bounds__(256) ref_level_stats_kernel(const R* f, const 
 }  // namespace
 
 hipError_t mpdata_stats_wm(const MpdataStatsJob& b, hipStream_t stream) {
-  const MpdataLayoutJob& j = b.j;
-  if (!j.prv || j.ntr < 1 || j.nlev < 1 || j.slp < 1 || j.ntiles < 1 || j.ncol_p < 7 || j.chunk != (long long)j.slp * j.nlev ||
-      j.main_e < 0 || j.main_e > j.chunk || (b.ipe != 1 && b.ipe != 2) || b.W < 1 || (!b.sum && !b.mn && !b.mx))
-    return hipErrorInvalidValue;
-  if (b.sl0 < 0 || b.n < 1 || b.sl0 + b.n > b.ncrms) return hipErrorInvalidValue;
-  const long long spt = (long long)j.slp * b.ipe;   // slots per tile
-  if (b.ncrms * b.W > (long long)j.ntiles * spt) return hipErrorInvalidValue;
-  if (b.W == 1 ? b.nz != j.nlev + 1 : (j.slp != 1 || b.nz <= j.nlev + 1)) return hipErrorInvalidValue;
-  const long long t0 = b.sl0 * b.W / spt, t1 = ((b.sl0 + b.n) * b.W - 1) / spt;
-  const int nslice = (int)((j.chunk + 63) / 64);
-  const long long waves = (long long)j.ntr * (t1 - t0 + 1) * nslice;
-  if (t1 - t0 + 1 > 2147483647LL || (waves + 3) / 4 > 2147483647LL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  if (b.ipe == 1) hipLaunchKernelGGL((wm_level_stats_kernel<double>), grid, block, 0, stream, b, t0, (int)(t1 - t0 + 1), nslice);
-  else hipLaunchKernelGGL((wm_level_stats_kernel<float2>), grid, block, 0, stream, b, t0, (int)(t1 - t0 + 1), nslice);
-  return hipGetLastError();
+  WmGrid g;
+  if (!b.sum && !b.mn && !b.mx) return hipErrorInvalidValue;
+  const hipError_t e = wm_block_grid(b.j, b.sel, b.j.ntr, &g);
+  return e != hipSuccess ? e : wm_block_launch(wm_level_stats_kernel<double>, wm_level_stats_kernel<float2>, b, g, stream);
 }
 
 hipError_t mpdata_stats_ref(const void* f, int elem_bytes, long long ld, long long sl0, long long n, int nx, int nlev, int ntr,
                             void* sum, void* mn, void* mx, hipStream_t stream) {
   if (!f || ld < 1 || sl0 < 0 || n < 1 || sl0 + n > ld || nx < 1 || nlev < 1 || ntr < 1 || (!sum && !mn && !mx)) return hipErrorInvalidValue;
-  const long long rows = (long long)nlev * ntr, gx = (n + 255) / 256;
-  if (gx > 2147483647LL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)gx, (unsigned)(rows < 65535 ? rows : 65535)), block(256);
+  const long long rows = (long long)nlev * ntr;
+  dim3 grid, block(256);
+  if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
   if (elem_bytes == 8)
     hipLaunchKernelGGL((ref_level_stats_kernel<double>), grid, block, 0, stream, static_cast<const double*>(f), ld, sl0, n, nx, rows,
                        static_cast<double*>(sum), static_cast<double*>(mn), static_cast<double*>(mx));
