@@ -123,6 +123,14 @@ def lib():
         for name in ("mpdata_scale_uw_device", "mpdata_scale_uw_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, dp, dp, dp, dp, vp]
+        L.mpdata_plan_column_path_device.restype = ci
+        L.mpdata_plan_column_path_device.argtypes = [vp, i64, i64, vp, vp, ci, ci]
+        for name in ("mpdata_plan_column_path", "mpdata_plan_column_path_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp]
+        for name in ("mpdata_column_path_device", "mpdata_column_path_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, dp, dp, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -743,6 +751,40 @@ class Plan:
                 raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {(n,)}")
         _check(getattr(lib(), "mpdata_plan_scale_uw" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def column_path(self, path, mass=None, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """Mass-weighted column integrals of f (include/mpdata_hip.h 3k): path(sl, i, t) = the sequential sum over k of
+        (rho(sl,k) * adz(sl,k)) * f(sl,i,k,t) on the interior columns 1 .. nx, and mass(sl, t) = the sequential sum of path over
+        i, instances [sl0, sl0+n) (default: the rest of the plan from sl0) -> reference-layout DEVICE tensors of the plan's
+        precision, on the plan's stream (mpdata_plan_column_path_device).  Shapes: column_path_shapes(n, nx, ntr) -- path
+        ([ntr,] nx, n), mass ([ntr,] n) or None (skipped).  The tracers are first_tracer .. +ntr-1, ntr = ntracers, or the
+        leading axis of a 3-d path (else 1).  Changes nothing of the plan."""
+        n = self._block_n(sl0, n)
+        nx = self.dims[1]
+        lead = path.dim() == 3
+        ntr = int(ntracers) if ntracers is not None else (int(path.shape[0]) if lead else 1)
+        sh = column_path_shapes(n, nx, ntr if (lead or ntr != 1) else None)
+        pp = _dev_ptr(path, sh["path"], "path", self._tdt())
+        pm = None if mass is None else _dev_ptr(mass, sh["mass"], "mass", self._tdt())
+        _check(lib().mpdata_plan_column_path_device(self._p, int(sl0), n, pp, pm, int(first_tracer), ntr))
+
+    def column_path_host(self, path, mass=None, sl0=0, n=None):
+        """The same for all tracers into HOST arrays (numpy, Fortran order): path (n, nx[, ntracers]), mass (n[, ntracers]) or
+        None, synchronous (mpdata_plan_column_path[_f32])."""
+        n = self._block_n(sl0, n)
+        nx, nt = self.dims[1], self.dims[3]
+        ptrs = []
+        for name, a, want in (("path", path, (n, nx)), ("mass", mass, (n,))):
+            if a is None:
+                if name == "path":
+                    raise MpdataError(-1, "column_path_host: path is None")
+                ptrs.append(None)
+                continue
+            ptrs.append(_host_ptr(a, name, True, self._dt))
+            full = want + ((nt,) if nt > 1 else ())
+            if tuple(a.shape) != full and not (nt == 1 and tuple(a.shape) == want + (1,)):
+                raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {full}")
+        _check(getattr(lib(), "mpdata_plan_column_path" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -828,6 +870,36 @@ def level_stats(f, sum=None, min=None, max=None, stream=None):
         raise MpdataError(-1, "level_stats: sum, min and max are all None")
     fn = lib().mpdata_level_stats_device if f.dtype == torch.float64 else lib().mpdata_level_stats_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, *ptrs, _stream_handle(stream)))
+
+
+def column_path_shapes(n, nx, ntracers=None):
+    """Torch shapes (reversed-axes view of the reference layout) of the outputs of a column_path call on n instances:
+    path ([ntracers,] nx, n), mass ([ntracers,] n); ntracers None: one tracer without the leading axis."""
+    lead = () if ntracers is None else (int(ntracers),)
+    return {"path": lead + (int(nx), int(n)), "mass": lead + (int(n),)}
+
+
+def column_path(f, rho, adz, path, mass=None, stream=None):
+    """Mass-weighted column integrals (include/mpdata_hip.h 3k) of a reference-layout DEVICE tensor f ([ntr,] nzm, nx+6,
+    ncrms) with rho, adz (nzm, ncrms), float64 or float32, into device tensors path ([ntr,] nx, ncrms) and mass ([ntr,]
+    ncrms) of the same dtype (column_path_shapes; mass None: skipped), asynchronous on `stream` (mpdata_column_path_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"column_path: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    if path is None:
+        raise MpdataError(-1, "column_path: path is None")
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    pr = _dev_ptr(rho, (nzm, ncrms), "rho", f.dtype)
+    pa = _dev_ptr(adz, (nzm, ncrms), "adz", f.dtype)
+    sh = column_path_shapes(ncrms, nxp6 - 6, nt if f.dim() == 4 else None)
+    pp = _dev_ptr(path, sh["path"], "path", f.dtype)
+    pm = None if mass is None else _dev_ptr(mass, sh["mass"], "mass", f.dtype)
+    fn = lib().mpdata_column_path_device if f.dtype == torch.float64 else lib().mpdata_column_path_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, pr, pa, pp, pm, _stream_handle(stream)))
 
 
 def level_add(f, d, mode=LEVEL_ADD, stream=None):

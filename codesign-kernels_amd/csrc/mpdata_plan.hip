@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "mpdata_courant.h"
+#include "mpdata_column_path.h"
 #include "mpdata_internal.h"
 #include "mpdata_level_add.h"
 #include "mpdata_scale_uw.h"
@@ -1188,6 +1189,86 @@ int mpdata_scale_uw_device(int64_t ncrms, int nx, int nz, double* u, double* w, 
 }
 int mpdata_scale_uw_f32_device(int64_t ncrms, int nx, int nz, float* u, float* w, const float* su, const float* sw, void* stream) {
   return scale_uw_array(ncrms, nx, nz, u, w, su, sw, stream, 4);
+}
+
+// ---- 3k: mass-weighted column integrals of f per interior column (path) and their sum over the columns (mass).  Reads f,
+// rho, adz, writes the outputs: as the level statistics no flag of the plan is touched (halo columns are not read, owned
+// levels are right whatever the seams hold), no event is recorded, and a windowed plan's inner plan is read where it
+// lies.  The velocities are not looked at: the plan need not hold any.
+static int plan_column_path(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int first, int count) {
+  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
+    const mpdata_plan* q = wm_plan(p);
+    const MpdataLayoutJob jr = wm_job(q, 3, nullptr, 0, 1), ja = wm_job(q, 5, nullptr, 0, 1);
+    MpdataColumnPathJob b;
+    b.j = wm_job(q, 0, nullptr, first, count);
+    b.rho = (const double*)jr.prv + jr.prv_col0 * jr.chunk;
+    b.adz = (const double*)ja.prv + ja.prv_col0 * ja.chunk;
+    b.kc_tile_stride = jr.prv_tile_stride;
+    b.sel = block_sel(p, sl0, n);
+    b.path = path; b.mass = mass;
+    HIP_TRY(mpdata_column_path_wm(b, p->stream));
+  } else {
+    const size_t f1 = p->sz.f / p->ntracers;
+    HIP_TRY(mpdata_column_path_ref((const char*)p->f + (size_t)first * f1 * p->eb, p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx,
+                                   p->nz - 1, count, path, mass, p->stream));
+  }
+  return 0;
+}
+int mpdata_plan_column_path_device(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int first_tracer, int ntracers) {
+  int rc = block_range("mpdata_plan_column_path_device", p, sl0, n);
+  if (rc) return rc;
+  rc = tracer_range(p, first_tracer, ntracers);
+  if (rc) return rc;
+  if (!path) return set_err(MPDATA_EINVAL, "mpdata_plan_column_path_device: null path");
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_column_path_device before upload / import");
+  DevGuard g(p->device);
+  return plan_column_path(p, sl0, n, path, mass, first_tracer, ntracers);
+}
+// host arrays, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
+static int plan_column_path_host(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int eb) {
+  int rc = block_range("mpdata_plan_column_path", p, sl0, n);
+  if (rc) return rc;
+  if (!path) return set_err(MPDATA_EINVAL, "mpdata_plan_column_path: null path");
+  rc = plan_check(p, eb);
+  if (rc) return rc;
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_column_path before upload / import");
+  DevGuard g(p->device);
+  const size_t pb = (size_t)n * p->nx * p->ntracers * eb, mb = mass ? (size_t)n * p->ntracers * eb : 0;
+  rc = plan_bstage(p, pb + mb);
+  if (rc) return rc;
+  void* dp = p->bstage;
+  void* dm = mass ? (char*)p->bstage + pb : nullptr;
+  rc = plan_column_path(p, sl0, n, dp, dm, 0, p->ntracers);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(path, dp, pb, hipMemcpyDeviceToHost, p->stream));
+  if (mass) HIP_TRY(hipMemcpyAsync(mass, dm, mb, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+int mpdata_plan_column_path(mpdata_plan* p, int64_t sl0, int64_t n, double* path, double* mass) {
+  return plan_column_path_host(p, sl0, n, path, mass, 8);
+}
+int mpdata_plan_column_path_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* path, float* mass) {
+  return plan_column_path_host(p, sl0, n, path, mass, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call)
+static int column_path_array(int64_t ncrms, int nx, int nz, int ntracers, const void* f, const void* rho, const void* adz, void* path,
+                             void* mass, void* stream, int eb) {
+  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
+    return set_err(MPDATA_EINVAL, "mpdata_column_path_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
+                   (long long)ncrms, nx, nz, ntracers);
+  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_column_path_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
+  if (!path) return set_err(MPDATA_EINVAL, "mpdata_column_path_device: null path");
+  HIP_TRY(mpdata_column_path_ref(f, rho, adz, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, path, mass, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_column_path_device(int64_t ncrms, int nx, int nz, int ntracers, const double* f, const double* rho, const double* adz,
+                              double* path, double* mass, void* stream) {
+  return column_path_array(ncrms, nx, nz, ntracers, f, rho, adz, path, mass, stream, 8);
+}
+int mpdata_column_path_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, const float* rho, const float* adz,
+                                  float* path, float* mass, void* stream) {
+  return column_path_array(ncrms, nx, nz, ntracers, f, rho, adz, path, mass, stream, 4);
 }
 
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)

@@ -38,6 +38,8 @@ module mpdata_hip_mod
   integer(c_int), parameter, public :: MPDATA_LEVEL_ADD = 0, MPDATA_LEVEL_ADD_CLIP = 1
   ! one factor per instance on a resident plan's u and w, in place (include/mpdata_hip.h section 3j)
   public :: mpdata_plan_scale_uw_device_c, mpdata_plan_scale_uw_c, mpdata_scale_uw_device_c
+  ! mass-weighted column integrals of a resident plan's tracers (include/mpdata_hip.h section 3k)
+  public :: mpdata_plan_column_path_device_c, mpdata_plan_column_path_c, mpdata_column_path_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -53,6 +55,8 @@ module mpdata_hip_mod
 #define MPDATA_C_LEVEL_ADD_DEVICE "mpdata_level_add_f32_device"
 #define MPDATA_C_PLAN_SCALE_UW "mpdata_plan_scale_uw_f32"
 #define MPDATA_C_SCALE_UW_DEVICE "mpdata_scale_uw_f32_device"
+#define MPDATA_C_PLAN_COLUMN_PATH "mpdata_plan_column_path_f32"
+#define MPDATA_C_COLUMN_PATH_DEVICE "mpdata_column_path_f32_device"
 #else
 #define MPDATA_C_ADVECT "mpdata_advect_scalar2d"
 #define MPDATA_C_PLAN_CREATE "mpdata_plan_create"
@@ -66,6 +70,8 @@ module mpdata_hip_mod
 #define MPDATA_C_LEVEL_ADD_DEVICE "mpdata_level_add_device"
 #define MPDATA_C_PLAN_SCALE_UW "mpdata_plan_scale_uw"
 #define MPDATA_C_SCALE_UW_DEVICE "mpdata_scale_uw_device"
+#define MPDATA_C_PLAN_COLUMN_PATH "mpdata_plan_column_path"
+#define MPDATA_C_COLUMN_PATH_DEVICE "mpdata_column_path_device"
 #endif
 
   interface
@@ -319,6 +325,33 @@ module mpdata_hip_mod
       integer(c_int64_t), value :: ncrms
       integer(c_int), value :: nx, nz
       type(c_ptr), value :: u, w, su, sw
+      type(c_ptr), value :: stream
+    end function
+    ! ---- mass-weighted column integrals (include/mpdata_hip.h section 3k): path(n, nx [, ntracers]) = the sequential sum
+    ! over k of (rho * adz) * f on the interior columns, mass(n [, ntracers]) = its sequential sum over i (c_null_ptr: skipped)
+    ! device arrays of the plan's precision, asynchronous on the plan's stream:
+    integer(c_int) function mpdata_plan_column_path_device_c(plan, sl0, n, path, mass, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_column_path_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: path, mass
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! host arrays, all tracers (c_loc of an array of the module's precision; mass may be c_null_ptr), synchronous
+    integer(c_int) function mpdata_plan_column_path_c(plan, sl0, n, path, mass) bind(C, name=MPDATA_C_PLAN_COLUMN_PATH)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: path, mass
+    end function
+    ! the same on reference-layout device arrays f, rho(ncrms,nzm), adz(ncrms,nzm)
+    integer(c_int) function mpdata_column_path_device_c(ncrms, nx, nz, ntracers, f, rho, adz, path, mass, stream) &
+        bind(C, name=MPDATA_C_COLUMN_PATH_DEVICE)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      type(c_ptr), value :: f, rho, adz, path, mass
       type(c_ptr), value :: stream
     end function
   end interface

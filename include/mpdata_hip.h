@@ -473,6 +473,51 @@ int mpdata_plan_scale_uw_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const fl
 int mpdata_scale_uw_device(int64_t ncrms, int nx, int nz, double* u, double* w, const double* su, const double* sw, void* stream);
 int mpdata_scale_uw_f32_device(int64_t ncrms, int nx, int nz, float* u, float* w, const float* su, const float* sw, void* stream);
 
+/* ---- 3k. Mass-weighted column integrals of a resident plan's tracers (what a host model takes from its CRMs along the
+ * column: SAM's precipitable water, its cloud and ice water paths, and, summed over x, the mass a conservation check looks
+ * at).  3g - 3j reduce or broadcast along x; this call reduces along the levels.  For instance sl in [sl0, sl0 + n),
+ * interior column i = 1 .. nx and tracer t in [first_tracer, first_tracer + ntracers), in the plan's precision:
+ *   wgt(sl,k)    = rho(sl,k) * adz(sl,k)                                      one rounded multiply
+ *   path(sl,i,t) : s = +0.0; do k = 1, nzm:  s = s + wgt(sl,k) * f(sl,i,k,t)   the product rounded, then the add; no fma
+ *   mass(sl,t)   : s = +0.0; do i = 1, nx:   s = s + path(sl,i,t)
+ * Every operation is rounded once, in exactly this order and association and without contraction, so EXACT and FAST
+ * plans give the same bits.  Multiplying by dz or dividing by nx is the caller's scalar.  NaN and infinities are outside
+ * the contract; the sign of a zero result is whatever this sequence gives.
+ *   path   reference layout (n, nx [, ntracers]), instance index fastest, leading dimension n, tightly packed, tracer
+ *          slowest; interior columns only.  Required.
+ *   mass   (n [, ntracers]); NULL: skipped.  Formed from path by a second kernel on the same stream.
+ * No byte outside n * nx * ntracers reals of path and n * ntracers reals of mass is touched.  Halo columns are never read:
+ * a PERIODIC plan needs no wrap.  Of a windowed plan (3e) only the OWNED levels of every window are read, each with its
+ * window's own weights, in rising order of the tall level -- right after a run whatever the seams hold, so no refresh is
+ * launched.  The phantom half of an odd fp32 plan (3f), the padding of the last tile and the partner of a pair an fp32
+ * block's ends split reach no output.  Nothing of a plan's state changes (filled, have_u, have_w, halo and seam marks,
+ * the timing pair and last_kernel_ms stay), outside the run's event pair; the plan need not hold velocities.
+ * A kernel of its own on every kind of plan, not fused into the run, nothing kept between calls.  Wave-major plans: the
+ * levels of an instance are the lanes of the layout and the sum is sequential in k, so a lane owns one (instance, column)
+ * pair; a workgroup copies the column slots of 16 adjacent 8-byte elements of the instance axis through LDS as the linear
+ * streams the other block calls read, with the products rho * adz, and every lane then sums its column from LDS -- no
+ * reduction across lanes, which would change the association.  The windows of a tall plan are staged one after the
+ * other, the running sums stay in registers.
+ * MPDATA_EINVAL (before any device call): null plan, n < 1, a range outside [0, ncrms), a bad tracer range, a null path;
+ * bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1) or a null f, rho, adz in the array forms.  MPDATA_ESTATE: a plan
+ * never filled (no upload and no whole import), a host form of the other precision.  A multi-GPU handle returns
+ * MPDATA_EUNSUPPORTED as in 3d and 3g - 3j: take mpdata_plan_shard_plan(plan, g) and a shard-local sl0.
+ * Time on the MI355X (docs/EXPERIMENTS.md O, tools/column_path_bench.py): not measured yet, and the GPU tests have not yet run there; the yardstick is
+ * mpdata_plan_export_device of f alone on the same plan (the call reads the same bytes and writes 1 / nzm of them). */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_column_path_device(mpdata_plan* plan, int64_t sl0, int64_t n, void* path, void* mass, int first_tracer,
+                                   int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3j host forms) */
+int mpdata_plan_column_path(mpdata_plan* plan, int64_t sl0, int64_t n, double* path, double* mass);
+int mpdata_plan_column_path_f32(mpdata_plan* plan, int64_t sl0, int64_t n, float* path, float* mass);
+/* the same on reference-layout DEVICE arrays f(ncrms,-2:nx+3,1,nzm[,ntracers]), rho(ncrms,nzm), adz(ncrms,nzm),
+ * asynchronous on `stream` (one thread per instance, 64-bit offsets: arrays of 4 GiB and more) */
+int mpdata_column_path_device(int64_t ncrms, int nx, int nz, int ntracers, const double* f, const double* rho,
+                              const double* adz, double* path, double* mass, void* stream);
+int mpdata_column_path_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, const float* rho,
+                                  const float* adz, float* path, float* mass, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
