@@ -131,6 +131,14 @@ def lib():
         for name in ("mpdata_column_path_device", "mpdata_column_path_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, dp, dp, dp, vp]
+        L.mpdata_plan_diffuse_device.restype = ci
+        L.mpdata_plan_diffuse_device.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_diffuse", "mpdata_plan_diffuse_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp, dp, dp, dp, dp]
+        for name in ("mpdata_diffuse_device", "mpdata_diffuse_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 9 + [vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -785,6 +793,39 @@ class Plan:
                 raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {full}")
         _check(getattr(lib(), "mpdata_plan_column_path" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def diffuse(self, tkh, cx, cz, sb=None, st=None, zflux=None, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """Eddy diffusion of f in place (include/mpdata_hip.h 3l) on the interior columns of instances [sl0, sl0+n) (default:
+        the rest of the plan from sl0), a Jacobi step from the x- and z-fluxes of the old field, on the plan's stream
+        (mpdata_plan_diffuse_device).  Reference-layout DEVICE tensors of the plan's precision, shapes diffuse_shapes(n, nx,
+        nz, ntr): tkh (nzm, nx+2, n), cx, cz (nzm, n), sb, st (nx, n) or None (zero flux), zflux ([ntr,] nz, n) or None
+        (skipped).  The tracers are first_tracer .. +ntr-1, ntr = ntracers, or the leading axis of a 3-d zflux (else 1).
+        Windowed plans: MpdataError (EUNSUPPORTED)."""
+        n = self._block_n(sl0, n)
+        nx, nz = self.dims[1], self.dims[2]
+        lead = zflux is not None and zflux.dim() == 3
+        ntr = int(ntracers) if ntracers is not None else (int(zflux.shape[0]) if lead else 1)
+        sh = diffuse_shapes(n, nx, nz, ntr if (lead or ntr != 1) else None)
+        ptrs = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt())
+                for k, t in (("tkh", tkh), ("cx", cx), ("cz", cz), ("sb", sb), ("st", st), ("zflux", zflux))]
+        _check(lib().mpdata_plan_diffuse_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
+
+    def diffuse_host(self, tkh, cx, cz, sb=None, st=None, zflux=None, sl0=0, n=None):
+        """The same for all tracers from HOST arrays (numpy, Fortran order): tkh (n, nx+2, nzm), cx, cz (n, nzm), sb, st
+        (n, nx) or None, zflux (n, nz[, ntracers]) or None (written), synchronous (mpdata_plan_diffuse[_f32])."""
+        n = self._block_n(sl0, n)
+        nx, nz, nt = self.dims[1], self.dims[2], self.dims[3]
+        ptrs = []
+        for name, a, want, wr in (("tkh", tkh, (n, nx + 2, nz - 1), False), ("cx", cx, (n, nz - 1), False), ("cz", cz, (n, nz - 1), False),
+                                  ("sb", sb, (n, nx), False), ("st", st, (n, nx), False),
+                                  ("zflux", zflux, (n, nz) + ((nt,) if nt > 1 else ()), True)):
+            if a is None:
+                ptrs.append(None)
+                continue
+            ptrs.append(_host_ptr(a, name, wr, self._dt))
+            if tuple(a.shape) != want and not (name == "zflux" and nt == 1 and tuple(a.shape) == want + (1,)):
+                raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {want}")
+        _check(getattr(lib(), "mpdata_plan_diffuse" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -900,6 +941,37 @@ def column_path(f, rho, adz, path, mass=None, stream=None):
     pm = None if mass is None else _dev_ptr(mass, sh["mass"], "mass", f.dtype)
     fn = lib().mpdata_column_path_device if f.dtype == torch.float64 else lib().mpdata_column_path_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, pr, pa, pp, pm, _stream_handle(stream)))
+
+
+def diffuse_shapes(n, nx, nz, ntracers=None):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a diffuse call on n instances: tkh (nzm,
+    nx+2, n), cx, cz (nzm, n), sb, st (nx, n), zflux ([ntracers,] nz, n); ntracers None: one tracer without the leading axis."""
+    lead = () if ntracers is None else (int(ntracers),)
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {"tkh": (nz - 1, nx + 2, n), "cx": (nz - 1, n), "cz": (nz - 1, n), "sb": (nx, n), "st": (nx, n), "zflux": lead + (nz, n)}
+
+
+def diffuse(f, rho, adz, tkh, cx, cz, sb=None, st=None, zflux=None, sl0=0, n=None, stream=None):
+    """Eddy diffusion (include/mpdata_hip.h 3l) of instances [sl0, sl0+n) (default: the rest from sl0) of a reference-layout
+    DEVICE tensor f ([ntr,] nzm, nx+6, ncrms) with rho, adz (nzm, ncrms), float64 or float32, in place; tkh, cx, cz, sb, st,
+    zflux of the same dtype with the shapes of diffuse_shapes(n, nx, nz, ntr) (sb, st, zflux may be None).  Enqueued on
+    `stream`; returns when the work is done (mpdata_diffuse_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"diffuse: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    pr = _dev_ptr(rho, (nzm, ncrms), "rho", f.dtype)
+    pa = _dev_ptr(adz, (nzm, ncrms), "adz", f.dtype)
+    sh = diffuse_shapes(n, nxp6 - 6, nzm + 1, nt if f.dim() == 4 else None)
+    ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype)
+            for k, t in (("tkh", tkh), ("cx", cx), ("cz", cz), ("sb", sb), ("st", st), ("zflux", zflux))]
+    fn = lib().mpdata_diffuse_device if f.dtype == torch.float64 else lib().mpdata_diffuse_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, *ptrs, _stream_handle(stream)))
 
 
 def level_add(f, d, mode=LEVEL_ADD, stream=None):

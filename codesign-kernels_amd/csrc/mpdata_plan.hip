@@ -15,6 +15,7 @@
 
 #include "mpdata_courant.h"
 #include "mpdata_column_path.h"
+#include "mpdata_diffuse.h"
 #include "mpdata_internal.h"
 #include "mpdata_level_add.h"
 #include "mpdata_scale_uw.h"
@@ -85,6 +86,8 @@ struct mpdata_plan {
   size_t stage_elems;
   void* bstage;                      // staging of mpdata_plan_download_instances: f and flux of one block (grown on demand)
   size_t bstage_bytes;
+  void* dbuf;                        // mpdata_plan_diffuse_device: tkh in the plan layout (wave-major plans), the new interior
+  size_t dbuf_bytes;                 // of the block (reference-layout plans); grown on demand
   void* flux_ref;                    // flux in the reference layout (level nz is carried through)
   void* wpark;                       // EXACT: park array of the limited vertical fluxes (bit-identical flux); with park_regs
   size_t wpark_bytes;                // only mpdata_plan_run_uw needs it: allocated by its first call
@@ -567,6 +570,16 @@ int plan_bstage(mpdata_plan* p, size_t need) {
   p->bstage = nullptr; p->bstage_bytes = 0;
   HIP_TRY(hipMalloc(&p->bstage, need));
   p->bstage_bytes = need;
+  return 0;
+}
+// the plan's diffusion buffer (mpdata_plan_diffuse_device), grown as the block staging buffer is
+int plan_dbuf(mpdata_plan* p, size_t need) {
+  if (p->dbuf_bytes >= need) return 0;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (p->dbuf) (void)hipFree(p->dbuf);
+  p->dbuf = nullptr; p->dbuf_bytes = 0;
+  HIP_TRY(hipMalloc(&p->dbuf, need));
+  p->dbuf_bytes = need;
   return 0;
 }
 // a block of a plan for the kernels that walk its plan layout (mpdata_wm_walk.h), with wm_plan(p) the plan the layout
@@ -1271,6 +1284,144 @@ int mpdata_column_path_f32_device(int64_t ncrms, int nx, int nz, int ntracers, c
   return column_path_array(ncrms, nx, nz, ntracers, f, rho, adz, path, mass, stream, 4);
 }
 
+// ---- 3l: eddy diffusion of f, in place.  Reads tkh, cx, cz, sb, st and the plan's rho and adz, rewrites the interior
+// columns of f of the block's instances and the tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not
+// touched and no event is recorded.  The halo columns 0 and nx+1 are inputs: a periodic plan wraps stale halos first, as a
+// run does, and afterwards its halos are copies of the OLD interior, so the marks of the range are cleared and the next
+// run or read-back wraps again.  Wave-major plans: tkh is brought into the plan layout once per call by the conversion
+// kernels of an import of f -- the block's for a block, the whole import's for the whole plan -- (a job of nx + 2 columns
+// at column slot 2 into the plan's diffusion buffer; slots outside the block are not written and reach no result); reference-layout plans: the buffer takes the new interior (mpdata_diffuse.h).
+static int plan_diffuse(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
+                        const void* st, void* zflux, int first, int count) {
+  const int nx = p->nx, nzm = p->nz - 1;
+  const bool wm = p->layout == MPDATA_LAYOUT_WAVEMAJOR;
+  int rc = plan_dbuf(p, wm ? (size_t)p->ntiles * p->tile_elems * 8 : (size_t)n * nx * nzm * count * p->eb);
+  if (!rc) rc = plan_wrap_f(p, first, count);
+  if (rc) return rc;
+  if (wm) {
+    MpdataBlockJob tj = wm_block_job(p, 0, const_cast<void*>(tkh), sl0, n, 0, 1);
+    tj.j.prv = p->dbuf; tj.j.ncols = nx + 2; tj.j.prv_col0 = 2; tj.j.ref_levmul = nx + 2; tj.j.ref_tstride = 0; tj.j.prv_tstride = 0;
+    if (n != p->ncrms) {
+      HIP_TRY(mpdata_layout_convert_block(tj, true, p->stream));
+    } else if (p->odd) {   // the whole plan: the kernels of a whole import of f (plan_import)
+      HIP_TRY(mpdata_layout_convert_odd(&tj.j, 1, true, p->stream));
+    } else if (!legacy_convert()) {
+      const hipError_t e = mpdata_layout_import_rows(&tj.j, 1, p->stream);
+      if (e == hipErrorNotSupported) HIP_TRY(mpdata_layout_convert_cols(&tj.j, 1, true, p->stream));
+      else HIP_TRY(e);
+    } else {
+      HIP_TRY(mpdata_layout_convert(tj.j, 8, true, p->stream));
+    }
+    const MpdataLayoutJob jr = wm_job(p, 3, nullptr, 0, 1), ja = wm_job(p, 5, nullptr, 0, 1);
+    MpdataDiffuseJob b;
+    b.j = wm_job(p, 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.tkh = p->dbuf;
+    b.rho = (const double*)jr.prv + jr.prv_col0 * jr.chunk;
+    b.adz = (const double*)ja.prv + ja.prv_col0 * ja.chunk;
+    b.kc_tile_stride = jr.prv_tile_stride;
+    b.cx = cx; b.cz = cz; b.sb = sb; b.st = st; b.zflux = zflux;
+    HIP_TRY(mpdata_diffuse_wm(b, p->stream));
+  } else {
+    const size_t f1 = p->sz.f / p->ntracers;
+    HIP_TRY(mpdata_diffuse_ref((char*)p->f + (size_t)first * f1 * p->eb, p->rho, p->adz, p->eb, p->ncrms, sl0, n, nx, nzm, count, tkh, cx,
+                               cz, sb, st, zflux, p->dbuf, p->stream));
+  }
+  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
+  return 0;
+}
+// range, then NULLs, then what the plan is and holds
+static int plan_diffuse_check(const char* what, mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz,
+                              int first, int count, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = tracer_range(p, first, count);
+  if (rc) return rc;
+  if (!tkh || !cx || !cz) return set_err(MPDATA_EINVAL, "%s: null %s", what, !tkh ? "tkh" : !cx ? "cx" : "cz");
+  if (p->inner)
+    return set_err(MPDATA_EUNSUPPORTED, "%s on a windowed plan (nz = %d > 238): tkh would have to be cut into level windows and the "
+                                        "seams refreshed; not built yet", what, p->nz);
+  if (eb) {
+    rc = plan_check(p, eb);
+    if (rc) return rc;
+  }
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
+  return 0;
+}
+int mpdata_plan_diffuse_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
+                               const void* st, void* zflux, int first_tracer, int ntracers) {
+  const int rc = plan_diffuse_check("mpdata_plan_diffuse_device", p, sl0, n, tkh, cx, cz, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_diffuse(p, sl0, n, tkh, cx, cz, sb, st, zflux, first_tracer, ntracers);
+}
+// host arrays, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
+static int plan_diffuse_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
+                             const void* st, void* zflux, int eb) {
+  int rc = plan_diffuse_check("mpdata_plan_diffuse", p, sl0, n, tkh, cx, cz, 0, p ? p->ntracers : 1, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const int nx = p->nx, nz = p->nz, nzm = nz - 1;
+  const size_t tb = (size_t)n * (nx + 2) * nzm * eb, cb = (size_t)n * nzm * eb, xb = (size_t)n * nx * eb,
+               zb = zflux ? (size_t)n * nz * p->ntracers * eb : 0;
+  rc = plan_bstage(p, tb + 2 * cb + 2 * xb + zb);
+  if (rc) return rc;
+  char* const d = (char*)p->bstage;
+  void* const dt = d; void* const dcx = d + tb; void* const dcz = d + tb + cb;
+  void* const dsb = sb ? d + tb + 2 * cb : nullptr;
+  void* const dst = st ? d + tb + 2 * cb + xb : nullptr;
+  void* const dz = zflux ? d + tb + 2 * cb + 2 * xb : nullptr;
+  HIP_TRY(hipMemcpyAsync(dt, tkh, tb, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(dcx, cx, cb, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(dcz, cz, cb, hipMemcpyHostToDevice, p->stream));
+  if (sb) HIP_TRY(hipMemcpyAsync(dsb, sb, xb, hipMemcpyHostToDevice, p->stream));
+  if (st) HIP_TRY(hipMemcpyAsync(dst, st, xb, hipMemcpyHostToDevice, p->stream));
+  rc = plan_diffuse(p, sl0, n, dt, dcx, dcz, dsb, dst, dz, 0, p->ntracers);
+  if (rc) return rc;
+  if (zflux) HIP_TRY(hipMemcpyAsync(zflux, dz, zb, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+int mpdata_plan_diffuse(mpdata_plan* p, int64_t sl0, int64_t n, const double* tkh, const double* cx, const double* cz, const double* sb,
+                        const double* st, double* zflux) {
+  return plan_diffuse_host(p, sl0, n, tkh, cx, cz, sb, st, zflux, 8);
+}
+int mpdata_plan_diffuse_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* tkh, const float* cx, const float* cz, const float* sb,
+                            const float* st, float* zflux) {
+  return plan_diffuse_host(p, sl0, n, tkh, cx, cz, sb, st, zflux, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call).  The new interior of the block
+// goes through a scratch array of the call's own, which is freed when the work is done: the call returns after it.
+static int diffuse_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* rho, const void* adz,
+                         const void* tkh, const void* cx, const void* cz, const void* sb, const void* st, void* zflux, void* stream, int eb) {
+  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
+    return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
+                   (long long)ncrms, nx, nz, ntracers);
+  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
+    return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
+                   (long long)(sl0 + n), (long long)ncrms);
+  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
+  if (!tkh || !cx || !cz) return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: null %s", !tkh ? "tkh" : !cx ? "cx" : "cz");
+  void* scratch = nullptr;
+  HIP_TRY(hipMalloc(&scratch, (size_t)n * nx * (nz - 1) * ntracers * eb));
+  hipError_t e = mpdata_diffuse_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tkh, cx, cz, sb, st, zflux, scratch,
+                                    (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(scratch);
+  HIP_TRY(e);
+  return 0;
+}
+int mpdata_diffuse_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                          const double* adz, const double* tkh, const double* cx, const double* cz, const double* sb, const double* st,
+                          double* zflux, void* stream) {
+  return diffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cx, cz, sb, st, zflux, stream, 8);
+}
+int mpdata_diffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                              const float* adz, const float* tkh, const float* cx, const float* cz, const float* sb, const float* st,
+                              float* zflux, void* stream) {
+  return diffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cx, cz, sb, st, zflux, stream, 4);
+}
+
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)
 static int plan_flux_finish(mpdata_plan* p, const MpdataWmArgs& a, int count) {
   if (!a.wpark) return 0;
@@ -1652,7 +1803,7 @@ int mpdata_plan_destroy(mpdata_plan* p) {
   }
   DevGuard g(p->device);
   arena_free(p->arena);
-  void* bufs[9] = {p->pf, p->pu, p->pw, p->pkc, p->pflux, p->stage, p->flux_ref, p->wpark, p->bstage};
+  void* bufs[10] = {p->pf, p->pu, p->pw, p->pkc, p->pflux, p->stage, p->flux_ref, p->wpark, p->bstage, p->dbuf};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (p->ev0) (void)hipEventDestroy(p->ev0);

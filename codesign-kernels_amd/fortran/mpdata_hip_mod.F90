@@ -40,6 +40,8 @@ module mpdata_hip_mod
   public :: mpdata_plan_scale_uw_device_c, mpdata_plan_scale_uw_c, mpdata_scale_uw_device_c
   ! mass-weighted column integrals of a resident plan's tracers (include/mpdata_hip.h section 3k)
   public :: mpdata_plan_column_path_device_c, mpdata_plan_column_path_c, mpdata_column_path_device_c
+  ! eddy diffusion of a resident plan's tracers, in place (include/mpdata_hip.h section 3l)
+  public :: mpdata_plan_diffuse_device_c, mpdata_plan_diffuse_c, mpdata_diffuse_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -57,6 +59,8 @@ module mpdata_hip_mod
 #define MPDATA_C_SCALE_UW_DEVICE "mpdata_scale_uw_f32_device"
 #define MPDATA_C_PLAN_COLUMN_PATH "mpdata_plan_column_path_f32"
 #define MPDATA_C_COLUMN_PATH_DEVICE "mpdata_column_path_f32_device"
+#define MPDATA_C_PLAN_DIFFUSE "mpdata_plan_diffuse_f32"
+#define MPDATA_C_DIFFUSE_DEVICE "mpdata_diffuse_f32_device"
 #else
 #define MPDATA_C_ADVECT "mpdata_advect_scalar2d"
 #define MPDATA_C_PLAN_CREATE "mpdata_plan_create"
@@ -72,6 +76,8 @@ module mpdata_hip_mod
 #define MPDATA_C_SCALE_UW_DEVICE "mpdata_scale_uw_device"
 #define MPDATA_C_PLAN_COLUMN_PATH "mpdata_plan_column_path"
 #define MPDATA_C_COLUMN_PATH_DEVICE "mpdata_column_path_device"
+#define MPDATA_C_PLAN_DIFFUSE "mpdata_plan_diffuse"
+#define MPDATA_C_DIFFUSE_DEVICE "mpdata_diffuse_device"
 #endif
 
   interface
@@ -352,6 +358,34 @@ module mpdata_hip_mod
       integer(c_int64_t), value :: ncrms
       integer(c_int), value :: nx, nz, ntracers
       type(c_ptr), value :: f, rho, adz, path, mass
+      type(c_ptr), value :: stream
+    end function
+    ! ---- eddy diffusion of f in place (include/mpdata_hip.h section 3l): tkh(n, 0:nx+1, nzm), cx, cz(n, nzm), sb, st(n, nx)
+    ! (c_null_ptr: zero flux), zflux(n, nz [, ntracers]) (c_null_ptr: skipped); windowed plans: MPDATA_EUNSUPPORTED
+    ! device arrays of the plan's precision, asynchronous on the plan's stream:
+    integer(c_int) function mpdata_plan_diffuse_device_c(plan, sl0, n, tkh, cx, cz, sb, st, zflux, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_diffuse_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: tkh, cx, cz, sb, st, zflux
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! host arrays, all tracers (c_loc of an array of the module's precision), synchronous
+    integer(c_int) function mpdata_plan_diffuse_c(plan, sl0, n, tkh, cx, cz, sb, st, zflux) bind(C, name=MPDATA_C_PLAN_DIFFUSE)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: tkh, cx, cz, sb, st, zflux
+    end function
+    ! the same on instances [sl0, sl0 + n) of reference-layout device arrays f, rho(ncrms,nzm), adz(ncrms,nzm)
+    integer(c_int) function mpdata_diffuse_device_c(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cx, cz, sb, st, zflux, &
+        stream) bind(C, name=MPDATA_C_DIFFUSE_DEVICE)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f, rho, adz, tkh, cx, cz, sb, st, zflux
       type(c_ptr), value :: stream
     end function
   end interface

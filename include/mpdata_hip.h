@@ -518,6 +518,68 @@ int mpdata_column_path_device(int64_t ncrms, int nx, int nz, int ntracers, const
 int mpdata_column_path_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, const float* rho,
                                   const float* adz, float* path, float* mass, void* stream);
 
+/* ---- 3l. Eddy diffusion of a resident plan's tracers, in place (the operator a host model applies to every tracer right
+ * after the advection: SAM's diffuse_scalar2D, the sibling of the routine -- the last per-step operator that forced f out
+ * of a resident plan).  For instance sl in [sl0, sl0 + n), tracer t in [first_tracer, first_tracer + ntracers), nzm = nz - 1,
+ * every f on the right-hand side the value BEFORE the call (Jacobi), every operation rounded once in the plan's precision
+ * in exactly this association, nothing contracted, the divide IEEE:
+ *   Fx(i,k) = -((cx(sl,k) * (tkh(sl,i,k) + tkh(sl,i+1,k))) * (f(i+1,k) - f(i,k)))        i = 0 .. nx,  k = 1 .. nzm
+ *   Fz(i,k) = -((cz(sl,k) * (tkh(sl,i,k) + tkh(sl,i,k+1))) * (f(i,k+1) - f(i,k)))        i = 1 .. nx,  k = 1 .. nzm - 1
+ *   Fz(i,0) = sb(sl,i)   (+0 if sb is NULL)          Fz(i,nzm) = st(sl,i)   (+0 if st is NULL)
+ *   ir(k)   = 1 / (rho(sl,k) * adz(sl,k))
+ *   f(i,k)  = f(i,k) - ((Fx(i,k) - Fx(i-1,k)) + (Fz(i,k) - Fz(i,k-1)) * ir(k))           i = 1 .. nx,  k = 1 .. nzm
+ *   zflux(sl,k',t) : s = +0; do i = 1, nx: s = s + Fz(i,k'-1)                            k' = 1 .. nz   (NULL: skipped)
+ * Negating a product is exact, so the sign convention costs no rounding; EXACT and FAST plans give the same bits.  NaN and
+ * infinities are outside the contract.  All arrays are of the plan's precision, reference layout, instance index fastest,
+ * leading dimension n (the block's first instance at index 0), tightly packed:
+ *   tkh   (n, 0:nx+1, nzm)     the eddy diffusivity, shared by all tracers of the call, used as given (NOT wrapped)
+ *   cx    (n, nzm)             the caller's folded coefficient, in SAM's terms 0.5 dtn grdf_x(k) / dx^2
+ *   cz    (n, nzm)             0.5 dtn grdf_z(k) / dz^2 * rhow(k+1) / adzw(k+1); cz(:, nzm) is never read
+ *   sb,st (n, nx)              the scaled surface and top fluxes; either may be NULL
+ *   zflux (n, nz [, ntracers]) the horizontal sum of the vertical flux through every interface; may be NULL
+ * rho and adz are those the plan holds.  Only the interior columns i = 1 .. nx change; the halo columns 0 and nx+1 are
+ * inputs, exactly as they are for the routine.  GIVEN plans: they are what the plan holds.  PERIODIC plans: stale halos
+ * of the tracer range are wrapped before the kernel, as a run does, and the marks of the range are cleared afterwards,
+ * so the next run or read-back hands out wrapped halos of the diffused field.  flux, u, w, rho, rhow, adz, the boundary
+ * mode, every tracer outside the range and every slot outside the block keep every bit: the padding of the last tile, a
+ * neighbour in a tile, the partner of a pair an fp32 block splits (stored back exactly as loaded).  The one exception, as
+ * in 3i / 3j: the phantom half of an odd fp32 plan (3f) follows instance ncrms - 1 whenever the block holds it.  The plan
+ * need not hold velocities; the call is outside the run's event pair.
+ * A kernel of its own on every kind of plan, not fused into the run.  Wave-major plans: tkh is brought into the plan
+ * layout once per call (the conversion kernels of an import of f, into a buffer the plan owns, grown on demand and freed with it); a
+ * workgroup owns whole tiles, loads every column batch, its look-ahead column and the vertical neighbours in the slice
+ * next door before a barrier and stores only after it, so the in-place update is race-free by construction.
+ * Reference-layout plans and the array forms write the new interior to a scratch array and copy it back by a second
+ * kernel on the same stream.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range; null tkh, cx or cz; in the array forms
+ * bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1) or a null f, rho, adz.  MPDATA_EUNSUPPORTED: a multi-GPU handle, as in
+ * 3d - 3k (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0); a WINDOWED plan (3e, nz > 238): tkh would have to be
+ * cut into level windows and the seams refreshed -- the named follow-up, not built yet.  MPDATA_ESTATE: a host form of the
+ * other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md P, tools/diffuse_bench.py), 65536 x 32 x 28, one tracer, cold: 0.50 ms fp64,
+ * 0.26 ms fp32 -- 1.16 x and 1.18 x mpdata_plan_export_device + mpdata_plan_import_device of f alone, the yardstick (the old
+ * route without the caller's kernel).  Algorithmic traffic: f read and written once, tkh read once (2.8 TB/s); the
+ * conversion pass of tkh reads and writes it once more (4.7 TB/s of all bytes moved) and is what a next version drops. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_diffuse_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz,
+                               const void* sb, const void* st, void* zflux, int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3k host forms) */
+int mpdata_plan_diffuse(mpdata_plan* plan, int64_t sl0, int64_t n, const double* tkh, const double* cx, const double* cz,
+                        const double* sb, const double* st, double* zflux);
+int mpdata_plan_diffuse_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* tkh, const float* cx, const float* cz,
+                            const float* sb, const float* st, float* zflux);
+/* the same on instances [sl0, sl0+n) of reference-layout DEVICE arrays f(ncrms,-2:nx+3,1,nzm[,ntracers]), rho(ncrms,nzm),
+ * adz(ncrms,nzm) (leading dimension ncrms); tkh, cx, cz, sb, st, zflux as above (leading dimension n).  Enqueued on
+ * `stream`; the call allocates its scratch array and returns when the work is done and the scratch is freed. */
+int mpdata_diffuse_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                          const double* adz, const double* tkh, const double* cx, const double* cz, const double* sb,
+                          const double* st, double* zflux, void* stream);
+int mpdata_diffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                              const float* adz, const float* tkh, const float* cx, const float* cz, const float* sb,
+                              const float* st, float* zflux, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
