@@ -18,6 +18,15 @@ module mpdata_hip_mod
   public :: advect_scalar2D, advect_resident_begin, advect_resident_run, advect_resident_end
   public :: mpdata_set_variant, mpdata_check, advect_transfer_stats
   public :: advect_device_problem_run
+  ! the plan API itself (include/mpdata_hip.h sections 3, 3b, 3d, 4, 4b): what a host model that keeps its own plan handle
+  ! calls -- every block call below takes that handle
+  public :: mpdata_advect_scalar2d_c, mpdata_plan_create_c, mpdata_plan_create_multi_c, mpdata_plan_upload_c
+  public :: mpdata_plan_run_c, mpdata_plan_run_tracers_c, mpdata_plan_run_uw_c, mpdata_plan_sync_c, mpdata_plan_download_c
+  public :: mpdata_plan_last_kernel_ms_c, mpdata_plan_set_timing_c, mpdata_plan_set_stream_c, mpdata_plan_destroy_c
+  public :: mpdata_plan_import_device_c, mpdata_plan_export_device_c, mpdata_plan_transfer_stats_c, mpdata_plan_ranks_seen_c
+  public :: mpdata_plan_import_instances_device_c, mpdata_plan_export_instances_device_c, mpdata_plan_download_instances_c
+  public :: mpdata_device_alloc_c, mpdata_plan_device_alloc_c, mpdata_device_free_c, mpdata_device_sum_c
+  public :: mpdata_fill_synthetic_device_c, mpdata_last_error_c
   ! periodic lateral boundaries (include/mpdata_hip.h sections 3a, 3c): the CRMs of the MMF are periodic in x
   public :: MPDATA_BOUNDARY_GIVEN, MPDATA_BOUNDARY_PERIODIC
   public :: mpdata_plan_set_boundary_c, mpdata_plan_boundary_c, mpdata_periodic_halo_device_c
@@ -32,7 +41,7 @@ module mpdata_hip_mod
   public :: mpdata_plan_level_stats_device_c, mpdata_plan_level_stats_c, mpdata_level_stats_device_c
 
   ! outflow Courant number of a resident plan's velocities (include/mpdata_hip.h section 3h)
-  public :: mpdata_plan_courant_device_c, mpdata_plan_courant_device
+  public :: mpdata_plan_courant_device_c, mpdata_plan_courant_device, mpdata_plan_courant_c, mpdata_courant_device_c
   ! per-level increments of a resident plan's tracers, in place (include/mpdata_hip.h section 3i)
   public :: mpdata_plan_level_add_device_c, mpdata_plan_level_add_c, mpdata_level_add_device_c
   integer(c_int), parameter, public :: MPDATA_LEVEL_ADD = 0, MPDATA_LEVEL_ADD_CLIP = 1
@@ -53,6 +62,8 @@ module mpdata_hip_mod
 #define MPDATA_C_PLAN_DOWNLOAD_INSTANCES "mpdata_plan_download_instances_f32"
 #define MPDATA_C_PLAN_LEVEL_STATS "mpdata_plan_level_stats_f32"
 #define MPDATA_C_LEVEL_STATS_DEVICE "mpdata_level_stats_f32_device"
+#define MPDATA_C_PLAN_COURANT "mpdata_plan_courant_f32"
+#define MPDATA_C_COURANT_DEVICE "mpdata_courant_f32_device"
 #define MPDATA_C_PLAN_LEVEL_ADD "mpdata_plan_level_add_f32"
 #define MPDATA_C_LEVEL_ADD_DEVICE "mpdata_level_add_f32_device"
 #define MPDATA_C_PLAN_SCALE_UW "mpdata_plan_scale_uw_f32"
@@ -70,6 +81,8 @@ module mpdata_hip_mod
 #define MPDATA_C_PLAN_DOWNLOAD_INSTANCES "mpdata_plan_download_instances"
 #define MPDATA_C_PLAN_LEVEL_STATS "mpdata_plan_level_stats"
 #define MPDATA_C_LEVEL_STATS_DEVICE "mpdata_level_stats_device"
+#define MPDATA_C_PLAN_COURANT "mpdata_plan_courant"
+#define MPDATA_C_COURANT_DEVICE "mpdata_courant_device"
 #define MPDATA_C_PLAN_LEVEL_ADD "mpdata_plan_level_add"
 #define MPDATA_C_LEVEL_ADD_DEVICE "mpdata_level_add_device"
 #define MPDATA_C_PLAN_SCALE_UW "mpdata_plan_scale_uw"
@@ -102,12 +115,13 @@ module mpdata_hip_mod
       integer(c_int), value :: nx, nz, ntracers, ngpus
       type(c_ptr) :: plan
     end function
-    integer(c_int) function mpdata_plan_transfer_stats_c(plan, scatter_s, gather_s, sbytes, gbytes, transport) &
+    integer(c_int) function mpdata_plan_transfer_stats_c(plan, scatter_s, gather_s, scatter_bytes_per_peer, gather_bytes_per_peer, &
+        transport) &
         bind(C, name="mpdata_plan_transfer_stats")
       import :: c_int, c_int64_t, c_ptr, c_double
       type(c_ptr), value :: plan
       real(c_double) :: scatter_s, gather_s
-      integer(c_int64_t) :: sbytes, gbytes
+      integer(c_int64_t) :: scatter_bytes_per_peer, gather_bytes_per_peer
       integer(c_int) :: transport
     end function
     integer(c_int) function mpdata_plan_upload_c(plan, f, u, w, rho, rhow, adz, flux) bind(C, name=MPDATA_C_PLAN_UPLOAD)
@@ -118,6 +132,19 @@ module mpdata_hip_mod
     integer(c_int) function mpdata_plan_run_c(plan) bind(C, name="mpdata_plan_run")
       import :: c_int, c_ptr
       type(c_ptr), value :: plan
+    end function
+    ! a sub-range of the tracers
+    integer(c_int) function mpdata_plan_run_tracers_c(plan, first_tracer, ntracers) bind(C, name="mpdata_plan_run_tracers")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! one step on fresh reference-layout DEVICE u, w of the plan's precision; the plan holds no velocities afterwards
+    integer(c_int) function mpdata_plan_run_uw_c(plan, first_tracer, ntracers, u, w) bind(C, name="mpdata_plan_run_uw")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int), value :: first_tracer, ntracers
+      type(c_ptr), value :: u, w
     end function
     integer(c_int) function mpdata_plan_sync_c(plan) bind(C, name="mpdata_plan_sync")
       import :: c_int, c_ptr
@@ -132,6 +159,17 @@ module mpdata_hip_mod
       import :: c_int, c_ptr, c_double
       type(c_ptr), value :: plan
       real(c_double) :: ms
+    end function
+    ! on = 0: no event pair around the runs (mpdata_plan_last_kernel_ms_c then returns MPDATA_ESTATE)
+    integer(c_int) function mpdata_plan_set_timing_c(plan, on) bind(C, name="mpdata_plan_set_timing")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int), value :: on
+    end function
+    ! run on the caller's stream (a hipStream_t; c_null_ptr: the default stream) from now on
+    integer(c_int) function mpdata_plan_set_stream_c(plan, stream) bind(C, name="mpdata_plan_set_stream")
+      import :: c_int, c_ptr
+      type(c_ptr), value :: plan, stream
     end function
     integer(c_int) function mpdata_plan_destroy_c(plan) bind(C, name="mpdata_plan_destroy")
       import :: c_int, c_ptr
@@ -160,11 +198,11 @@ module mpdata_hip_mod
       import :: c_int, c_ptr
       type(c_ptr), value :: ptr
     end function
-    integer(c_int) function mpdata_device_sum_c(a, n, blk, stride, s) bind(C, name="mpdata_device_sum")
+    integer(c_int) function mpdata_device_sum_c(a, n, block, stride, sum) bind(C, name="mpdata_device_sum")
       import :: c_int, c_int64_t, c_ptr, c_double
       type(c_ptr), value :: a
-      integer(c_int64_t), value :: n, blk, stride
-      real(c_double) :: s
+      integer(c_int64_t), value :: n, block, stride
+      real(c_double) :: sum
     end function
     integer(c_int) function mpdata_fill_synthetic_device_c(a, sid, rows, ncrms_global, sl0, nloc, seed, dist, stream) &
         bind(C, name="mpdata_fill_synthetic_device")
@@ -173,33 +211,35 @@ module mpdata_hip_mod
       integer(c_int), value :: sid, dist
       integer(c_int64_t), value :: rows, ncrms_global, sl0, nloc, seed
     end function
-    integer(c_int) function mpdata_plan_import_device_c(plan, f, u, w, rho, rhow, adz, flux, first, n) &
+    integer(c_int) function mpdata_plan_import_device_c(plan, f, u, w, rho, rhow, adz, flux, first_tracer, ntracers) &
         bind(C, name="mpdata_plan_import_device")
       import :: c_int, c_ptr
       type(c_ptr), value :: plan, f, u, w, rho, rhow, adz, flux
-      integer(c_int), value :: first, n
+      integer(c_int), value :: first_tracer, ntracers
     end function
-    integer(c_int) function mpdata_plan_export_device_c(plan, f, flux, first, n) bind(C, name="mpdata_plan_export_device")
+    integer(c_int) function mpdata_plan_export_device_c(plan, f, flux, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_export_device")
       import :: c_int, c_ptr
       type(c_ptr), value :: plan, f, flux
-      integer(c_int), value :: first, n
+      integer(c_int), value :: first_tracer, ntracers
     end function
     ! ---- blocks of CRM instances [sl0, sl0+n) of a filled plan (include/mpdata_hip.h 3d; sl0 counts from 0): reference-layout
     ! arrays of a problem of n instances (leading dimension n); device forms asynchronous (c_null_ptr: skipped), the
     ! host form synchronous and over all tracers
-    integer(c_int) function mpdata_plan_import_instances_device_c(plan, sl0, n, f, u, w, rho, rhow, adz, flux, first, ntr) &
+    integer(c_int) function mpdata_plan_import_instances_device_c(plan, sl0, n, f, u, w, rho, rhow, adz, flux, first_tracer, &
+        ntracers) &
         bind(C, name="mpdata_plan_import_instances_device")
       import :: c_int, c_int64_t, c_ptr
       type(c_ptr), value :: plan, f, u, w, rho, rhow, adz, flux
       integer(c_int64_t), value :: sl0, n
-      integer(c_int), value :: first, ntr
+      integer(c_int), value :: first_tracer, ntracers
     end function
-    integer(c_int) function mpdata_plan_export_instances_device_c(plan, sl0, n, f, flux, first, ntr) &
+    integer(c_int) function mpdata_plan_export_instances_device_c(plan, sl0, n, f, flux, first_tracer, ntracers) &
         bind(C, name="mpdata_plan_export_instances_device")
       import :: c_int, c_int64_t, c_ptr
       type(c_ptr), value :: plan, f, flux
       integer(c_int64_t), value :: sl0, n
-      integer(c_int), value :: first, ntr
+      integer(c_int), value :: first_tracer, ntracers
     end function
     integer(c_int) function mpdata_plan_download_instances_c(plan, sl0, n, f, flux) &
         bind(C, name=MPDATA_C_PLAN_DOWNLOAD_INSTANCES)
@@ -278,6 +318,24 @@ module mpdata_hip_mod
       type(c_ptr), value :: plan
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: clev, cinst
+    end function
+    ! host clev, cinst (c_loc of an array of the module's precision, or c_null_ptr: skipped, not both), synchronous: what a
+    ! Fortran loop forms ncycle from
+    integer(c_int) function mpdata_plan_courant_c(plan, sl0, n, clev, cinst) bind(C, name=MPDATA_C_PLAN_COURANT)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: clev, cinst
+    end function
+    ! the same reduction on reference-layout device arrays u, w, rho(ncrms,nzm), adz(ncrms,nzm): the fresh u, w of a
+    ! caller of mpdata_plan_run_uw_c
+    integer(c_int) function mpdata_courant_device_c(ncrms, nx, nz, u, w, rho, adz, clev, cinst, stream) &
+        bind(C, name=MPDATA_C_COURANT_DEVICE)
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz
+      type(c_ptr), value :: u, w, rho, adz, clev, cinst
+      type(c_ptr), value :: stream
     end function
     ! section 3i: f(sl,i,k,t) = f(sl,i,k,t) + d(sl,k,t) on every column i = -2 .. nx+3 of instances [sl0, sl0+n), in place
     ! (mode MPDATA_LEVEL_ADD_CLIP: max(0, .) of the sum); d(n, nzm [, ntracers]) -- the shape of a 3g output -- is only read.
