@@ -139,6 +139,14 @@ def lib():
         for name in ("mpdata_diffuse_device", "mpdata_diffuse_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 9 + [vp]
+        L.mpdata_plan_subside_device.restype = ci
+        L.mpdata_plan_subside_device.argtypes = [vp, i64, i64, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_subside", "mpdata_plan_subside_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp, dp]
+        for name in ("mpdata_subside_device", "mpdata_subside_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, dp, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -826,6 +834,39 @@ class Plan:
                 raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {want}")
         _check(getattr(lib(), "mpdata_plan_diffuse" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def subside(self, cb, cc, dsum=None, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """Large-scale vertical advection of f in place (include/mpdata_hip.h 3m) on EVERY column (halos included) of
+        instances [sl0, sl0+n) (default: the rest of the plan from sl0): f(k) -= cb(k) (f(k) - f(k-1)) + cc(k) (f(k+1) - f(k))
+        from the old field, on the plan's stream (mpdata_plan_subside_device).  Reference-layout DEVICE tensors of the
+        plan's precision: cb, cc (nzm, n), shared by the tracers; dsum ([ntr,] nzm, n) or None (skipped), the decrement
+        summed over the interior columns.  The tracers are first_tracer .. +ntr-1, ntr = ntracers, or the leading axis of a
+        3-d dsum (else 1).  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        lead = dsum is not None and dsum.dim() == 3
+        ntr = int(ntracers) if ntracers is not None else (int(dsum.shape[0]) if lead else 1)
+        pb = _dev_ptr(cb, (nzm, n), "cb", self._tdt())
+        pc = _dev_ptr(cc, (nzm, n), "cc", self._tdt())
+        pd = None if dsum is None else _dev_ptr(dsum, ((ntr,) if (lead or ntr != 1) else ()) + (nzm, n), "dsum", self._tdt())
+        _check(lib().mpdata_plan_subside_device(self._p, int(sl0), n, pb, pc, pd, int(first_tracer), ntr))
+
+    def subside_host(self, cb, cc, dsum=None, sl0=0, n=None):
+        """The same for all tracers from HOST arrays (numpy, Fortran order): cb, cc (n, nzm), dsum (n, nzm[, ntracers]) or
+        None (written), synchronous (mpdata_plan_subside[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        ptrs = []
+        for name, a in (("cb", cb), ("cc", cc)):
+            ptrs.append(_host_ptr(a, name, False, self._dt))
+            if tuple(a.shape) != (n, nzm):
+                raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {(n, nzm)}")
+        if dsum is None:
+            ptrs.append(None)
+        else:
+            ptrs.append(_host_ptr(dsum, "dsum", True, self._dt))
+            self._block_host_shape(dsum, "dsum", n)
+        _check(getattr(lib(), "mpdata_plan_subside" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -972,6 +1013,25 @@ def diffuse(f, rho, adz, tkh, cx, cz, sb=None, st=None, zflux=None, sl0=0, n=Non
             for k, t in (("tkh", tkh), ("cx", cx), ("cz", cz), ("sb", sb), ("st", st), ("zflux", zflux))]
     fn = lib().mpdata_diffuse_device if f.dtype == torch.float64 else lib().mpdata_diffuse_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, *ptrs, _stream_handle(stream)))
+
+
+def subside_device(f, cb, cc, dsum=None, stream=None):
+    """Large-scale vertical advection (include/mpdata_hip.h 3m) on every column of a reference-layout DEVICE tensor f
+    ([ntr,] nzm, nx+6, ncrms), float64 or float32, in place; cb, cc (nzm, ncrms) and dsum ([ntr,] nzm, ncrms) or None of the
+    same dtype.  Enqueued on `stream`; returns when the work is done (mpdata_subside_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"subside_device: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    pb = _dev_ptr(cb, (nzm, ncrms), "cb", f.dtype)
+    pc = _dev_ptr(cc, (nzm, ncrms), "cc", f.dtype)
+    pd = None if dsum is None else _dev_ptr(dsum, tuple(f.shape[:-3]) + (nzm, ncrms), "dsum", f.dtype)
+    fn = lib().mpdata_subside_device if f.dtype == torch.float64 else lib().mpdata_subside_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, pf, pb, pc, pd, _stream_handle(stream)))
 
 
 def level_add(f, d, mode=LEVEL_ADD, stream=None):

@@ -20,6 +20,7 @@
 #include "mpdata_level_add.h"
 #include "mpdata_scale_uw.h"
 #include "mpdata_stats.h"
+#include "mpdata_subside.h"
 #include "mpdata_windows.h"
 
 using namespace mpd;
@@ -87,7 +88,7 @@ struct mpdata_plan {
   void* bstage;                      // staging of mpdata_plan_download_instances: f and flux of one block (grown on demand)
   size_t bstage_bytes;
   void* dbuf;                        // mpdata_plan_diffuse_device: tkh in the plan layout (wave-major plans), the new interior
-  size_t dbuf_bytes;                 // of the block (reference-layout plans); grown on demand
+  size_t dbuf_bytes;                 // of the block (reference-layout plans, mpdata_plan_subside_device too); grown on demand
   void* flux_ref;                    // flux in the reference layout (level nz is carried through)
   void* wpark;                       // EXACT: park array of the limited vertical fluxes (bit-identical flux); with park_regs
   size_t wpark_bytes;                // only mpdata_plan_run_uw needs it: allocated by its first call
@@ -1420,6 +1421,111 @@ int mpdata_diffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64
                               const float* adz, const float* tkh, const float* cx, const float* cz, const float* sb, const float* st,
                               float* zflux, void* stream) {
   return diffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cx, cz, sb, st, zflux, stream, 4);
+}
+
+// ---- 3m: large-scale vertical advection of f, in place.  Reads cb, cc, rewrites f on every column slot of the block's
+// instances and the tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not touched and no event is recorded.
+//   halo marks  the operator is the same in every column slot and couples none, so halo columns that are wrapped copies
+//               stay wrapped copies (same bits in, same operations) and stale ones stay stale -- halo_ok is right as it stands;
+//   seam marks  an owned level reads one level outside the owned range, so stale seams of the range are refreshed first,
+//               as a run does; only owned levels are written, so afterwards the other copies are stale: the marks of the
+//               range are cleared and the next run refreshes them;
+//   phantom     follows the plan's last slot inside the kernel (mpdata_subside.h); on a windowed plan the refresh of the
+//               inner plan follows as after a seam refresh.
+// Reference-layout plans: the plan's diffusion buffer takes the new rows (mpdata_subside.h).
+static int plan_subside(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int first, int count) {
+  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
+    int rc = plan_seams(p, first, count);
+    if (rc) return rc;
+    MpdataSubsideJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.cb = cb; b.cc = cc; b.dsum = dsum;
+    HIP_TRY(mpdata_subside_wm(b, p->stream));
+    if (p->inner) {
+      memset(p->seam_ok + first, 0, (size_t)count);
+      if (sl0 + n == p->ncrms) rc = plan_phantom(p->inner, 0, first, count);
+      if (rc) return rc;
+    }
+  } else {
+    const int rc = plan_dbuf(p, (size_t)n * (p->nx + 6) * (p->nz - 1) * count * p->eb);
+    if (rc) return rc;
+    const size_t f1 = p->sz.f / p->ntracers;
+    HIP_TRY(mpdata_subside_ref((char*)p->f + (size_t)first * f1 * p->eb, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, cb, cc, dsum,
+                               p->dbuf, p->stream));
+  }
+  return 0;
+}
+// range, then NULLs, then what the plan is and holds
+static int plan_subside_check(const char* what, mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, int first,
+                              int count, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = tracer_range(p, first, count);
+  if (rc) return rc;
+  if (!cb || !cc) return set_err(MPDATA_EINVAL, "%s: null %s", what, !cb ? "cb" : "cc");
+  if (eb) {
+    rc = plan_check(p, eb);
+    if (rc) return rc;
+  }
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
+  return 0;
+}
+int mpdata_plan_subside_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int first_tracer,
+                               int ntracers) {
+  const int rc = plan_subside_check("mpdata_plan_subside_device", p, sl0, n, cb, cc, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_subside(p, sl0, n, cb, cc, dsum, first_tracer, ntracers);
+}
+// host arrays, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
+static int plan_subside_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int eb) {
+  int rc = plan_subside_check("mpdata_plan_subside", p, sl0, n, cb, cc, 0, p ? p->ntracers : 1, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb, db = dsum ? kb * p->ntracers : 0;
+  rc = plan_bstage(p, 2 * kb + db);
+  if (rc) return rc;
+  char* const d = (char*)p->bstage;
+  void* const dd = dsum ? d + 2 * kb : nullptr;
+  HIP_TRY(hipMemcpyAsync(d, cb, kb, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(d + kb, cc, kb, hipMemcpyHostToDevice, p->stream));
+  rc = plan_subside(p, sl0, n, d, d + kb, dd, 0, p->ntracers);
+  if (rc) return rc;
+  if (dsum) HIP_TRY(hipMemcpyAsync(dsum, dd, db, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+int mpdata_plan_subside(mpdata_plan* p, int64_t sl0, int64_t n, const double* cb, const double* cc, double* dsum) {
+  return plan_subside_host(p, sl0, n, cb, cc, dsum, 8);
+}
+int mpdata_plan_subside_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* cb, const float* cc, float* dsum) {
+  return plan_subside_host(p, sl0, n, cb, cc, dsum, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call).  The new rows go through a
+// scratch array of the call's own, which is freed when the work is done: the call returns after it.
+static int subside_array(int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* cb, const void* cc, void* dsum, void* stream,
+                         int eb) {
+  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
+    return set_err(MPDATA_EINVAL, "mpdata_subside_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
+                   (long long)ncrms, nx, nz, ntracers);
+  if (!f) return set_err(MPDATA_EINVAL, "mpdata_subside_device: null f");
+  if (!cb || !cc) return set_err(MPDATA_EINVAL, "mpdata_subside_device: null %s", !cb ? "cb" : "cc");
+  void* scratch = nullptr;
+  HIP_TRY(hipMalloc(&scratch, (size_t)ncrms * (nx + 6) * (nz - 1) * ntracers * eb));
+  hipError_t e = mpdata_subside_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, cb, cc, dsum, scratch, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(scratch);
+  HIP_TRY(e);
+  return 0;
+}
+int mpdata_subside_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* cb, const double* cc, double* dsum,
+                          void* stream) {
+  return subside_array(ncrms, nx, nz, ntracers, f, cb, cc, dsum, stream, 8);
+}
+int mpdata_subside_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* cb, const float* cc, float* dsum,
+                              void* stream) {
+  return subside_array(ncrms, nx, nz, ntracers, f, cb, cc, dsum, stream, 4);
 }
 
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)

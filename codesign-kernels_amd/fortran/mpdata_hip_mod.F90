@@ -51,6 +51,10 @@ module mpdata_hip_mod
   public :: mpdata_plan_column_path_device_c, mpdata_plan_column_path_c, mpdata_column_path_device_c
   ! eddy diffusion of a resident plan's tracers, in place (include/mpdata_hip.h section 3l)
   public :: mpdata_plan_diffuse_device_c, mpdata_plan_diffuse_c, mpdata_diffuse_device_c
+  ! large-scale vertical advection of a resident plan's tracers, in place (include/mpdata_hip.h section 3m): the device
+  ! form only -- it carries no reals of its own, so one binding serves both precisions; the per-precision host and array
+  ! forms (mpdata_plan_subside[_f32], mpdata_subside[_f32]_device) have no Fortran interface yet
+  public :: mpdata_plan_subside_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -445,6 +449,17 @@ module mpdata_hip_mod
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: f, rho, adz, tkh, cx, cz, sb, st, zflux
       type(c_ptr), value :: stream
+    end function
+    ! ---- large-scale vertical advection of f in place (include/mpdata_hip.h section 3m): cb, cc(n, nzm), dsum(n, nzm
+    ! [, ntracers]) (c_null_ptr: skipped); device arrays of the plan's precision, asynchronous on the plan's stream;
+    ! windowed plans are supported
+    integer(c_int) function mpdata_plan_subside_device_c(plan, sl0, n, cb, cc, dsum, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_subside_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: cb, cc, dsum
+      integer(c_int), value :: first_tracer, ntracers
     end function
   end interface
 

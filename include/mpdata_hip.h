@@ -580,6 +580,72 @@ int mpdata_diffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64
                               const float* adz, const float* tkh, const float* cx, const float* cz, const float* sb,
                               const float* st, float* zflux, void* stream);
 
+/* ---- 3m. Large-scale vertical advection of a resident plan's tracers, in place (the per-step operator a host model
+ * applies to every tracer with the large-scale vertical velocity: SAM's subsidence, first-order upwind along k with one
+ * velocity per level).  This section is the specification; the reference tree has no such routine.  For instance sl in
+ * [sl0, sl0 + n), tracer t in [first_tracer, first_tracer + ntracers), nzm = nz - 1, level k = 1 .. nzm, kb = max(1, k-1),
+ * kc = min(nzm, k+1) and EVERY column slot i = -2 .. nx+3:
+ *   dec(i,k) = cb(sl,k) * (f(i,k) - f(i,kb))  +  cc(sl,k) * (f(i,kc) - f(i,k))
+ *   f(i,k)   = f(i,k) - dec(i,k)
+ *   dsum(sl,k,t) : s = +0;  do i = 1, nx:  s = s + dec(i,k)                              (NULL: skipped)
+ * Every f on the right-hand side is the value BEFORE the call (Jacobi).  Every operation is rounded once in the plan's
+ * precision, in exactly this association: two subtractions, two products, their sum, the final subtraction.  Nothing is
+ * contracted, so EXACT and FAST plans give the same bits.  NaN and infinities are outside the contract.  A field that is
+ * constant in k keeps every bit for any cb, cc, except that a -0.0 may come back as +0.0 (the differences are +0, the
+ * decrement is -0 where both coefficients are negative, and -0 - (-0) = +0).  All arrays are of the plan's precision,
+ * reference layout, instance index fastest, leading dimension n (the block's first instance at index 0), tightly packed:
+ *   cb,cc (n, nzm)              shared by the tracers of the call, both required.  In SAM's terms the caller folds
+ *                               dtn wsub(k) / (dz adzw(k)) into cb where wsub(k) >= 0, with cc = 0 there, and
+ *                               dtn wsub(k) / (dz adzw(k+1)) into cc where wsub(k) < 0, with cb = 0; both zero at k = 1
+ *                               and k = nzm.  The library does not look at signs.
+ *   dsum  (n, nzm [, ntracers]) the decrement summed over the interior columns in rising i -- what a host model
+ *                               accumulates as its large-scale advective tendency; may be NULL
+ * Towards the rest of a plan:
+ *   halo marks   the operator is the same in every column and couples none, so it acts on halo slots as on any other:
+ *     the wrapped halos of a PERIODIC plan stay wrapped copies (same bits in, same operations), stale ones stay stale,
+ *     and the marks are not touched -- no wrap is launched before or after.
+ *   windowed plans (3e, nz > 238) are supported.  An owned level reads one level outside the owned range, so the call
+ *     first refreshes the seams of the tracers of the range that a run has left stale, as a run does.  It then writes
+ *     OWNED levels only, each with the coefficients of the tall level it stands for, and dsum is written by the owner:
+ *     every tall level once.  A margin of 3 levels exceeds the radius of 1, so the merged result equals the operator on
+ *     the tall column bit for bit.  The non-owned copies are stale afterwards: the seam marks of the range are cleared
+ *     and the next run refreshes them.
+ *   odd fp32 plans (3f)  the phantom half takes the result of instance ncrms - 1 whenever the block holds it (on a
+ *     windowed plan the phantom of the inner plan is restored behind the call, as after a seam refresh).
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded; padding slots, neighbours in a tile,
+ *     instances and tracers outside the ranges, flux, u, w, rho, rhow, adz, the held-velocity flags, the boundary mode and
+ *     the timing pair keep every bit.  The call is outside the run's event pair; the plan need not hold velocities.
+ * A kernel of its own on every kind of plan, not fused into the run.  Wave-major plans: cb(k), cc(k) sit in a lane's
+ * registers, f is read once and written once; f(k +- 1) come by a shuffle of the values just loaded, at a wave's first and
+ * last lane by a load.  Up to 64 levels a tile's column chunk is one wave's; above, a workgroup owns whole tiles and loads
+ * every column batch and its edge neighbours before a barrier and stores only after it, so the in-place update is
+ * race-free by construction.  Reference-layout plans and the array forms write the new rows to a scratch array (the
+ * plan's diffusion buffer of 3l; an allocation of the call's own in the array forms) and copy them back by a second
+ * kernel on the same stream.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range, null cb or cc; in the array forms bad
+ * sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a null f, then null cb or cc.  MPDATA_EUNSUPPORTED: a multi-GPU handle,
+ * as in 3d - 3l (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).  MPDATA_ESTATE: a host form of the other
+ * precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md S, tools/subside_bench.py), 65536 x 32 x 28, one tracer, cold: 0.237 ms fp64,
+ * 0.121 ms fp32 (4.5 / 4.4 TB/s of f read once and written once) -- 0.54 x and 0.51 x mpdata_plan_export_device +
+ * mpdata_plan_import_device of f alone (the old route without the caller's kernel) and 1.03 x mpdata_plan_level_add_device,
+ * which moves the same bytes without the stencil; dsum adds 8 %. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_subside_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum,
+                               int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3l host forms) */
+int mpdata_plan_subside(mpdata_plan* plan, int64_t sl0, int64_t n, const double* cb, const double* cc, double* dsum);
+int mpdata_plan_subside_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* cb, const float* cc, float* dsum);
+/* the same on reference-layout DEVICE arrays f(ncrms,-2:nx+3,1,nzm[,ntracers]), cb, cc (ncrms,nzm), dsum
+ * (ncrms,nzm[,ntracers]) (leading dimension ncrms).  Enqueued on `stream`; the call allocates its scratch array and
+ * returns when the work is done and the scratch is freed. */
+int mpdata_subside_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* cb, const double* cc,
+                          double* dsum, void* stream);
+int mpdata_subside_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* cb, const float* cc,
+                              float* dsum, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
