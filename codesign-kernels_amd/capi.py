@@ -669,12 +669,23 @@ class Plan:
         ntr = int(t.shape[0]) if t.dim() == 3 else 1
         return ((ntr,) if t.dim() == 3 else ()) + (self.dims[2] - 1, n), ntr
 
-    def _block_host_shape(self, a, name, n):
-        """a host array of a block call is (n, nzm[, ntracers]) (one tracer: with or without the last axis)"""
+    def _block_host(self, a, name, want, tracer_axis=False, writable=False):
+        """pointer of a host array of a block call after checking dtype, order and shape: `want`, with tracer_axis followed
+        by the plan's tracers (one tracer: with or without that axis)"""
+        p = _host_ptr(a, name, writable, self._dt)
         nt = self.dims[3]
-        want = (n, self.dims[2] - 1) + ((nt,) if nt > 1 else ())
-        if tuple(a.shape) != want and not (nt == 1 and tuple(a.shape) == want + (1,)):
-            raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {want}")
+        full = want + ((nt,) if tracer_axis and nt > 1 else ())
+        if tuple(a.shape) != full and not (tracer_axis and nt == 1 and tuple(a.shape) == want + (1,)):
+            raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {full}")
+        return p
+
+    @staticmethod
+    def _block_ntr(t, ntracers):
+        """(ntr, axis) of a block call whose tensor t (or None) may carry a leading tracer axis: ntr = ntracers, or the leading
+        axis of a 3-d t (else 1); axis: the shapes of the call carry that axis"""
+        lead = t is not None and t.dim() == 3
+        ntr = int(ntracers) if ntracers is not None else (int(t.shape[0]) if lead else 1)
+        return ntr, lead or ntr != 1
 
     def level_stats(self, sl0=0, n=None, sum=None, min=None, max=None, first_tracer=0):
         """Horizontal sum / min / max per level of f over the interior columns 1 .. nx, instances [sl0, sl0+n) (default:
@@ -693,13 +704,8 @@ class Plan:
         """The same for all tracers into HOST arrays (numpy, Fortran order, (n, nzm[, ntracers]); None = not wanted),
         synchronous (mpdata_plan_level_stats[_f32])."""
         n = self._block_n(sl0, n)
-        ptrs = []
-        for k, a in (("sum", sum), ("min", min), ("max", max)):
-            if a is None:
-                ptrs.append(None)
-                continue
-            ptrs.append(_host_ptr(a, k, True, self._dt))
-            self._block_host_shape(a, k, n)
+        ptrs = [None if a is None else self._block_host(a, k, (n, self.dims[2] - 1), True, True)
+                for k, a in (("sum", sum), ("min", min), ("max", max))]
         if all(p is None for p in ptrs):
             raise MpdataError(-1, "level_stats_host: sum, min and max are all None")
         _check(getattr(lib(), "mpdata_plan_level_stats" + self._sfx)(self._p, int(sl0), n, *ptrs))
@@ -743,8 +749,7 @@ class Plan:
         """The same for all tracers from a HOST array d (numpy, Fortran order, (n, nzm[, ntracers])), synchronous
         (mpdata_plan_level_add[_f32])."""
         n = self._block_n(sl0, n)
-        pd = _host_ptr(d, "d", False, self._dt)
-        self._block_host_shape(d, "d", n)
+        pd = self._block_host(d, "d", (n, self.dims[2] - 1), True)
         _check(getattr(lib(), "mpdata_plan_level_add" + self._sfx)(self._p, int(sl0), n, pd, int(mode)))
 
     def scale_uw(self, su=None, sw=None, sl0=0, n=None):
@@ -760,11 +765,7 @@ class Plan:
     def scale_uw_host(self, su=None, sw=None, sl0=0, n=None):
         """The same from HOST arrays su, sw (numpy, (n,)), synchronous (mpdata_plan_scale_uw[_f32])."""
         n = self._block_n(sl0, n)
-        ptrs = []
-        for name, a in (("su", su), ("sw", sw)):
-            ptrs.append(None if a is None else _host_ptr(a, name, False, self._dt))
-            if a is not None and tuple(a.shape) != (n,):
-                raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {(n,)}")
+        ptrs = [None if a is None else self._block_host(a, name, (n,)) for name, a in (("su", su), ("sw", sw))]
         _check(getattr(lib(), "mpdata_plan_scale_uw" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
     def column_path(self, path, mass=None, sl0=0, n=None, first_tracer=0, ntracers=None):
@@ -776,9 +777,8 @@ class Plan:
         leading axis of a 3-d path (else 1).  Changes nothing of the plan."""
         n = self._block_n(sl0, n)
         nx = self.dims[1]
-        lead = path.dim() == 3
-        ntr = int(ntracers) if ntracers is not None else (int(path.shape[0]) if lead else 1)
-        sh = column_path_shapes(n, nx, ntr if (lead or ntr != 1) else None)
+        ntr, axis = self._block_ntr(path, ntracers)
+        sh = column_path_shapes(n, nx, ntr if axis else None)
         pp = _dev_ptr(path, sh["path"], "path", self._tdt())
         pm = None if mass is None else _dev_ptr(mass, sh["mass"], "mass", self._tdt())
         _check(lib().mpdata_plan_column_path_device(self._p, int(sl0), n, pp, pm, int(first_tracer), ntr))
@@ -787,18 +787,10 @@ class Plan:
         """The same for all tracers into HOST arrays (numpy, Fortran order): path (n, nx[, ntracers]), mass (n[, ntracers]) or
         None, synchronous (mpdata_plan_column_path[_f32])."""
         n = self._block_n(sl0, n)
-        nx, nt = self.dims[1], self.dims[3]
-        ptrs = []
-        for name, a, want in (("path", path, (n, nx)), ("mass", mass, (n,))):
-            if a is None:
-                if name == "path":
-                    raise MpdataError(-1, "column_path_host: path is None")
-                ptrs.append(None)
-                continue
-            ptrs.append(_host_ptr(a, name, True, self._dt))
-            full = want + ((nt,) if nt > 1 else ())
-            if tuple(a.shape) != full and not (nt == 1 and tuple(a.shape) == want + (1,)):
-                raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {full}")
+        if path is None:
+            raise MpdataError(-1, "column_path_host: path is None")
+        ptrs = [None if a is None else self._block_host(a, name, want, True, True)
+                for name, a, want in (("path", path, (n, self.dims[1])), ("mass", mass, (n,)))]
         _check(getattr(lib(), "mpdata_plan_column_path" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
     def diffuse(self, tkh, cx, cz, sb=None, st=None, zflux=None, sl0=0, n=None, first_tracer=0, ntracers=None):
@@ -810,9 +802,8 @@ class Plan:
         Windowed plans: MpdataError (EUNSUPPORTED)."""
         n = self._block_n(sl0, n)
         nx, nz = self.dims[1], self.dims[2]
-        lead = zflux is not None and zflux.dim() == 3
-        ntr = int(ntracers) if ntracers is not None else (int(zflux.shape[0]) if lead else 1)
-        sh = diffuse_shapes(n, nx, nz, ntr if (lead or ntr != 1) else None)
+        ntr, axis = self._block_ntr(zflux, ntracers)
+        sh = diffuse_shapes(n, nx, nz, ntr if axis else None)
         ptrs = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt())
                 for k, t in (("tkh", tkh), ("cx", cx), ("cz", cz), ("sb", sb), ("st", st), ("zflux", zflux))]
         _check(lib().mpdata_plan_diffuse_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
@@ -821,17 +812,11 @@ class Plan:
         """The same for all tracers from HOST arrays (numpy, Fortran order): tkh (n, nx+2, nzm), cx, cz (n, nzm), sb, st
         (n, nx) or None, zflux (n, nz[, ntracers]) or None (written), synchronous (mpdata_plan_diffuse[_f32])."""
         n = self._block_n(sl0, n)
-        nx, nz, nt = self.dims[1], self.dims[2], self.dims[3]
-        ptrs = []
-        for name, a, want, wr in (("tkh", tkh, (n, nx + 2, nz - 1), False), ("cx", cx, (n, nz - 1), False), ("cz", cz, (n, nz - 1), False),
-                                  ("sb", sb, (n, nx), False), ("st", st, (n, nx), False),
-                                  ("zflux", zflux, (n, nz) + ((nt,) if nt > 1 else ()), True)):
-            if a is None:
-                ptrs.append(None)
-                continue
-            ptrs.append(_host_ptr(a, name, wr, self._dt))
-            if tuple(a.shape) != want and not (name == "zflux" and nt == 1 and tuple(a.shape) == want + (1,)):
-                raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {want}")
+        nx, nz = self.dims[1], self.dims[2]
+        ptrs = [None if a is None else self._block_host(a, name, want, out, out)   # (zflux: the tracer axis, and written)
+                for name, a, want, out in (("tkh", tkh, (n, nx + 2, nz - 1), False), ("cx", cx, (n, nz - 1), False),
+                                           ("cz", cz, (n, nz - 1), False), ("sb", sb, (n, nx), False), ("st", st, (n, nx), False),
+                                           ("zflux", zflux, (n, nz), True))]
         _check(getattr(lib(), "mpdata_plan_diffuse" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
     def subside(self, cb, cc, dsum=None, sl0=0, n=None, first_tracer=0, ntracers=None):
@@ -843,11 +828,10 @@ class Plan:
         3-d dsum (else 1).  Windowed plans are supported."""
         n = self._block_n(sl0, n)
         nzm = self.dims[2] - 1
-        lead = dsum is not None and dsum.dim() == 3
-        ntr = int(ntracers) if ntracers is not None else (int(dsum.shape[0]) if lead else 1)
+        ntr, axis = self._block_ntr(dsum, ntracers)
         pb = _dev_ptr(cb, (nzm, n), "cb", self._tdt())
         pc = _dev_ptr(cc, (nzm, n), "cc", self._tdt())
-        pd = None if dsum is None else _dev_ptr(dsum, ((ntr,) if (lead or ntr != 1) else ()) + (nzm, n), "dsum", self._tdt())
+        pd = None if dsum is None else _dev_ptr(dsum, ((ntr,) if axis else ()) + (nzm, n), "dsum", self._tdt())
         _check(lib().mpdata_plan_subside_device(self._p, int(sl0), n, pb, pc, pd, int(first_tracer), ntr))
 
     def subside_host(self, cb, cc, dsum=None, sl0=0, n=None):
@@ -855,16 +839,8 @@ class Plan:
         None (written), synchronous (mpdata_plan_subside[_f32])."""
         n = self._block_n(sl0, n)
         nzm = self.dims[2] - 1
-        ptrs = []
-        for name, a in (("cb", cb), ("cc", cc)):
-            ptrs.append(_host_ptr(a, name, False, self._dt))
-            if tuple(a.shape) != (n, nzm):
-                raise MpdataError(-1, f"{name}: shape {tuple(a.shape)} != expected {(n, nzm)}")
-        if dsum is None:
-            ptrs.append(None)
-        else:
-            ptrs.append(_host_ptr(dsum, "dsum", True, self._dt))
-            self._block_host_shape(dsum, "dsum", n)
+        ptrs = [self._block_host(cb, "cb", (n, nzm)), self._block_host(cc, "cc", (n, nzm)),
+                None if dsum is None else self._block_host(dsum, "dsum", (n, nzm), True, True)]
         _check(getattr(lib(), "mpdata_plan_subside" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
     def shard_plan(self, g):

@@ -3,6 +3,9 @@
 // choice, the staggered device arena, the reference-layout launch (advect_device), device guards.
 //   mpdata_core.hip      errors, settings, tile choice, reference-layout device calls, device utilities
 //   mpdata_plan.hip      plans (device state in the library's own layout), run / run_uw dispatch, multi-GPU handles
+//   mpdata_plan_blocks.hip  the calls on a block of instances of a resident plan (3g .. 3m), host side: checks, dispatch
+//                        on the layout, staging of the host forms; shares struct mpdata_plan with mpdata_plan.hip
+//                        through mpdata_plan_priv.h; the kernels: mpdata_stats.hip .. mpdata_subside.hip (mpdata_wm_walk.h)
 //   mpdata_hostcall.hip  the host-array calls (chunked, pipelined H2D / kernel / D2H)
 //   mpdata_multi.hip     multi-GPU orchestration on top of single-device plans;   mpdata_diag.hip  stream ceilings
 #ifndef MPDATA_INTERNAL_H

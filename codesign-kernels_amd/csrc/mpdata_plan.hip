@@ -1,4 +1,5 @@
-// mpdata_plan.hip -- plans: the device-resident state of one problem behind the C-ABI (include/mpdata_hip.h 3).
+// mpdata_plan.hip -- plans: the device-resident state of one problem behind the C-ABI (include/mpdata_hip.h 3; the calls on
+// a block of instances, 3g .. 3m, are in mpdata_plan_blocks.hip).
 // A plan owns the device state of one problem (what the OpenACC `enter data pcreate` of the
 // reference does, :105, :280, :662) on the device that was current when it was created; every
 // plan call switches to that device and back.  Variant and layout are fixed at creation.
@@ -13,14 +14,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "mpdata_courant.h"
-#include "mpdata_column_path.h"
-#include "mpdata_diffuse.h"
-#include "mpdata_internal.h"
-#include "mpdata_level_add.h"
-#include "mpdata_scale_uw.h"
-#include "mpdata_stats.h"
-#include "mpdata_subside.h"
+#include "mpdata_plan_priv.h"
 #include "mpdata_windows.h"
 
 using namespace mpd;
@@ -62,62 +56,8 @@ __global__ void __launch_bounds__(256) flux_finish_kernel(R2* flux, const R2* pa
 
 }  // namespace
 
-struct mpdata_plan {
-  int64_t ncrms;
-  int nx, nz, ntracers;
-  int eb;        // bytes per real: 8 (fp64 plan) or 4 (fp32 plan)
-  int device;    // the plan's device
-  int variant;   // MPDATA_VARIANT_* at creation
-  int layout;    // MPDATA_LAYOUT_*
-  Sizes sz;      // element counts of the reference-layout arrays
-  // reference-layout plans
-  Arena arena;
-  void *f, *u, *w, *rho, *rhow, *adz, *flux;  // = arena.p[0..6]
-  // wave-major plans
-  int lps, slp, wpb, ntiles;
-  int64_t wm_ncrms;  // instances as the wave-major side sees them: ncrms (fp64) or (ncrms + 1) / 2 pairs (fp32)
-  // fp32 plans with an odd ncrms (include/mpdata_hip.h 3f): the upper half of the last pair is a phantom.  INVARIANT: in
-  // every plan array it is a copy of instance ncrms - 1, and the padding pairs of the last tile are copies of that pair.
-  // Whole imports keep it themselves (mpdata_layout_convert_odd); plan_phantom restores it behind everything else that
-  // replaces instance ncrms - 1.  No export reads it.
-  bool odd;
-  long long chunk, tile_elems, main_e;   // main_e: elements of the line-aligned part of a column chunk
-  void *pf, *pu, *pw, *pkc, *pflux;  // private arrays
-  void* stage;                       // reference-layout staging: one tracer of f (or u, w)
-  size_t stage_elems;
-  void* bstage;                      // staging of mpdata_plan_download_instances: f and flux of one block (grown on demand)
-  size_t bstage_bytes;
-  void* dbuf;                        // mpdata_plan_diffuse_device: tkh in the plan layout (wave-major plans), the new interior
-  size_t dbuf_bytes;                 // of the block (reference-layout plans, mpdata_plan_subside_device too); grown on demand
-  void* flux_ref;                    // flux in the reference layout (level nz is carried through)
-  void* wpark;                       // EXACT: park array of the limited vertical fluxes (bit-identical flux); with park_regs
-  size_t wpark_bytes;                // only mpdata_plan_run_uw needs it: allocated by its first call
-  bool park_regs;                    // EXACT, nx <= MPDATA_WM_NPK: mpdata_plan_run parks in registers (no park array)
-  hipStream_t stream;
-  bool own_stream;
-  hipEvent_t ev0, ev1;
-  bool uploaded, ran;
-  bool have_u, have_w;   // the plan holds velocities (imported since the last mpdata_plan_run_uw)
-  bool timing;     // record the event pair around every run (mpdata_plan_last_kernel_ms); mpdata_plan_set_timing
-  unsigned runs;   // launches so far (serpentine tile order)
-  int boundary;    // MPDATA_BOUNDARY_* (mpdata_plan_set_boundary)
-  // per tracer: f's halo columns hold copies of its interior (set by the halo kernel; cleared by an import of f and
-  // by every run, whose kernels leave first-pass values there)
-  unsigned char* halo_ok;
-  // windowed plans (include/mpdata_hip.h 3e; nz > 238): `inner` is an ordinary wave-major plan whose ncrms * W instances
-  // are the W level windows (mpdata_windows.h) of this plan's instances, window index fastest.  It runs on this plan's
-  // stream with this plan's boundary mode and shares halo_ok; of the fields above this plan itself uses the sizes,
-  // stage (tall reference-layout staging of host transfers), bstage, flux_ref (level nz), the stream, the events
-  // and the state flags.
-  mpdata_plan* inner;
-  int W;
-  // per tracer: every non-owned level of every window of f holds its owner's value (set by a whole import of f and by
-  // the seam refresh; cleared by every run, which leaves the 3 + 3 margin levels of a seam wrong)
-  unsigned char* seam_ok;
-  mpdata_multi* multi;  // != null: a multi-GPU plan (mpdata_multi.hip); nothing else above is used
-};
-
-namespace {
+// (the helpers mpdata_plan_blocks.hip shares are declared in mpdata_plan_priv.h; the others are static)
+namespace mpd {
 
 // conversion jobs of a wave-major plan: which = 0 f, 1 u, 2 w, 3 rho, 4 rhow, 5 adz, 6 flux
 MpdataLayoutJob wm_job(const mpdata_plan* p, int which, void* ref, int first_tracer, int ntr) {
@@ -155,11 +95,11 @@ MpdataLayoutJob wm_job(const mpdata_plan* p, int which, void* ref, int first_tra
 // lanes per instance of the wave-major kernels; 128 = an instance wider than a wave (65 <= nz <= 238: several waves
 // per instance, mpdata_kernel_wm_body.h "KS"; the layout kernels hold a column of one instance group in LDS: nzm <= 126)
 #define MPDATA_WM_NZ_MAX 238   // 64 + 3 * 58: four windows = the four waves of a workgroup
-int wm_lps_for(int nz) { return nz <= 8 ? 8 : nz <= 16 ? 16 : nz <= 32 ? 32 : nz <= 64 ? 64 : nz <= MPDATA_WM_NZ_MAX ? 128 : 0; }
-int wm_nkw_for(int nz) { return nz <= 64 ? 1 : 1 + (nz - 64 + 57) / 58; }
+static int wm_lps_for(int nz) { return nz <= 8 ? 8 : nz <= 16 ? 16 : nz <= 32 ? 32 : nz <= 64 ? 64 : nz <= MPDATA_WM_NZ_MAX ? 128 : 0; }
+static int wm_nkw_for(int nz) { return nz <= 64 ? 1 : 1 + (nz - 64 + 57) / 58; }
 // nz > 64: lanes of the last window where it is a share of a wave (16: the window needs <= 16 levels, 32: <= 32; else 0 = a
 // wave of its own); MPDATA_KS_TAIL=0: never (A/B)
-int wm_lwt_for(int nz) {
+static int wm_lwt_for(int nz) {
   static const bool off = getenv("MPDATA_KS_TAIL") && !strcmp(getenv("MPDATA_KS_TAIL"), "0");
   if (nz <= 64 || off || wm_nkw_for(nz) != 2) return 0;   // (three windows: a 9-wave workgroup would cap the two-waves-per-SIMD forms' registers)
   const int need = nz - 58 * (wm_nkw_for(nz) - 1);
@@ -167,13 +107,13 @@ int wm_lwt_for(int nz) {
 }
 
 // ---- windowed plans: the inner plan follows the outer one's stream and boundary mode
-mpdata_plan* win_inner(mpdata_plan* p) {
+static mpdata_plan* win_inner(mpdata_plan* p) {
   p->inner->stream = p->stream;
   p->inner->boundary = p->boundary;
   return p->inner;
 }
 // one array of instances [sl0, sl0 + n) between a tall reference-layout array of leading dimension n and the windows
-MpdataWindowJob win_job(const mpdata_plan* p, int which, void* ref, int64_t sl0, int64_t n, int first_tracer, int ntr) {
+static MpdataWindowJob win_job(const mpdata_plan* p, int which, void* ref, int64_t sl0, int64_t n, int first_tracer, int ntr) {
   MpdataWindowJob b;
   b.j = wm_job(p->inner, which, ref, first_tracer, ntr);
   b.j.ref_tstride = which == 0 ? (long long)n * (p->nx + 6) * (p->nz - 1) : which == 6 ? (long long)n * p->nz : 0;
@@ -195,7 +135,7 @@ int tracer_range(const mpdata_plan* p, int first, int count) {
 // The reference-layout staging buffer of a wave-major plan (one tracer of f, or u / w): only host
 // transfers need it, so it is allocated by the first of them (a plan that is only ever fed from
 // device arrays -- bench.py keeps one per field set -- never pays its 538 MB).
-int plan_stage(mpdata_plan* p) {
+static int plan_stage(mpdata_plan* p) {
   if (p->stage) return 0;
   HIP_TRY(hipMalloc(&p->stage, p->stage_elems * p->eb));
   return 0;
@@ -218,8 +158,8 @@ int plan_phantom(mpdata_plan* p, int which, int first, int ntr) {
 // Windowed plans: tall reference-layout arrays of instances [sl0, sl0 + n) (leading dimension n; host arrays: the whole
 // plan only) -> the windows (split: every level every window holds, so a whole import of f leaves fresh seams; after a
 // block import the seams of the plan are as fresh as they were).  flux is also kept tall (level nz).
-int win_import(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w, const void* rho,
-               const void* rhow, const void* adz, const void* flux, int first, int count, bool dev) {
+static int win_import(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w, const void* rho,
+                      const void* rhow, const void* adz, const void* flux, int first, int count, bool dev) {
   const int eb = p->eb;
   const bool whole = n == p->ncrms, last = sl0 + n == p->ncrms;
   const size_t f1 = (size_t)n * (p->nx + 6) * (p->nz - 1);   // elements of one tracer of f
@@ -266,7 +206,7 @@ int win_import(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void
 
 // ... and back (merge: the owned levels of every window; flux level nz from the tall copy).  The caller has wrapped
 // the halos of a periodic plan.
-int win_export(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flux, int first, int count, bool dev) {
+static int win_export(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flux, int first, int count, bool dev) {
   const int eb = p->eb, nz = p->nz, nzm = nz - 1;
   const bool whole = n == p->ncrms;
   const size_t f1 = (size_t)n * (p->nx + 6) * nzm;
@@ -318,8 +258,8 @@ int plan_seams(mpdata_plan* p, int first, int count) {
 
 // Arrays in the reference layout -> the plan.  `dev` says where the pointers live.  Null
 // pointers are skipped (the plan keeps what it has).  f / flux cover `count` tracers.
-int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, const void* rho,
-                const void* rhow, const void* adz, const void* flux, int first, int count, bool dev) {
+static int plan_import(mpdata_plan* p, const void* f, const void* u, const void* w, const void* rho,
+                       const void* rhow, const void* adz, const void* flux, int first, int count, bool dev) {
   const int eb = p->eb;
   const size_t f1 = p->sz.f / p->ntracers;  // elements of one tracer of f
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -416,7 +356,7 @@ int plan_wrap_f(mpdata_plan* p, int first, int count) {
   return 0;
 }
 
-int plan_export(mpdata_plan* p, void* f, void* flux, int first, int count, bool dev) {
+static int plan_export(mpdata_plan* p, void* f, void* flux, int first, int count, bool dev) {
   const int eb = p->eb;
   if (f) {   // (periodic plans hand out wrapped halos)
     const int rc = plan_wrap_f(p, first, count);
@@ -476,8 +416,8 @@ MpdataBlockJob wm_block_job(const mpdata_plan* p, int which, void* ref, int64_t 
   return b;
 }
 
-int plan_import_block(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w, const void* rho,
-                      const void* rhow, const void* adz, const void* flux, int first, int count) {
+static int plan_import_block(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, const void* u, const void* w, const void* rho,
+                             const void* rhow, const void* adz, const void* flux, int first, int count) {
   const int eb = p->eb, nx = p->nx, nz = p->nz, nzm = nz - 1;
   if (p->inner) return win_import(p, sl0, n, f, u, w, rho, rhow, adz, flux, first, count, true);
   if (f) memset(p->halo_ok + first, 0, (size_t)count);   // (as a whole import: a periodic plan wraps these tracers again)
@@ -516,7 +456,7 @@ int plan_import_block(mpdata_plan* p, int64_t sl0, int64_t n, const void* f, con
 }
 
 // f, flux: device arrays of the block
-int plan_export_block(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flux, int first, int count) {
+static int plan_export_block(mpdata_plan* p, int64_t sl0, int64_t n, void* f, void* flux, int first, int count) {
   const int eb = p->eb, nx = p->nx, nz = p->nz, nzm = nz - 1;
   auto slab = [&](void* dst, const void* src, long long rows) -> int {
     HIP_TRY(mpdata_layout_copy_rows(dst, (const char*)src + (size_t)sl0 * eb, eb, n, rows, n, p->ncrms, p->stream));
@@ -573,36 +513,8 @@ int plan_bstage(mpdata_plan* p, size_t need) {
   p->bstage_bytes = need;
   return 0;
 }
-// the plan's diffusion buffer (mpdata_plan_diffuse_device), grown as the block staging buffer is
-int plan_dbuf(mpdata_plan* p, size_t need) {
-  if (p->dbuf_bytes >= need) return 0;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  if (p->dbuf) (void)hipFree(p->dbuf);
-  p->dbuf = nullptr; p->dbuf_bytes = 0;
-  HIP_TRY(hipMalloc(&p->dbuf, need));
-  p->dbuf_bytes = need;
-  return 0;
-}
-// a block of a plan for the kernels that walk its plan layout (mpdata_wm_walk.h), with wm_plan(p) the plan the layout
-// jobs are made of: a windowed plan's inner plan, read and rewritten where it lies (its stream and boundary are not
-// forwarded: nothing of it runs)
-MpdataBlockSel block_sel(const mpdata_plan* p, int64_t sl0, int64_t n) {
-  MpdataBlockSel b;
-  b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
-  b.W = p->inner ? p->W : 1; b.nz = p->nz;
-  return b;
-}
-const mpdata_plan* wm_plan(const mpdata_plan* p) { return p->inner ? p->inner : p; }
-// the state a call on the plan's velocities needs: filled once, and the arrays asked for still held
-int plan_uw_state(const char* what, const mpdata_plan* p, bool need_u, bool need_w) {
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
-  if ((need_u && !p->have_u) || (need_w && !p->have_w))
-    return set_err(MPDATA_ESTATE, "%s: the plan does not hold %s (mpdata_plan_run_uw used them up: import u and w)", what,
-                   (need_u && !p->have_u) ? "u" : "w");
-  return 0;
-}
 
-}  // namespace
+}  // namespace mpd
 
 extern "C" {
 
@@ -887,645 +799,6 @@ int mpdata_plan_download_instances(mpdata_plan* p, int64_t sl0, int64_t n, doubl
 }
 int mpdata_plan_download_instances_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* f, float* flux) {
   return plan_download_block(p, sl0, n, f, flux, 4);
-}
-
-// ---- 3g: horizontal sum / min / max per level of f.  Reads f, writes the outputs: no flag of the plan is touched (the
-// halo and seam marks stay -- halo columns are not read, owned levels are right whatever the seams hold), no event is
-// recorded, and a windowed plan's inner plan is read where it lies (its stream and boundary are not forwarded: nothing
-// of it runs).
-static int plan_level_stats(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int first, int count) {
-  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
-    MpdataStatsJob b;
-    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
-    b.sel = block_sel(p, sl0, n);
-    b.sum = sum; b.mn = mn; b.mx = mx;
-    HIP_TRY(mpdata_stats_wm(b, p->stream));
-  } else {
-    const size_t f1 = p->sz.f / p->ntracers;
-    HIP_TRY(mpdata_stats_ref((const char*)p->f + (size_t)first * f1 * p->eb, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, sum, mn, mx,
-                             p->stream));
-  }
-  return 0;
-}
-int mpdata_plan_level_stats_device(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int first_tracer,
-                                   int ntracers) {
-  int rc = block_range("mpdata_plan_level_stats_device", p, sl0, n);
-  if (rc) return rc;
-  rc = tracer_range(p, first_tracer, ntracers);
-  if (rc) return rc;
-  if (!sum && !mn && !mx) return set_err(MPDATA_EINVAL, "mpdata_plan_level_stats_device: sum, min and max are all NULL");
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_stats_device before upload / import");
-  DevGuard g(p->device);
-  return plan_level_stats(p, sl0, n, sum, mn, mx, first_tracer, ntracers);
-}
-// host arrays, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
-static int plan_level_stats_host(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int eb) {
-  int rc = block_range("mpdata_plan_level_stats", p, sl0, n);
-  if (rc) return rc;
-  if (!sum && !mn && !mx) return set_err(MPDATA_EINVAL, "mpdata_plan_level_stats: sum, min and max are all NULL");
-  rc = plan_check(p, eb);
-  if (rc) return rc;
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_stats before upload / import");
-  DevGuard g(p->device);
-  const size_t one = (size_t)n * (p->nz - 1) * p->ntracers * eb;
-  void* host[3] = {sum, mn, mx};
-  size_t need = 0;
-  for (void* h : host) need += h ? one : 0;
-  rc = plan_bstage(p, need);
-  if (rc) return rc;
-  void* dev[3] = {nullptr, nullptr, nullptr};
-  size_t off = 0;
-  for (int i = 0; i < 3; ++i)
-    if (host[i]) { dev[i] = (char*)p->bstage + off; off += one; }
-  rc = plan_level_stats(p, sl0, n, dev[0], dev[1], dev[2], 0, p->ntracers);
-  if (rc) return rc;
-  for (int i = 0; i < 3; ++i)
-    if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], one, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return 0;
-}
-int mpdata_plan_level_stats(mpdata_plan* p, int64_t sl0, int64_t n, double* sum, double* mn, double* mx) {
-  return plan_level_stats_host(p, sl0, n, sum, mn, mx, 8);
-}
-int mpdata_plan_level_stats_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* sum, float* mn, float* mx) {
-  return plan_level_stats_host(p, sl0, n, sum, mn, mx, 4);
-}
-// the same reduction on a reference-layout device array (arguments checked before any device call)
-static int level_stats_array(int64_t ncrms, int nx, int nz, int ntracers, const void* f, void* sum, void* mn, void* mx, void* stream,
-                             int eb) {
-  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
-    return set_err(MPDATA_EINVAL, "mpdata_level_stats_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
-                   (long long)ncrms, nx, nz, ntracers);
-  if (!f) return set_err(MPDATA_EINVAL, "mpdata_level_stats_device: null f");
-  if (!sum && !mn && !mx) return set_err(MPDATA_EINVAL, "mpdata_level_stats_device: sum, min and max are all NULL");
-  HIP_TRY(mpdata_stats_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, sum, mn, mx, (hipStream_t)stream));
-  return 0;
-}
-int mpdata_level_stats_device(int64_t ncrms, int nx, int nz, int ntracers, const double* f, double* sum, double* mn, double* mx,
-                              void* stream) {
-  return level_stats_array(ncrms, nx, nz, ntracers, f, sum, mn, mx, stream, 8);
-}
-int mpdata_level_stats_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, float* sum, float* mn, float* mx,
-                                  void* stream) {
-  return level_stats_array(ncrms, nx, nz, ntracers, f, sum, mn, mx, stream, 4);
-}
-
-// ---- 3h: outflow Courant number of the plan's velocities per level (clev) and per instance (cinst).  Reads u, w, rho,
-// adz, writes the outputs: as the level statistics above no flag of the plan is touched, no event is recorded, and a
-// windowed plan's inner plan is read where it lies.
-static int plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst) {
-  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
-    const mpdata_plan* q = wm_plan(p);
-    const MpdataLayoutJob jr = wm_job(q, 3, nullptr, 0, 1), ja = wm_job(q, 5, nullptr, 0, 1);
-    MpdataCourantJob b;
-    b.j = wm_job(q, 1, nullptr, 0, 1);
-    b.w = wm_job(q, 2, nullptr, 0, 1).prv;
-    b.rho = (const double*)jr.prv + jr.prv_col0 * jr.chunk;
-    b.adz = (const double*)ja.prv + ja.prv_col0 * ja.chunk;
-    b.kc_tile_stride = jr.prv_tile_stride;
-    b.sel = block_sel(p, sl0, n);
-    b.clev = clev; b.cinst = cinst;
-    HIP_TRY(mpdata_courant_wm(b, p->stream));
-  } else {
-    HIP_TRY(mpdata_courant_ref(p->u, p->w, p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, p->nz, clev, cinst, p->stream));
-  }
-  return 0;
-}
-int mpdata_plan_courant_device(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst) {
-  int rc = block_range("mpdata_plan_courant_device", p, sl0, n);
-  if (rc) return rc;
-  if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_plan_courant_device: clev and cinst are both NULL");
-  rc = plan_uw_state("mpdata_plan_courant_device", p, true, true);
-  if (rc) return rc;
-  DevGuard g(p->device);
-  return plan_courant(p, sl0, n, clev, cinst);
-}
-// host arrays, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
-static int plan_courant_host(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst, int eb) {
-  int rc = block_range("mpdata_plan_courant", p, sl0, n);
-  if (rc) return rc;
-  if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_plan_courant: clev and cinst are both NULL");
-  rc = plan_check(p, eb);
-  if (rc) return rc;
-  rc = plan_uw_state("mpdata_plan_courant", p, true, true);
-  if (rc) return rc;
-  DevGuard g(p->device);
-  const size_t lb = clev ? (size_t)n * (p->nz - 1) * eb : 0, ib = cinst ? (size_t)n * eb : 0;
-  rc = plan_bstage(p, lb + ib);
-  if (rc) return rc;
-  void* dl = clev ? p->bstage : nullptr;
-  void* di = cinst ? (char*)p->bstage + lb : nullptr;
-  rc = plan_courant(p, sl0, n, dl, di);
-  if (rc) return rc;
-  if (clev) HIP_TRY(hipMemcpyAsync(clev, dl, lb, hipMemcpyDeviceToHost, p->stream));
-  if (cinst) HIP_TRY(hipMemcpyAsync(cinst, di, ib, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return 0;
-}
-int mpdata_plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, double* clev, double* cinst) {
-  return plan_courant_host(p, sl0, n, clev, cinst, 8);
-}
-int mpdata_plan_courant_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* clev, float* cinst) {
-  return plan_courant_host(p, sl0, n, clev, cinst, 4);
-}
-// the same reduction on reference-layout device arrays (arguments checked before any device call)
-static int courant_array(int64_t ncrms, int nx, int nz, const void* u, const void* w, const void* rho, const void* adz, void* clev,
-                         void* cinst, void* stream, int eb) {
-  if (ncrms < 1 || nx < 1 || nz < 2)
-    return set_err(MPDATA_EINVAL, "mpdata_courant_device: bad sizes ncrms=%lld nx=%d nz=%d (need >=1,>=1,>=2)", (long long)ncrms, nx, nz);
-  if (!u || !w || !rho || !adz)
-    return set_err(MPDATA_EINVAL, "mpdata_courant_device: null %s", !u ? "u" : !w ? "w" : !rho ? "rho" : "adz");
-  if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_courant_device: clev and cinst are both NULL");
-  HIP_TRY(mpdata_courant_ref(u, w, rho, adz, eb, ncrms, 0, ncrms, nx, nz, clev, cinst, (hipStream_t)stream));
-  return 0;
-}
-int mpdata_courant_device(int64_t ncrms, int nx, int nz, const double* u, const double* w, const double* rho, const double* adz,
-                          double* clev, double* cinst, void* stream) {
-  return courant_array(ncrms, nx, nz, u, w, rho, adz, clev, cinst, stream, 8);
-}
-int mpdata_courant_f32_device(int64_t ncrms, int nx, int nz, const float* u, const float* w, const float* rho, const float* adz,
-                              float* clev, float* cinst, void* stream) {
-  return courant_array(ncrms, nx, nz, u, w, rho, adz, clev, cinst, stream, 4);
-}
-
-// ---- 3i: per-level increments of f, in place.  Reads d, rewrites f on every column slot of the block's instances: no
-// flag of the plan is touched and no event is recorded.  The hidden invariants hold by construction, not by a refresh:
-//   halo marks  the increment is uniform in i, so halo columns that are wrapped copies stay wrapped copies (same bits in,
-//               same operation) and stale ones stay stale -- halo_ok is right as it stands;
-//   seam marks  every level a window stores takes the increment of the tall level it stands for, so fresh seams stay
-//               fresh and stale ones stay stale -- seam_ok is right as it stands;
-//   phantom     follows the plan's last instance inside the kernel (mpdata_level_add.h).
-// A windowed plan's inner plan is rewritten where it lies (its stream and boundary are not forwarded: nothing of it runs).
-static int plan_level_add(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int first, int count) {
-  const int clip = mode == MPDATA_LEVEL_ADD_CLIP;
-  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
-    MpdataLevelAddJob b;
-    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
-    b.sel = block_sel(p, sl0, n);
-    b.d = d; b.clip = clip;
-    HIP_TRY(mpdata_level_add_wm(b, p->stream));
-  } else {
-    const size_t f1 = p->sz.f / p->ntracers;
-    HIP_TRY(mpdata_level_add_ref((char*)p->f + (size_t)first * f1 * p->eb, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, d, clip,
-                                 p->stream));
-  }
-  return 0;
-}
-static int level_add_mode(const char* what, int mode) {
-  if (mode != MPDATA_LEVEL_ADD && mode != MPDATA_LEVEL_ADD_CLIP) return set_err(MPDATA_EINVAL, "%s: unknown mode %d", what, mode);
-  return 0;
-}
-int mpdata_plan_level_add_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int first_tracer, int ntracers) {
-  int rc = block_range("mpdata_plan_level_add_device", p, sl0, n);
-  if (rc) return rc;
-  rc = tracer_range(p, first_tracer, ntracers);
-  if (rc) return rc;
-  if (!d) return set_err(MPDATA_EINVAL, "mpdata_plan_level_add_device: null d");
-  rc = level_add_mode("mpdata_plan_level_add_device", mode);
-  if (rc) return rc;
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_add_device before upload / import");
-  DevGuard g(p->device);
-  return plan_level_add(p, sl0, n, d, mode, first_tracer, ntracers);
-}
-// host d, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
-static int plan_level_add_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int eb) {
-  int rc = block_range("mpdata_plan_level_add", p, sl0, n);
-  if (rc) return rc;
-  if (!d) return set_err(MPDATA_EINVAL, "mpdata_plan_level_add: null d");
-  rc = level_add_mode("mpdata_plan_level_add", mode);
-  if (rc) return rc;
-  rc = plan_check(p, eb);
-  if (rc) return rc;
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_level_add before upload / import");
-  DevGuard g(p->device);
-  const size_t need = (size_t)n * (p->nz - 1) * p->ntracers * eb;
-  rc = plan_bstage(p, need);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(p->bstage, d, need, hipMemcpyHostToDevice, p->stream));
-  rc = plan_level_add(p, sl0, n, p->bstage, mode, 0, p->ntracers);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return 0;
-}
-int mpdata_plan_level_add(mpdata_plan* p, int64_t sl0, int64_t n, const double* d, int mode) {
-  return plan_level_add_host(p, sl0, n, d, mode, 8);
-}
-int mpdata_plan_level_add_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* d, int mode) {
-  return plan_level_add_host(p, sl0, n, d, mode, 4);
-}
-// the same on a reference-layout device array (arguments checked before any device call)
-static int level_add_array(int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* d, int mode, void* stream, int eb) {
-  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
-    return set_err(MPDATA_EINVAL, "mpdata_level_add_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
-                   (long long)ncrms, nx, nz, ntracers);
-  if (!f || !d) return set_err(MPDATA_EINVAL, "mpdata_level_add_device: null %s", !f ? "f" : "d");
-  const int rc = level_add_mode("mpdata_level_add_device", mode);
-  if (rc) return rc;
-  HIP_TRY(mpdata_level_add_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, d, mode == MPDATA_LEVEL_ADD_CLIP, (hipStream_t)stream));
-  return 0;
-}
-int mpdata_level_add_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* d, int mode, void* stream) {
-  return level_add_array(ncrms, nx, nz, ntracers, f, d, mode, stream, 8);
-}
-int mpdata_level_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* d, int mode, void* stream) {
-  return level_add_array(ncrms, nx, nz, ntracers, f, d, mode, stream, 4);
-}
-
-// ---- 3j: one factor per instance on the plan's u and / or w, in place.  Reads su, sw, rewrites every column and level
-// the plan stores of the block's instances: no flag of the plan is touched and no event is recorded.  f, flux, rho, rhow,
-// adz are not looked at, so halo and seam marks are right as they stand; every window of an instance and every level it
-// stores takes the instance's factor, so all stored copies of a tall level change alike; the phantom half follows the
-// plan's last instance inside the kernel (mpdata_scale_uw.h).  A windowed plan's inner plan is rewritten where it lies.
-static int plan_scale_uw(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw) {
-  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
-    const mpdata_plan* q = wm_plan(p);
-    MpdataScaleUwJob b;
-    b.sel = block_sel(p, sl0, n);
-    if (su) { b.j = wm_job(q, 1, nullptr, 0, 1); b.s = su; HIP_TRY(mpdata_scale_uw_wm(b, p->stream)); }
-    if (sw) { b.j = wm_job(q, 2, nullptr, 0, 1); b.s = sw; HIP_TRY(mpdata_scale_uw_wm(b, p->stream)); }
-  } else {
-    if (su) HIP_TRY(mpdata_scale_uw_ref(p->u, p->eb, p->ncrms, sl0, n, p->nx + 5, p->nz - 1, su, p->stream));
-    if (sw) HIP_TRY(mpdata_scale_uw_ref(p->w, p->eb, p->ncrms, sl0, n, p->nx + 4, p->nz, sw, p->stream));
-  }
-  return 0;
-}
-int mpdata_plan_scale_uw_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw) {
-  int rc = block_range("mpdata_plan_scale_uw_device", p, sl0, n);
-  if (rc) return rc;
-  if (!su && !sw) return set_err(MPDATA_EINVAL, "mpdata_plan_scale_uw_device: su and sw are both NULL");
-  rc = plan_uw_state("mpdata_plan_scale_uw_device", p, su != nullptr, sw != nullptr);
-  if (rc) return rc;
-  DevGuard g(p->device);
-  return plan_scale_uw(p, sl0, n, su, sw);
-}
-// host factors, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
-static int plan_scale_uw_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw, int eb) {
-  int rc = block_range("mpdata_plan_scale_uw", p, sl0, n);
-  if (rc) return rc;
-  if (!su && !sw) return set_err(MPDATA_EINVAL, "mpdata_plan_scale_uw: su and sw are both NULL");
-  rc = plan_check(p, eb);
-  if (rc) return rc;
-  rc = plan_uw_state("mpdata_plan_scale_uw", p, su != nullptr, sw != nullptr);
-  if (rc) return rc;
-  DevGuard g(p->device);
-  const size_t one = (size_t)n * eb, need = 2 * one;
-  rc = plan_bstage(p, need);
-  if (rc) return rc;
-  void* du = su ? p->bstage : nullptr;
-  void* dw = sw ? (char*)p->bstage + one : nullptr;
-  if (su) HIP_TRY(hipMemcpyAsync(du, su, one, hipMemcpyHostToDevice, p->stream));
-  if (sw) HIP_TRY(hipMemcpyAsync(dw, sw, one, hipMemcpyHostToDevice, p->stream));
-  rc = plan_scale_uw(p, sl0, n, du, dw);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return 0;
-}
-int mpdata_plan_scale_uw(mpdata_plan* p, int64_t sl0, int64_t n, const double* su, const double* sw) {
-  return plan_scale_uw_host(p, sl0, n, su, sw, 8);
-}
-int mpdata_plan_scale_uw_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* su, const float* sw) {
-  return plan_scale_uw_host(p, sl0, n, su, sw, 4);
-}
-// the same on reference-layout device arrays (arguments checked before any device call)
-static int scale_uw_array(int64_t ncrms, int nx, int nz, void* u, void* w, const void* su, const void* sw, void* stream, int eb) {
-  if (ncrms < 1 || nx < 1 || nz < 2)
-    return set_err(MPDATA_EINVAL, "mpdata_scale_uw_device: bad sizes ncrms=%lld nx=%d nz=%d (need >=1,>=1,>=2)", (long long)ncrms, nx, nz);
-  if (!u && !w) return set_err(MPDATA_EINVAL, "mpdata_scale_uw_device: u and w are both NULL");
-  if (!u != !su || !w != !sw)
-    return set_err(MPDATA_EINVAL, "mpdata_scale_uw_device: %s without %s", !u != !su ? (u ? "u" : "su") : (w ? "w" : "sw"),
-                   !u != !su ? (u ? "su" : "u") : (w ? "sw" : "w"));
-  if (u) HIP_TRY(mpdata_scale_uw_ref(u, eb, ncrms, 0, ncrms, nx + 5, nz - 1, su, (hipStream_t)stream));
-  if (w) HIP_TRY(mpdata_scale_uw_ref(w, eb, ncrms, 0, ncrms, nx + 4, nz, sw, (hipStream_t)stream));
-  return 0;
-}
-int mpdata_scale_uw_device(int64_t ncrms, int nx, int nz, double* u, double* w, const double* su, const double* sw, void* stream) {
-  return scale_uw_array(ncrms, nx, nz, u, w, su, sw, stream, 8);
-}
-int mpdata_scale_uw_f32_device(int64_t ncrms, int nx, int nz, float* u, float* w, const float* su, const float* sw, void* stream) {
-  return scale_uw_array(ncrms, nx, nz, u, w, su, sw, stream, 4);
-}
-
-// ---- 3k: mass-weighted column integrals of f per interior column (path) and their sum over the columns (mass).  Reads f,
-// rho, adz, writes the outputs: as the level statistics no flag of the plan is touched (halo columns are not read, owned
-// levels are right whatever the seams hold), no event is recorded, and a windowed plan's inner plan is read where it
-// lies.  The velocities are not looked at: the plan need not hold any.
-static int plan_column_path(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int first, int count) {
-  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
-    const mpdata_plan* q = wm_plan(p);
-    const MpdataLayoutJob jr = wm_job(q, 3, nullptr, 0, 1), ja = wm_job(q, 5, nullptr, 0, 1);
-    MpdataColumnPathJob b;
-    b.j = wm_job(q, 0, nullptr, first, count);
-    b.rho = (const double*)jr.prv + jr.prv_col0 * jr.chunk;
-    b.adz = (const double*)ja.prv + ja.prv_col0 * ja.chunk;
-    b.kc_tile_stride = jr.prv_tile_stride;
-    b.sel = block_sel(p, sl0, n);
-    b.path = path; b.mass = mass;
-    HIP_TRY(mpdata_column_path_wm(b, p->stream));
-  } else {
-    const size_t f1 = p->sz.f / p->ntracers;
-    HIP_TRY(mpdata_column_path_ref((const char*)p->f + (size_t)first * f1 * p->eb, p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx,
-                                   p->nz - 1, count, path, mass, p->stream));
-  }
-  return 0;
-}
-int mpdata_plan_column_path_device(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int first_tracer, int ntracers) {
-  int rc = block_range("mpdata_plan_column_path_device", p, sl0, n);
-  if (rc) return rc;
-  rc = tracer_range(p, first_tracer, ntracers);
-  if (rc) return rc;
-  if (!path) return set_err(MPDATA_EINVAL, "mpdata_plan_column_path_device: null path");
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_column_path_device before upload / import");
-  DevGuard g(p->device);
-  return plan_column_path(p, sl0, n, path, mass, first_tracer, ntracers);
-}
-// host arrays, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
-static int plan_column_path_host(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int eb) {
-  int rc = block_range("mpdata_plan_column_path", p, sl0, n);
-  if (rc) return rc;
-  if (!path) return set_err(MPDATA_EINVAL, "mpdata_plan_column_path: null path");
-  rc = plan_check(p, eb);
-  if (rc) return rc;
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "mpdata_plan_column_path before upload / import");
-  DevGuard g(p->device);
-  const size_t pb = (size_t)n * p->nx * p->ntracers * eb, mb = mass ? (size_t)n * p->ntracers * eb : 0;
-  rc = plan_bstage(p, pb + mb);
-  if (rc) return rc;
-  void* dp = p->bstage;
-  void* dm = mass ? (char*)p->bstage + pb : nullptr;
-  rc = plan_column_path(p, sl0, n, dp, dm, 0, p->ntracers);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(path, dp, pb, hipMemcpyDeviceToHost, p->stream));
-  if (mass) HIP_TRY(hipMemcpyAsync(mass, dm, mb, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return 0;
-}
-int mpdata_plan_column_path(mpdata_plan* p, int64_t sl0, int64_t n, double* path, double* mass) {
-  return plan_column_path_host(p, sl0, n, path, mass, 8);
-}
-int mpdata_plan_column_path_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* path, float* mass) {
-  return plan_column_path_host(p, sl0, n, path, mass, 4);
-}
-// the same on reference-layout device arrays (arguments checked before any device call)
-static int column_path_array(int64_t ncrms, int nx, int nz, int ntracers, const void* f, const void* rho, const void* adz, void* path,
-                             void* mass, void* stream, int eb) {
-  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
-    return set_err(MPDATA_EINVAL, "mpdata_column_path_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
-                   (long long)ncrms, nx, nz, ntracers);
-  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_column_path_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
-  if (!path) return set_err(MPDATA_EINVAL, "mpdata_column_path_device: null path");
-  HIP_TRY(mpdata_column_path_ref(f, rho, adz, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, path, mass, (hipStream_t)stream));
-  return 0;
-}
-int mpdata_column_path_device(int64_t ncrms, int nx, int nz, int ntracers, const double* f, const double* rho, const double* adz,
-                              double* path, double* mass, void* stream) {
-  return column_path_array(ncrms, nx, nz, ntracers, f, rho, adz, path, mass, stream, 8);
-}
-int mpdata_column_path_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, const float* rho, const float* adz,
-                                  float* path, float* mass, void* stream) {
-  return column_path_array(ncrms, nx, nz, ntracers, f, rho, adz, path, mass, stream, 4);
-}
-
-// ---- 3l: eddy diffusion of f, in place.  Reads tkh, cx, cz, sb, st and the plan's rho and adz, rewrites the interior
-// columns of f of the block's instances and the tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not
-// touched and no event is recorded.  The halo columns 0 and nx+1 are inputs: a periodic plan wraps stale halos first, as a
-// run does, and afterwards its halos are copies of the OLD interior, so the marks of the range are cleared and the next
-// run or read-back wraps again.  Wave-major plans: tkh is brought into the plan layout once per call by the conversion
-// kernels of an import of f -- the block's for a block, the whole import's for the whole plan -- (a job of nx + 2 columns
-// at column slot 2 into the plan's diffusion buffer; slots outside the block are not written and reach no result); reference-layout plans: the buffer takes the new interior (mpdata_diffuse.h).
-static int plan_diffuse(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
-                        const void* st, void* zflux, int first, int count) {
-  const int nx = p->nx, nzm = p->nz - 1;
-  const bool wm = p->layout == MPDATA_LAYOUT_WAVEMAJOR;
-  int rc = plan_dbuf(p, wm ? (size_t)p->ntiles * p->tile_elems * 8 : (size_t)n * nx * nzm * count * p->eb);
-  if (!rc) rc = plan_wrap_f(p, first, count);
-  if (rc) return rc;
-  if (wm) {
-    MpdataBlockJob tj = wm_block_job(p, 0, const_cast<void*>(tkh), sl0, n, 0, 1);
-    tj.j.prv = p->dbuf; tj.j.ncols = nx + 2; tj.j.prv_col0 = 2; tj.j.ref_levmul = nx + 2; tj.j.ref_tstride = 0; tj.j.prv_tstride = 0;
-    if (n != p->ncrms) {
-      HIP_TRY(mpdata_layout_convert_block(tj, true, p->stream));
-    } else if (p->odd) {   // the whole plan: the kernels of a whole import of f (plan_import)
-      HIP_TRY(mpdata_layout_convert_odd(&tj.j, 1, true, p->stream));
-    } else if (!legacy_convert()) {
-      const hipError_t e = mpdata_layout_import_rows(&tj.j, 1, p->stream);
-      if (e == hipErrorNotSupported) HIP_TRY(mpdata_layout_convert_cols(&tj.j, 1, true, p->stream));
-      else HIP_TRY(e);
-    } else {
-      HIP_TRY(mpdata_layout_convert(tj.j, 8, true, p->stream));
-    }
-    const MpdataLayoutJob jr = wm_job(p, 3, nullptr, 0, 1), ja = wm_job(p, 5, nullptr, 0, 1);
-    MpdataDiffuseJob b;
-    b.j = wm_job(p, 0, nullptr, first, count);
-    b.sel = block_sel(p, sl0, n);
-    b.tkh = p->dbuf;
-    b.rho = (const double*)jr.prv + jr.prv_col0 * jr.chunk;
-    b.adz = (const double*)ja.prv + ja.prv_col0 * ja.chunk;
-    b.kc_tile_stride = jr.prv_tile_stride;
-    b.cx = cx; b.cz = cz; b.sb = sb; b.st = st; b.zflux = zflux;
-    HIP_TRY(mpdata_diffuse_wm(b, p->stream));
-  } else {
-    const size_t f1 = p->sz.f / p->ntracers;
-    HIP_TRY(mpdata_diffuse_ref((char*)p->f + (size_t)first * f1 * p->eb, p->rho, p->adz, p->eb, p->ncrms, sl0, n, nx, nzm, count, tkh, cx,
-                               cz, sb, st, zflux, p->dbuf, p->stream));
-  }
-  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
-  return 0;
-}
-// range, then NULLs, then what the plan is and holds
-static int plan_diffuse_check(const char* what, mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz,
-                              int first, int count, int eb) {
-  int rc = block_range(what, p, sl0, n);
-  if (rc) return rc;
-  rc = tracer_range(p, first, count);
-  if (rc) return rc;
-  if (!tkh || !cx || !cz) return set_err(MPDATA_EINVAL, "%s: null %s", what, !tkh ? "tkh" : !cx ? "cx" : "cz");
-  if (p->inner)
-    return set_err(MPDATA_EUNSUPPORTED, "%s on a windowed plan (nz = %d > 238): tkh would have to be cut into level windows and the "
-                                        "seams refreshed; not built yet", what, p->nz);
-  if (eb) {
-    rc = plan_check(p, eb);
-    if (rc) return rc;
-  }
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
-  return 0;
-}
-int mpdata_plan_diffuse_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
-                               const void* st, void* zflux, int first_tracer, int ntracers) {
-  const int rc = plan_diffuse_check("mpdata_plan_diffuse_device", p, sl0, n, tkh, cx, cz, first_tracer, ntracers, 0);
-  if (rc) return rc;
-  DevGuard g(p->device);
-  return plan_diffuse(p, sl0, n, tkh, cx, cz, sb, st, zflux, first_tracer, ntracers);
-}
-// host arrays, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
-static int plan_diffuse_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
-                             const void* st, void* zflux, int eb) {
-  int rc = plan_diffuse_check("mpdata_plan_diffuse", p, sl0, n, tkh, cx, cz, 0, p ? p->ntracers : 1, eb);
-  if (rc) return rc;
-  DevGuard g(p->device);
-  const int nx = p->nx, nz = p->nz, nzm = nz - 1;
-  const size_t tb = (size_t)n * (nx + 2) * nzm * eb, cb = (size_t)n * nzm * eb, xb = (size_t)n * nx * eb,
-               zb = zflux ? (size_t)n * nz * p->ntracers * eb : 0;
-  rc = plan_bstage(p, tb + 2 * cb + 2 * xb + zb);
-  if (rc) return rc;
-  char* const d = (char*)p->bstage;
-  void* const dt = d; void* const dcx = d + tb; void* const dcz = d + tb + cb;
-  void* const dsb = sb ? d + tb + 2 * cb : nullptr;
-  void* const dst = st ? d + tb + 2 * cb + xb : nullptr;
-  void* const dz = zflux ? d + tb + 2 * cb + 2 * xb : nullptr;
-  HIP_TRY(hipMemcpyAsync(dt, tkh, tb, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(dcx, cx, cb, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(dcz, cz, cb, hipMemcpyHostToDevice, p->stream));
-  if (sb) HIP_TRY(hipMemcpyAsync(dsb, sb, xb, hipMemcpyHostToDevice, p->stream));
-  if (st) HIP_TRY(hipMemcpyAsync(dst, st, xb, hipMemcpyHostToDevice, p->stream));
-  rc = plan_diffuse(p, sl0, n, dt, dcx, dcz, dsb, dst, dz, 0, p->ntracers);
-  if (rc) return rc;
-  if (zflux) HIP_TRY(hipMemcpyAsync(zflux, dz, zb, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return 0;
-}
-int mpdata_plan_diffuse(mpdata_plan* p, int64_t sl0, int64_t n, const double* tkh, const double* cx, const double* cz, const double* sb,
-                        const double* st, double* zflux) {
-  return plan_diffuse_host(p, sl0, n, tkh, cx, cz, sb, st, zflux, 8);
-}
-int mpdata_plan_diffuse_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* tkh, const float* cx, const float* cz, const float* sb,
-                            const float* st, float* zflux) {
-  return plan_diffuse_host(p, sl0, n, tkh, cx, cz, sb, st, zflux, 4);
-}
-// the same on reference-layout device arrays (arguments checked before any device call).  The new interior of the block
-// goes through a scratch array of the call's own, which is freed when the work is done: the call returns after it.
-static int diffuse_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* rho, const void* adz,
-                         const void* tkh, const void* cx, const void* cz, const void* sb, const void* st, void* zflux, void* stream, int eb) {
-  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
-    return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
-                   (long long)ncrms, nx, nz, ntracers);
-  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
-    return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
-                   (long long)(sl0 + n), (long long)ncrms);
-  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
-  if (!tkh || !cx || !cz) return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: null %s", !tkh ? "tkh" : !cx ? "cx" : "cz");
-  void* scratch = nullptr;
-  HIP_TRY(hipMalloc(&scratch, (size_t)n * nx * (nz - 1) * ntracers * eb));
-  hipError_t e = mpdata_diffuse_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tkh, cx, cz, sb, st, zflux, scratch,
-                                    (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(scratch);
-  HIP_TRY(e);
-  return 0;
-}
-int mpdata_diffuse_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
-                          const double* adz, const double* tkh, const double* cx, const double* cz, const double* sb, const double* st,
-                          double* zflux, void* stream) {
-  return diffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cx, cz, sb, st, zflux, stream, 8);
-}
-int mpdata_diffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
-                              const float* adz, const float* tkh, const float* cx, const float* cz, const float* sb, const float* st,
-                              float* zflux, void* stream) {
-  return diffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cx, cz, sb, st, zflux, stream, 4);
-}
-
-// ---- 3m: large-scale vertical advection of f, in place.  Reads cb, cc, rewrites f on every column slot of the block's
-// instances and the tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not touched and no event is recorded.
-//   halo marks  the operator is the same in every column slot and couples none, so halo columns that are wrapped copies
-//               stay wrapped copies (same bits in, same operations) and stale ones stay stale -- halo_ok is right as it stands;
-//   seam marks  an owned level reads one level outside the owned range, so stale seams of the range are refreshed first,
-//               as a run does; only owned levels are written, so afterwards the other copies are stale: the marks of the
-//               range are cleared and the next run refreshes them;
-//   phantom     follows the plan's last slot inside the kernel (mpdata_subside.h); on a windowed plan the refresh of the
-//               inner plan follows as after a seam refresh.
-// Reference-layout plans: the plan's diffusion buffer takes the new rows (mpdata_subside.h).
-static int plan_subside(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int first, int count) {
-  if (p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR) {
-    int rc = plan_seams(p, first, count);
-    if (rc) return rc;
-    MpdataSubsideJob b;
-    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
-    b.sel = block_sel(p, sl0, n);
-    b.cb = cb; b.cc = cc; b.dsum = dsum;
-    HIP_TRY(mpdata_subside_wm(b, p->stream));
-    if (p->inner) {
-      memset(p->seam_ok + first, 0, (size_t)count);
-      if (sl0 + n == p->ncrms) rc = plan_phantom(p->inner, 0, first, count);
-      if (rc) return rc;
-    }
-  } else {
-    const int rc = plan_dbuf(p, (size_t)n * (p->nx + 6) * (p->nz - 1) * count * p->eb);
-    if (rc) return rc;
-    const size_t f1 = p->sz.f / p->ntracers;
-    HIP_TRY(mpdata_subside_ref((char*)p->f + (size_t)first * f1 * p->eb, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, cb, cc, dsum,
-                               p->dbuf, p->stream));
-  }
-  return 0;
-}
-// range, then NULLs, then what the plan is and holds
-static int plan_subside_check(const char* what, mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, int first,
-                              int count, int eb) {
-  int rc = block_range(what, p, sl0, n);
-  if (rc) return rc;
-  rc = tracer_range(p, first, count);
-  if (rc) return rc;
-  if (!cb || !cc) return set_err(MPDATA_EINVAL, "%s: null %s", what, !cb ? "cb" : "cc");
-  if (eb) {
-    rc = plan_check(p, eb);
-    if (rc) return rc;
-  }
-  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
-  return 0;
-}
-int mpdata_plan_subside_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int first_tracer,
-                               int ntracers) {
-  const int rc = plan_subside_check("mpdata_plan_subside_device", p, sl0, n, cb, cc, first_tracer, ntracers, 0);
-  if (rc) return rc;
-  DevGuard g(p->device);
-  return plan_subside(p, sl0, n, cb, cc, dsum, first_tracer, ntracers);
-}
-// host arrays, all tracers, synchronous: through the plan's block staging buffer (that of mpdata_plan_download_instances)
-static int plan_subside_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int eb) {
-  int rc = plan_subside_check("mpdata_plan_subside", p, sl0, n, cb, cc, 0, p ? p->ntracers : 1, eb);
-  if (rc) return rc;
-  DevGuard g(p->device);
-  const size_t kb = (size_t)n * (p->nz - 1) * eb, db = dsum ? kb * p->ntracers : 0;
-  rc = plan_bstage(p, 2 * kb + db);
-  if (rc) return rc;
-  char* const d = (char*)p->bstage;
-  void* const dd = dsum ? d + 2 * kb : nullptr;
-  HIP_TRY(hipMemcpyAsync(d, cb, kb, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(d + kb, cc, kb, hipMemcpyHostToDevice, p->stream));
-  rc = plan_subside(p, sl0, n, d, d + kb, dd, 0, p->ntracers);
-  if (rc) return rc;
-  if (dsum) HIP_TRY(hipMemcpyAsync(dsum, dd, db, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return 0;
-}
-int mpdata_plan_subside(mpdata_plan* p, int64_t sl0, int64_t n, const double* cb, const double* cc, double* dsum) {
-  return plan_subside_host(p, sl0, n, cb, cc, dsum, 8);
-}
-int mpdata_plan_subside_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* cb, const float* cc, float* dsum) {
-  return plan_subside_host(p, sl0, n, cb, cc, dsum, 4);
-}
-// the same on reference-layout device arrays (arguments checked before any device call).  The new rows go through a
-// scratch array of the call's own, which is freed when the work is done: the call returns after it.
-static int subside_array(int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* cb, const void* cc, void* dsum, void* stream,
-                         int eb) {
-  if (ncrms < 1 || nx < 1 || nz < 2 || ntracers < 1)
-    return set_err(MPDATA_EINVAL, "mpdata_subside_device: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)",
-                   (long long)ncrms, nx, nz, ntracers);
-  if (!f) return set_err(MPDATA_EINVAL, "mpdata_subside_device: null f");
-  if (!cb || !cc) return set_err(MPDATA_EINVAL, "mpdata_subside_device: null %s", !cb ? "cb" : "cc");
-  void* scratch = nullptr;
-  HIP_TRY(hipMalloc(&scratch, (size_t)ncrms * (nx + 6) * (nz - 1) * ntracers * eb));
-  hipError_t e = mpdata_subside_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, cb, cc, dsum, scratch, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(scratch);
-  HIP_TRY(e);
-  return 0;
-}
-int mpdata_subside_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* cb, const double* cc, double* dsum,
-                          void* stream) {
-  return subside_array(ncrms, nx, nz, ntracers, f, cb, cc, dsum, stream, 8);
-}
-int mpdata_subside_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* cb, const float* cc, float* dsum,
-                              void* stream) {
-  return subside_array(ncrms, nx, nz, ntracers, f, cb, cc, dsum, stream, 4);
 }
 
 // (EXACT wave-major runs: the finishing kernel of the bit-identical flux, behind the plan kernels on the same stream)

@@ -1,0 +1,645 @@
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3m).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_subside.hip.  A call is its kernel file, a dispatch on the
+// layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays.
+#include <cstring>
+
+#include "mpdata_column_path.h"
+#include "mpdata_courant.h"
+#include "mpdata_diffuse.h"
+#include "mpdata_level_add.h"
+#include "mpdata_plan_priv.h"
+#include "mpdata_scale_uw.h"
+#include "mpdata_stats.h"
+#include "mpdata_subside.h"
+
+using namespace mpd;
+
+namespace {
+
+// the plan's scratch buffer (struct mpdata_plan: dbuf), grown as the block staging buffer is
+int plan_dbuf(mpdata_plan* p, size_t need) {
+  if (p->dbuf_bytes >= need) return 0;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (p->dbuf) (void)hipFree(p->dbuf);
+  p->dbuf = nullptr; p->dbuf_bytes = 0;
+  HIP_TRY(hipMalloc(&p->dbuf, need));
+  p->dbuf_bytes = need;
+  return 0;
+}
+// a block of a plan for the kernels that walk its plan layout (mpdata_wm_walk.h), with wm_plan(p) the plan the layout
+// jobs are made of: a windowed plan's inner plan, read and rewritten where it lies (its stream and boundary are not
+// forwarded: nothing of it runs)
+MpdataBlockSel block_sel(const mpdata_plan* p, int64_t sl0, int64_t n) {
+  MpdataBlockSel b;
+  b.sl0 = sl0; b.n = n; b.ncrms = p->ncrms; b.ipe = 8 / p->eb;
+  b.W = p->inner ? p->W : 1; b.nz = p->nz;
+  return b;
+}
+const mpdata_plan* wm_plan(const mpdata_plan* p) { return p->inner ? p->inner : p; }
+// the plan is walked in its plan layout (else: a reference-layout plan, whose arrays the *_ref kernels take)
+bool plan_walked(const mpdata_plan* p) { return p->inner || p->layout == MPDATA_LAYOUT_WAVEMAJOR; }
+// tracer `first` of a reference-layout plan's f
+char* ref_f(const mpdata_plan* p, int first) { return (char*)p->f + (size_t)first * (p->sz.f / p->ntracers) * p->eb; }
+// rho and adz of a wave-major plan's kc array ([tile][rho, adz, rhow][chunk]) into the three fields of a job
+template <typename Job>
+void kc_rho_adz(const mpdata_plan* q, Job& b) {
+  const MpdataLayoutJob jr = wm_job(q, 3, nullptr, 0, 1), ja = wm_job(q, 5, nullptr, 0, 1);
+  b.rho = (const double*)jr.prv + jr.prv_col0 * jr.chunk;
+  b.adz = (const double*)ja.prv + ja.prv_col0 * ja.chunk;
+  b.kc_tile_stride = jr.prv_tile_stride;
+}
+
+// ---- Argument checks.  Every plan_X_check(what, ..., eb) serves both forms of its call (eb = 0: the device form) and
+// checks in one order: block_ranges (block_range alone for a call without tracers), the call's own arguments, plan_state.
+// A host form takes all tracers: it has no range to check and passes none.
+int block_ranges(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int first, int count, int eb) {
+  const int rc = block_range(what, p, sl0, n);
+  return rc || eb ? rc : tracer_range(p, first, count);
+}
+// the state a call on the plan's velocities needs: filled once, and the arrays asked for still held
+int plan_uw_state(const char* what, const mpdata_plan* p, bool need_u, bool need_w) {
+  if (!p->uploaded) return set_err(MPDATA_ESTATE, "%s before upload / import", what);
+  if ((need_u && !p->have_u) || (need_w && !p->have_w))
+    return set_err(MPDATA_ESTATE, "%s: the plan does not hold %s (mpdata_plan_run_uw used them up: import u and w)", what,
+                   (need_u && !p->have_u) ? "u" : "w");
+  return 0;
+}
+// what the plan is (host forms: its precision) and holds
+int plan_state(const char* what, const mpdata_plan* p, int eb, bool need_u = false, bool need_w = false) {
+  const int rc = eb ? plan_check(p, eb) : 0;
+  return rc ? rc : plan_uw_state(what, p, need_u, need_w);
+}
+int level_add_mode(const char* what, int mode) {
+  if (mode != MPDATA_LEVEL_ADD && mode != MPDATA_LEVEL_ADD_CLIP) return set_err(MPDATA_EINVAL, "%s: unknown mode %d", what, mode);
+  return 0;
+}
+// the sizes of a call on reference-layout device arrays (ntracers = NULL: a call without tracers)
+int array_sizes(const char* what, int64_t ncrms, int nx, int nz, const int* ntracers) {
+  if (ncrms >= 1 && nx >= 1 && nz >= 2 && (!ntracers || *ntracers >= 1)) return 0;
+  if (!ntracers) return set_err(MPDATA_EINVAL, "%s: bad sizes ncrms=%lld nx=%d nz=%d (need >=1,>=1,>=2)", what, (long long)ncrms, nx, nz);
+  return set_err(MPDATA_EINVAL, "%s: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)", what, (long long)ncrms, nx,
+                 nz, *ntracers);
+}
+
+// ---- Host forms (all tracers, synchronous): the host arrays of a call go through the plan's block staging buffer, in
+// argument order without padding; an absent array takes no room and gets a NULL device address.  Element alignment is all
+// the kernels need of these arrays -- they read them one real at a time -- but for tkh, which feeds the layout conversion
+// of wave-major plans (its fast path looks at the alignment of the base): it is the first of its call, at offset 0.
+struct HostArr {
+  const void* host;   // NULL: absent
+  size_t bytes;
+  bool out;           // false: read by the call (H2D in front of it); true: written by it (D2H behind it)
+  void* dev = nullptr;
+};
+// sizes the buffer, assigns the device addresses and issues the H2D copies on the plan's stream
+template <int N>
+int stage_in(mpdata_plan* p, HostArr (&a)[N]) {
+  size_t need = 0, off = 0;
+  for (const HostArr& h : a) need += h.host ? h.bytes : 0;
+  const int rc = plan_bstage(p, need);
+  if (rc) return rc;
+  for (HostArr& h : a) {
+    if (!h.host) continue;
+    h.dev = (char*)p->bstage + off;
+    off += h.bytes;
+    if (!h.out) HIP_TRY(hipMemcpyAsync(h.dev, h.host, h.bytes, hipMemcpyHostToDevice, p->stream));
+  }
+  return 0;
+}
+// ... and behind the call the D2H copies and the synchronisation
+template <int N>
+int stage_out(mpdata_plan* p, const HostArr (&a)[N]) {
+  for (const HostArr& h : a)
+    if (h.host && h.out) HIP_TRY(hipMemcpyAsync(const_cast<void*>(h.host), h.dev, h.bytes, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- 3g: horizontal sum / min / max per level of f.  Reads f, writes the outputs: no flag of the plan is touched (the
+// halo and seam marks stay -- halo columns are not read, owned levels are right whatever the seams hold), no event is
+// recorded, and a windowed plan's inner plan is read where it lies (its stream and boundary are not forwarded: nothing
+// of it runs).
+static int plan_level_stats(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int first, int count) {
+  if (plan_walked(p)) {
+    MpdataStatsJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.sum = sum; b.mn = mn; b.mx = mx;
+    HIP_TRY(mpdata_stats_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_stats_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, sum, mn, mx, p->stream));
+  }
+  return 0;
+}
+static int plan_level_stats_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* sum, const void* mn,
+                                  const void* mx, int first, int count, int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!sum && !mn && !mx) return set_err(MPDATA_EINVAL, "%s: sum, min and max are all NULL", what);
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_level_stats_device(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int first_tracer,
+                                   int ntracers) {
+  const int rc = plan_level_stats_check("mpdata_plan_level_stats_device", p, sl0, n, sum, mn, mx, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_level_stats(p, sl0, n, sum, mn, mx, first_tracer, ntracers);
+}
+static int plan_level_stats_host(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* mn, void* mx, int eb) {
+  int rc = plan_level_stats_check("mpdata_plan_level_stats", p, sl0, n, sum, mn, mx, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t one = (size_t)n * (p->nz - 1) * p->ntracers * eb;
+  HostArr a[3] = {{sum, one, true}, {mn, one, true}, {mx, one, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_level_stats(p, sl0, n, a[0].dev, a[1].dev, a[2].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_level_stats(mpdata_plan* p, int64_t sl0, int64_t n, double* sum, double* mn, double* mx) {
+  return plan_level_stats_host(p, sl0, n, sum, mn, mx, 8);
+}
+int mpdata_plan_level_stats_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* sum, float* mn, float* mx) {
+  return plan_level_stats_host(p, sl0, n, sum, mn, mx, 4);
+}
+// the same reduction on a reference-layout device array (arguments checked before any device call)
+static int level_stats_array(int64_t ncrms, int nx, int nz, int ntracers, const void* f, void* sum, void* mn, void* mx, void* stream,
+                             int eb) {
+  const int rc = array_sizes("mpdata_level_stats_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "mpdata_level_stats_device: null f");
+  if (!sum && !mn && !mx) return set_err(MPDATA_EINVAL, "mpdata_level_stats_device: sum, min and max are all NULL");
+  HIP_TRY(mpdata_stats_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, sum, mn, mx, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_level_stats_device(int64_t ncrms, int nx, int nz, int ntracers, const double* f, double* sum, double* mn, double* mx,
+                              void* stream) {
+  return level_stats_array(ncrms, nx, nz, ntracers, f, sum, mn, mx, stream, 8);
+}
+int mpdata_level_stats_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, float* sum, float* mn, float* mx,
+                                  void* stream) {
+  return level_stats_array(ncrms, nx, nz, ntracers, f, sum, mn, mx, stream, 4);
+}
+
+// ---- 3h: outflow Courant number of the plan's velocities per level (clev) and per instance (cinst).  Reads u, w, rho,
+// adz, writes the outputs: as the level statistics above no flag of the plan is touched, no event is recorded, and a
+// windowed plan's inner plan is read where it lies.
+static int plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst) {
+  if (plan_walked(p)) {
+    const mpdata_plan* q = wm_plan(p);
+    MpdataCourantJob b;
+    b.j = wm_job(q, 1, nullptr, 0, 1);
+    b.w = wm_job(q, 2, nullptr, 0, 1).prv;
+    kc_rho_adz(q, b);
+    b.sel = block_sel(p, sl0, n);
+    b.clev = clev; b.cinst = cinst;
+    HIP_TRY(mpdata_courant_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_courant_ref(p->u, p->w, p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, p->nz, clev, cinst, p->stream));
+  }
+  return 0;
+}
+static int plan_courant_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* clev, const void* cinst,
+                              int eb) {
+  const int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  if (!clev && !cinst) return set_err(MPDATA_EINVAL, "%s: clev and cinst are both NULL", what);
+  return plan_state(what, p, eb, true, true);
+}
+int mpdata_plan_courant_device(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst) {
+  const int rc = plan_courant_check("mpdata_plan_courant_device", p, sl0, n, clev, cinst, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_courant(p, sl0, n, clev, cinst);
+}
+static int plan_courant_host(mpdata_plan* p, int64_t sl0, int64_t n, void* clev, void* cinst, int eb) {
+  int rc = plan_courant_check("mpdata_plan_courant", p, sl0, n, clev, cinst, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  HostArr a[2] = {{clev, (size_t)n * (p->nz - 1) * eb, true}, {cinst, (size_t)n * eb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_courant(p, sl0, n, a[0].dev, a[1].dev);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_courant(mpdata_plan* p, int64_t sl0, int64_t n, double* clev, double* cinst) {
+  return plan_courant_host(p, sl0, n, clev, cinst, 8);
+}
+int mpdata_plan_courant_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* clev, float* cinst) {
+  return plan_courant_host(p, sl0, n, clev, cinst, 4);
+}
+// the same reduction on reference-layout device arrays (arguments checked before any device call)
+static int courant_array(int64_t ncrms, int nx, int nz, const void* u, const void* w, const void* rho, const void* adz, void* clev,
+                         void* cinst, void* stream, int eb) {
+  const int rc = array_sizes("mpdata_courant_device", ncrms, nx, nz, nullptr);
+  if (rc) return rc;
+  if (!u || !w || !rho || !adz)
+    return set_err(MPDATA_EINVAL, "mpdata_courant_device: null %s", !u ? "u" : !w ? "w" : !rho ? "rho" : "adz");
+  if (!clev && !cinst) return set_err(MPDATA_EINVAL, "mpdata_courant_device: clev and cinst are both NULL");
+  HIP_TRY(mpdata_courant_ref(u, w, rho, adz, eb, ncrms, 0, ncrms, nx, nz, clev, cinst, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_courant_device(int64_t ncrms, int nx, int nz, const double* u, const double* w, const double* rho, const double* adz,
+                          double* clev, double* cinst, void* stream) {
+  return courant_array(ncrms, nx, nz, u, w, rho, adz, clev, cinst, stream, 8);
+}
+int mpdata_courant_f32_device(int64_t ncrms, int nx, int nz, const float* u, const float* w, const float* rho, const float* adz,
+                              float* clev, float* cinst, void* stream) {
+  return courant_array(ncrms, nx, nz, u, w, rho, adz, clev, cinst, stream, 4);
+}
+
+// ---- 3i: per-level increments of f, in place.  Reads d, rewrites f on every column slot of the block's instances: no
+// flag of the plan is touched and no event is recorded.  The hidden invariants hold by construction, not by a refresh:
+//   halo marks  the increment is uniform in i, so halo columns that are wrapped copies stay wrapped copies (same bits in,
+//               same operation) and stale ones stay stale -- halo_ok is right as it stands;
+//   seam marks  every level a window stores takes the increment of the tall level it stands for, so fresh seams stay
+//               fresh and stale ones stay stale -- seam_ok is right as it stands;
+//   phantom     follows the plan's last instance inside the kernel (mpdata_level_add.h).
+// A windowed plan's inner plan is rewritten where it lies (its stream and boundary are not forwarded: nothing of it runs).
+static int plan_level_add(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int first, int count) {
+  const int clip = mode == MPDATA_LEVEL_ADD_CLIP;
+  if (plan_walked(p)) {
+    MpdataLevelAddJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.d = d; b.clip = clip;
+    HIP_TRY(mpdata_level_add_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_level_add_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, d, clip, p->stream));
+  }
+  return 0;
+}
+static int plan_level_add_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int first,
+                                int count, int eb) {
+  int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!d) return set_err(MPDATA_EINVAL, "%s: null d", what);
+  rc = level_add_mode(what, mode);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_level_add_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int first_tracer, int ntracers) {
+  const int rc = plan_level_add_check("mpdata_plan_level_add_device", p, sl0, n, d, mode, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_level_add(p, sl0, n, d, mode, first_tracer, ntracers);
+}
+static int plan_level_add_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* d, int mode, int eb) {
+  int rc = plan_level_add_check("mpdata_plan_level_add", p, sl0, n, d, mode, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  HostArr a[1] = {{d, (size_t)n * (p->nz - 1) * p->ntracers * eb, false}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_level_add(p, sl0, n, a[0].dev, mode, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_level_add(mpdata_plan* p, int64_t sl0, int64_t n, const double* d, int mode) {
+  return plan_level_add_host(p, sl0, n, d, mode, 8);
+}
+int mpdata_plan_level_add_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* d, int mode) {
+  return plan_level_add_host(p, sl0, n, d, mode, 4);
+}
+// the same on a reference-layout device array (arguments checked before any device call)
+static int level_add_array(int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* d, int mode, void* stream, int eb) {
+  int rc = array_sizes("mpdata_level_add_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (!f || !d) return set_err(MPDATA_EINVAL, "mpdata_level_add_device: null %s", !f ? "f" : "d");
+  rc = level_add_mode("mpdata_level_add_device", mode);
+  if (rc) return rc;
+  HIP_TRY(mpdata_level_add_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, d, mode == MPDATA_LEVEL_ADD_CLIP, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_level_add_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* d, int mode, void* stream) {
+  return level_add_array(ncrms, nx, nz, ntracers, f, d, mode, stream, 8);
+}
+int mpdata_level_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* d, int mode, void* stream) {
+  return level_add_array(ncrms, nx, nz, ntracers, f, d, mode, stream, 4);
+}
+
+// ---- 3j: one factor per instance on the plan's u and / or w, in place.  Reads su, sw, rewrites every column and level
+// the plan stores of the block's instances: no flag of the plan is touched and no event is recorded.  f, flux, rho, rhow,
+// adz are not looked at, so halo and seam marks are right as they stand; every window of an instance and every level it
+// stores takes the instance's factor, so all stored copies of a tall level change alike; the phantom half follows the
+// plan's last instance inside the kernel (mpdata_scale_uw.h).  A windowed plan's inner plan is rewritten where it lies.
+static int plan_scale_uw(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw) {
+  if (plan_walked(p)) {
+    const mpdata_plan* q = wm_plan(p);
+    MpdataScaleUwJob b;
+    b.sel = block_sel(p, sl0, n);
+    if (su) { b.j = wm_job(q, 1, nullptr, 0, 1); b.s = su; HIP_TRY(mpdata_scale_uw_wm(b, p->stream)); }
+    if (sw) { b.j = wm_job(q, 2, nullptr, 0, 1); b.s = sw; HIP_TRY(mpdata_scale_uw_wm(b, p->stream)); }
+  } else {
+    if (su) HIP_TRY(mpdata_scale_uw_ref(p->u, p->eb, p->ncrms, sl0, n, p->nx + 5, p->nz - 1, su, p->stream));
+    if (sw) HIP_TRY(mpdata_scale_uw_ref(p->w, p->eb, p->ncrms, sl0, n, p->nx + 4, p->nz, sw, p->stream));
+  }
+  return 0;
+}
+static int plan_scale_uw_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw, int eb) {
+  const int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  if (!su && !sw) return set_err(MPDATA_EINVAL, "%s: su and sw are both NULL", what);
+  return plan_state(what, p, eb, su != nullptr, sw != nullptr);
+}
+int mpdata_plan_scale_uw_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw) {
+  const int rc = plan_scale_uw_check("mpdata_plan_scale_uw_device", p, sl0, n, su, sw, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_scale_uw(p, sl0, n, su, sw);
+}
+static int plan_scale_uw_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* su, const void* sw, int eb) {
+  int rc = plan_scale_uw_check("mpdata_plan_scale_uw", p, sl0, n, su, sw, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  HostArr a[2] = {{su, (size_t)n * eb, false}, {sw, (size_t)n * eb, false}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_scale_uw(p, sl0, n, a[0].dev, a[1].dev);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_scale_uw(mpdata_plan* p, int64_t sl0, int64_t n, const double* su, const double* sw) {
+  return plan_scale_uw_host(p, sl0, n, su, sw, 8);
+}
+int mpdata_plan_scale_uw_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* su, const float* sw) {
+  return plan_scale_uw_host(p, sl0, n, su, sw, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call)
+static int scale_uw_array(int64_t ncrms, int nx, int nz, void* u, void* w, const void* su, const void* sw, void* stream, int eb) {
+  const int rc = array_sizes("mpdata_scale_uw_device", ncrms, nx, nz, nullptr);
+  if (rc) return rc;
+  if (!u && !w) return set_err(MPDATA_EINVAL, "mpdata_scale_uw_device: u and w are both NULL");
+  if (!u != !su || !w != !sw)
+    return set_err(MPDATA_EINVAL, "mpdata_scale_uw_device: %s without %s", !u != !su ? (u ? "u" : "su") : (w ? "w" : "sw"),
+                   !u != !su ? (u ? "su" : "u") : (w ? "sw" : "w"));
+  if (u) HIP_TRY(mpdata_scale_uw_ref(u, eb, ncrms, 0, ncrms, nx + 5, nz - 1, su, (hipStream_t)stream));
+  if (w) HIP_TRY(mpdata_scale_uw_ref(w, eb, ncrms, 0, ncrms, nx + 4, nz, sw, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_scale_uw_device(int64_t ncrms, int nx, int nz, double* u, double* w, const double* su, const double* sw, void* stream) {
+  return scale_uw_array(ncrms, nx, nz, u, w, su, sw, stream, 8);
+}
+int mpdata_scale_uw_f32_device(int64_t ncrms, int nx, int nz, float* u, float* w, const float* su, const float* sw, void* stream) {
+  return scale_uw_array(ncrms, nx, nz, u, w, su, sw, stream, 4);
+}
+
+// ---- 3k: mass-weighted column integrals of f per interior column (path) and their sum over the columns (mass).  Reads f,
+// rho, adz, writes the outputs: as the level statistics no flag of the plan is touched (halo columns are not read, owned
+// levels are right whatever the seams hold), no event is recorded, and a windowed plan's inner plan is read where it
+// lies.  The velocities are not looked at: the plan need not hold any.
+static int plan_column_path(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int first, int count) {
+  if (plan_walked(p)) {
+    const mpdata_plan* q = wm_plan(p);
+    MpdataColumnPathJob b;
+    b.j = wm_job(q, 0, nullptr, first, count);
+    kc_rho_adz(q, b);
+    b.sel = block_sel(p, sl0, n);
+    b.path = path; b.mass = mass;
+    HIP_TRY(mpdata_column_path_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_column_path_ref(ref_f(p, first), p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, path, mass,
+                                   p->stream));
+  }
+  return 0;
+}
+static int plan_column_path_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* path, int first,
+                                  int count, int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!path) return set_err(MPDATA_EINVAL, "%s: null path", what);
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_column_path_device(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int first_tracer, int ntracers) {
+  const int rc = plan_column_path_check("mpdata_plan_column_path_device", p, sl0, n, path, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_column_path(p, sl0, n, path, mass, first_tracer, ntracers);
+}
+static int plan_column_path_host(mpdata_plan* p, int64_t sl0, int64_t n, void* path, void* mass, int eb) {
+  int rc = plan_column_path_check("mpdata_plan_column_path", p, sl0, n, path, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  HostArr a[2] = {{path, (size_t)n * p->nx * p->ntracers * eb, true}, {mass, (size_t)n * p->ntracers * eb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_column_path(p, sl0, n, a[0].dev, a[1].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_column_path(mpdata_plan* p, int64_t sl0, int64_t n, double* path, double* mass) {
+  return plan_column_path_host(p, sl0, n, path, mass, 8);
+}
+int mpdata_plan_column_path_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* path, float* mass) {
+  return plan_column_path_host(p, sl0, n, path, mass, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call)
+static int column_path_array(int64_t ncrms, int nx, int nz, int ntracers, const void* f, const void* rho, const void* adz, void* path,
+                             void* mass, void* stream, int eb) {
+  const int rc = array_sizes("mpdata_column_path_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_column_path_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
+  if (!path) return set_err(MPDATA_EINVAL, "mpdata_column_path_device: null path");
+  HIP_TRY(mpdata_column_path_ref(f, rho, adz, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, path, mass, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_column_path_device(int64_t ncrms, int nx, int nz, int ntracers, const double* f, const double* rho, const double* adz,
+                              double* path, double* mass, void* stream) {
+  return column_path_array(ncrms, nx, nz, ntracers, f, rho, adz, path, mass, stream, 8);
+}
+int mpdata_column_path_f32_device(int64_t ncrms, int nx, int nz, int ntracers, const float* f, const float* rho, const float* adz,
+                                  float* path, float* mass, void* stream) {
+  return column_path_array(ncrms, nx, nz, ntracers, f, rho, adz, path, mass, stream, 4);
+}
+
+// ---- 3l: eddy diffusion of f, in place.  Reads tkh, cx, cz, sb, st and the plan's rho and adz, rewrites the interior
+// columns of f of the block's instances and the tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not
+// touched and no event is recorded.  The halo columns 0 and nx+1 are inputs: a periodic plan wraps stale halos first, as a
+// run does, and afterwards its halos are copies of the OLD interior, so the marks of the range are cleared and the next
+// run or read-back wraps again.  Wave-major plans: tkh is brought into the plan layout once per call by the conversion
+// kernels of an import of f -- the block's for a block, the whole import's for the whole plan -- (a job of nx + 2 columns
+// at column slot 2 into the plan's diffusion buffer; slots outside the block are not written and reach no result); reference-layout plans: the buffer takes the new interior (mpdata_diffuse.h).
+static int plan_diffuse(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
+                        const void* st, void* zflux, int first, int count) {
+  const int nx = p->nx, nzm = p->nz - 1;
+  const bool wm = p->layout == MPDATA_LAYOUT_WAVEMAJOR;
+  int rc = plan_dbuf(p, wm ? (size_t)p->ntiles * p->tile_elems * 8 : (size_t)n * nx * nzm * count * p->eb);
+  if (!rc) rc = plan_wrap_f(p, first, count);
+  if (rc) return rc;
+  if (wm) {
+    MpdataBlockJob tj = wm_block_job(p, 0, const_cast<void*>(tkh), sl0, n, 0, 1);
+    tj.j.prv = p->dbuf; tj.j.ncols = nx + 2; tj.j.prv_col0 = 2; tj.j.ref_levmul = nx + 2; tj.j.ref_tstride = 0; tj.j.prv_tstride = 0;
+    if (n != p->ncrms) {
+      HIP_TRY(mpdata_layout_convert_block(tj, true, p->stream));
+    } else if (p->odd) {   // the whole plan: the kernels of a whole import of f (plan_import)
+      HIP_TRY(mpdata_layout_convert_odd(&tj.j, 1, true, p->stream));
+    } else if (!legacy_convert()) {
+      const hipError_t e = mpdata_layout_import_rows(&tj.j, 1, p->stream);
+      if (e == hipErrorNotSupported) HIP_TRY(mpdata_layout_convert_cols(&tj.j, 1, true, p->stream));
+      else HIP_TRY(e);
+    } else {
+      HIP_TRY(mpdata_layout_convert(tj.j, 8, true, p->stream));
+    }
+    MpdataDiffuseJob b;
+    b.j = wm_job(p, 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.tkh = p->dbuf;
+    kc_rho_adz(p, b);
+    b.cx = cx; b.cz = cz; b.sb = sb; b.st = st; b.zflux = zflux;
+    HIP_TRY(mpdata_diffuse_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_diffuse_ref(ref_f(p, first), p->rho, p->adz, p->eb, p->ncrms, sl0, n, nx, nzm, count, tkh, cx, cz, sb, st, zflux,
+                               p->dbuf, p->stream));
+  }
+  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
+  return 0;
+}
+static int plan_diffuse_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx,
+                              const void* cz, int first, int count, int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!tkh || !cx || !cz) return set_err(MPDATA_EINVAL, "%s: null %s", what, !tkh ? "tkh" : !cx ? "cx" : "cz");
+  if (p->inner)
+    return set_err(MPDATA_EUNSUPPORTED, "%s on a windowed plan (nz = %d > 238): tkh would have to be cut into level windows and the "
+                                        "seams refreshed; not built yet", what, p->nz);
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_diffuse_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
+                               const void* st, void* zflux, int first_tracer, int ntracers) {
+  const int rc = plan_diffuse_check("mpdata_plan_diffuse_device", p, sl0, n, tkh, cx, cz, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_diffuse(p, sl0, n, tkh, cx, cz, sb, st, zflux, first_tracer, ntracers);
+}
+static int plan_diffuse_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx, const void* cz, const void* sb,
+                             const void* st, void* zflux, int eb) {
+  int rc = plan_diffuse_check("mpdata_plan_diffuse", p, sl0, n, tkh, cx, cz, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t cb = (size_t)n * (p->nz - 1) * eb, xb = (size_t)n * p->nx * eb;
+  HostArr a[6] = {{tkh, cb * (p->nx + 2), false}, {cx, cb, false}, {cz, cb, false}, {sb, xb, false}, {st, xb, false},
+                  {zflux, (size_t)n * p->nz * p->ntracers * eb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_diffuse(p, sl0, n, a[0].dev, a[1].dev, a[2].dev, a[3].dev, a[4].dev, a[5].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_diffuse(mpdata_plan* p, int64_t sl0, int64_t n, const double* tkh, const double* cx, const double* cz, const double* sb,
+                        const double* st, double* zflux) {
+  return plan_diffuse_host(p, sl0, n, tkh, cx, cz, sb, st, zflux, 8);
+}
+int mpdata_plan_diffuse_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* tkh, const float* cx, const float* cz, const float* sb,
+                            const float* st, float* zflux) {
+  return plan_diffuse_host(p, sl0, n, tkh, cx, cz, sb, st, zflux, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call).  The new interior of the block
+// goes through a scratch array of the call's own, which is freed when the work is done: the call returns after it.
+static int diffuse_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* rho, const void* adz,
+                         const void* tkh, const void* cx, const void* cz, const void* sb, const void* st, void* zflux, void* stream, int eb) {
+  const int rc = array_sizes("mpdata_diffuse_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
+    return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
+                   (long long)(sl0 + n), (long long)ncrms);
+  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
+  if (!tkh || !cx || !cz) return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: null %s", !tkh ? "tkh" : !cx ? "cx" : "cz");
+  void* scratch = nullptr;
+  HIP_TRY(hipMalloc(&scratch, (size_t)n * nx * (nz - 1) * ntracers * eb));
+  hipError_t e = mpdata_diffuse_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tkh, cx, cz, sb, st, zflux, scratch,
+                                    (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(scratch);
+  HIP_TRY(e);
+  return 0;
+}
+int mpdata_diffuse_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                          const double* adz, const double* tkh, const double* cx, const double* cz, const double* sb, const double* st,
+                          double* zflux, void* stream) {
+  return diffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cx, cz, sb, st, zflux, stream, 8);
+}
+int mpdata_diffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                              const float* adz, const float* tkh, const float* cx, const float* cz, const float* sb, const float* st,
+                              float* zflux, void* stream) {
+  return diffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cx, cz, sb, st, zflux, stream, 4);
+}
+
+// ---- 3m: large-scale vertical advection of f, in place.  Reads cb, cc, rewrites f on every column slot of the block's
+// instances and the tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not touched and no event is recorded.
+//   halo marks  the operator is the same in every column slot and couples none, so halo columns that are wrapped copies
+//               stay wrapped copies (same bits in, same operations) and stale ones stay stale -- halo_ok is right as it stands;
+//   seam marks  an owned level reads one level outside the owned range, so stale seams of the range are refreshed first,
+//               as a run does; only owned levels are written, so afterwards the other copies are stale: the marks of the
+//               range are cleared and the next run refreshes them;
+//   phantom     follows the plan's last slot inside the kernel (mpdata_subside.h); on a windowed plan the refresh of the
+//               inner plan follows as after a seam refresh.
+// Reference-layout plans: the plan's diffusion buffer takes the new rows (mpdata_subside.h).
+static int plan_subside(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int first, int count) {
+  if (plan_walked(p)) {
+    int rc = plan_seams(p, first, count);
+    if (rc) return rc;
+    MpdataSubsideJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.cb = cb; b.cc = cc; b.dsum = dsum;
+    HIP_TRY(mpdata_subside_wm(b, p->stream));
+    if (p->inner) {
+      memset(p->seam_ok + first, 0, (size_t)count);
+      if (sl0 + n == p->ncrms) rc = plan_phantom(p->inner, 0, first, count);
+      if (rc) return rc;
+    }
+  } else {
+    const int rc = plan_dbuf(p, (size_t)n * (p->nx + 6) * (p->nz - 1) * count * p->eb);
+    if (rc) return rc;
+    HIP_TRY(mpdata_subside_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, cb, cc, dsum, p->dbuf, p->stream));
+  }
+  return 0;
+}
+static int plan_subside_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, int first,
+                              int count, int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!cb || !cc) return set_err(MPDATA_EINVAL, "%s: null %s", what, !cb ? "cb" : "cc");
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_subside_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int first_tracer,
+                               int ntracers) {
+  const int rc = plan_subside_check("mpdata_plan_subside_device", p, sl0, n, cb, cc, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_subside(p, sl0, n, cb, cc, dsum, first_tracer, ntracers);
+}
+static int plan_subside_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int eb) {
+  int rc = plan_subside_check("mpdata_plan_subside", p, sl0, n, cb, cc, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb;
+  HostArr a[3] = {{cb, kb, false}, {cc, kb, false}, {dsum, kb * p->ntracers, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_subside(p, sl0, n, a[0].dev, a[1].dev, a[2].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_subside(mpdata_plan* p, int64_t sl0, int64_t n, const double* cb, const double* cc, double* dsum) {
+  return plan_subside_host(p, sl0, n, cb, cc, dsum, 8);
+}
+int mpdata_plan_subside_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* cb, const float* cc, float* dsum) {
+  return plan_subside_host(p, sl0, n, cb, cc, dsum, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call).  The new rows go through a
+// scratch array of the call's own, which is freed when the work is done: the call returns after it.
+static int subside_array(int64_t ncrms, int nx, int nz, int ntracers, void* f, const void* cb, const void* cc, void* dsum, void* stream,
+                         int eb) {
+  const int rc = array_sizes("mpdata_subside_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "mpdata_subside_device: null f");
+  if (!cb || !cc) return set_err(MPDATA_EINVAL, "mpdata_subside_device: null %s", !cb ? "cb" : "cc");
+  void* scratch = nullptr;
+  HIP_TRY(hipMalloc(&scratch, (size_t)ncrms * (nx + 6) * (nz - 1) * ntracers * eb));
+  hipError_t e = mpdata_subside_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, cb, cc, dsum, scratch, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(scratch);
+  HIP_TRY(e);
+  return 0;
+}
+int mpdata_subside_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* cb, const double* cc, double* dsum,
+                          void* stream) {
+  return subside_array(ncrms, nx, nz, ntracers, f, cb, cc, dsum, stream, 8);
+}
+int mpdata_subside_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* cb, const float* cc, float* dsum,
+                              void* stream) {
+  return subside_array(ncrms, nx, nz, ntracers, f, cb, cc, dsum, stream, 4);
+}
+}  // extern "C"
