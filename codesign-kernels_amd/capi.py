@@ -147,6 +147,14 @@ def lib():
         for name in ("mpdata_subside_device", "mpdata_subside_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, dp, dp, dp, dp, vp]
+        L.mpdata_plan_sediment_device.restype = ci
+        L.mpdata_plan_sediment_device.argtypes = [vp, i64, i64, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_sediment", "mpdata_plan_sediment_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp, dp]
+        for name in ("mpdata_sediment_device", "mpdata_sediment_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 6 + [vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -843,6 +851,34 @@ class Plan:
                 None if dsum is None else self._block_host(dsum, "dsum", (n, nzm), True, True)]
         _check(getattr(lib(), "mpdata_plan_subside" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def sediment(self, wp, psfc=None, pflux=None, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """Sedimentation of f in place (include/mpdata_hip.h 3n) on the interior columns of instances [sl0, sl0+n) (default:
+        the rest of the plan from sl0): f(k) -= (wp(k) f(k) - wp(k+1) f(k+1)) / (rho(k) adz(k)) from the old field, nothing
+        entering through the top, on the plan's stream (mpdata_plan_sediment_device).  Reference-layout DEVICE tensors of
+        the plan's precision, shapes sediment_shapes(n, nx, nz, ntr): wp ([ntr,] nzm, nx, n), one field per tracer, read
+        where it lies; psfc ([ntr,] nx, n) or None (skipped), the flux through the surface; pflux ([ntr,] nzm, n) or None
+        (skipped), the flux summed over the interior columns.  The tracers are first_tracer .. +ntr-1, ntr = ntracers, or
+        the leading axis of a 4-d wp (else 1); psfc and pflux carry that axis exactly when wp does.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        nx, nz = self.dims[1], self.dims[2]
+        # the one tracer-count rule (_block_ntr) on the first tensor given, wp seen without its column axis: the leading
+        # axis of any of the three is the tracer axis of all three
+        lead = wp[..., 0, :] if wp is not None else (psfc if psfc is not None else pflux)
+        ntr, axis = self._block_ntr(lead, ntracers)
+        sh = sediment_shapes(n, nx, nz, ntr if axis else None)
+        ptrs = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("wp", wp), ("psfc", psfc), ("pflux", pflux))]
+        _check(lib().mpdata_plan_sediment_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
+
+    def sediment_host(self, wp, psfc=None, pflux=None, sl0=0, n=None):
+        """The same for all tracers from HOST arrays (numpy, Fortran order): wp (n, nx, nzm[, ntracers]), psfc (n, nx[,
+        ntracers]) or None, pflux (n, nzm[, ntracers]) or None (both written), synchronous (mpdata_plan_sediment[_f32])."""
+        n = self._block_n(sl0, n)
+        nx, nzm = self.dims[1], self.dims[2] - 1
+        ptrs = [None if a is None else self._block_host(a, name, want, True, out)
+                for name, a, want, out in (("wp", wp, (n, nx, nzm), False), ("psfc", psfc, (n, nx), True),
+                                           ("pflux", pflux, (n, nzm), True))]
+        _check(getattr(lib(), "mpdata_plan_sediment" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -988,6 +1024,37 @@ def diffuse(f, rho, adz, tkh, cx, cz, sb=None, st=None, zflux=None, sl0=0, n=Non
     ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype)
             for k, t in (("tkh", tkh), ("cx", cx), ("cz", cz), ("sb", sb), ("st", st), ("zflux", zflux))]
     fn = lib().mpdata_diffuse_device if f.dtype == torch.float64 else lib().mpdata_diffuse_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, *ptrs, _stream_handle(stream)))
+
+
+def sediment_shapes(n, nx, nz, ntracers=None):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a sediment call on n instances: wp
+    ([ntracers,] nzm, nx, n), psfc ([ntracers,] nx, n), pflux ([ntracers,] nzm, n); ntracers None: one tracer without the
+    leading axis."""
+    lead = () if ntracers is None else (int(ntracers),)
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {"wp": lead + (nz - 1, nx, n), "psfc": lead + (nx, n), "pflux": lead + (nz - 1, n)}
+
+
+def sediment(f, rho, adz, wp, psfc=None, pflux=None, sl0=0, n=None, stream=None):
+    """Sedimentation (include/mpdata_hip.h 3n) of instances [sl0, sl0+n) (default: the rest from sl0) of a reference-layout
+    DEVICE tensor f ([ntr,] nzm, nx+6, ncrms) with rho, adz (nzm, ncrms), float64 or float32, in place; wp, psfc, pflux of
+    the same dtype with the shapes of sediment_shapes(n, nx, nz, ntr) (psfc, pflux may be None).  Enqueued on `stream`;
+    returns when the work is done (mpdata_sediment_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"sediment: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    pr = _dev_ptr(rho, (nzm, ncrms), "rho", f.dtype)
+    pa = _dev_ptr(adz, (nzm, ncrms), "adz", f.dtype)
+    sh = sediment_shapes(n, nxp6 - 6, nzm + 1, nt if f.dim() == 4 else None)
+    ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("wp", wp), ("psfc", psfc), ("pflux", pflux))]
+    fn = lib().mpdata_sediment_device if f.dtype == torch.float64 else lib().mpdata_sediment_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, *ptrs, _stream_handle(stream)))
 
 

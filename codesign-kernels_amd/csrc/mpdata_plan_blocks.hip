@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3m).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_subside.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3n).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_sediment.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays.
 #include <cstring>
 
@@ -9,6 +9,7 @@
 #include "mpdata_level_add.h"
 #include "mpdata_plan_priv.h"
 #include "mpdata_scale_uw.h"
+#include "mpdata_sediment.h"
 #include "mpdata_stats.h"
 #include "mpdata_subside.h"
 
@@ -641,5 +642,101 @@ int mpdata_subside_device(int64_t ncrms, int nx, int nz, int ntracers, double* f
 int mpdata_subside_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* cb, const float* cc, float* dsum,
                               void* stream) {
   return subside_array(ncrms, nx, nz, ntracers, f, cb, cc, dsum, stream, 4);
+}
+
+// ---- 3n: sedimentation of f, in place.  Reads wp and the plan's rho and adz, rewrites the INTERIOR columns of f of the
+// block's instances and the tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not touched and no event
+// is recorded.
+//   halo marks  halo columns are neither read nor written, so no wrap is launched in front; afterwards a periodic plan's
+//               halos are copies of the OLD interior: the marks of the range are cleared and the next run or read-back
+//               wraps again;
+//   seam marks  an owned level reads the level above it, one level outside the owned range at a window's top, so stale
+//               seams of the range are refreshed first, as a run does; only owned levels are written, so afterwards the
+//               other copies are stale: the marks of the range are cleared and the next run refreshes them;
+//   phantom     follows the plan's last slot inside the kernel (mpdata_sediment.h); on a windowed plan the refresh of the
+//               inner plan follows as after a seam refresh.
+// Wave-major and windowed plans: wp is read where it lies (mpdata_sediment.h), the diffusion buffer is not used.
+// Reference-layout plans: the buffer takes the new interior.
+static int plan_sediment(mpdata_plan* p, int64_t sl0, int64_t n, const void* wp, void* psfc, void* pflux, int first, int count) {
+  if (plan_walked(p)) {
+    int rc = plan_seams(p, first, count);
+    if (rc) return rc;
+    const mpdata_plan* q = wm_plan(p);
+    MpdataSedimentJob b;
+    b.j = wm_job(q, 0, nullptr, first, count);
+    kc_rho_adz(q, b);
+    b.sel = block_sel(p, sl0, n);
+    b.wp = wp; b.psfc = psfc; b.pflux = pflux;
+    HIP_TRY(mpdata_sediment_wm(b, p->stream));
+    if (p->inner) {
+      memset(p->seam_ok + first, 0, (size_t)count);
+      if (sl0 + n == p->ncrms) rc = plan_phantom(p->inner, 0, first, count);
+      if (rc) return rc;
+    }
+  } else {
+    const int rc = plan_dbuf(p, (size_t)n * p->nx * (p->nz - 1) * count * p->eb);
+    if (rc) return rc;
+    HIP_TRY(mpdata_sediment_ref(ref_f(p, first), p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, wp, psfc, pflux,
+                                p->dbuf, p->stream));
+  }
+  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
+  return 0;
+}
+static int plan_sediment_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* wp, int first, int count,
+                               int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!wp) return set_err(MPDATA_EINVAL, "%s: null wp", what);
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_sediment_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* wp, void* psfc, void* pflux, int first_tracer,
+                                int ntracers) {
+  const int rc = plan_sediment_check("mpdata_plan_sediment_device", p, sl0, n, wp, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_sediment(p, sl0, n, wp, psfc, pflux, first_tracer, ntracers);
+}
+static int plan_sediment_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* wp, void* psfc, void* pflux, int eb) {
+  int rc = plan_sediment_check("mpdata_plan_sediment", p, sl0, n, wp, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t xb = (size_t)n * p->nx * p->ntracers * eb, kb = (size_t)n * (p->nz - 1) * p->ntracers * eb;
+  HostArr a[3] = {{wp, xb * (p->nz - 1), false}, {psfc, xb, true}, {pflux, kb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_sediment(p, sl0, n, a[0].dev, a[1].dev, a[2].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_sediment(mpdata_plan* p, int64_t sl0, int64_t n, const double* wp, double* psfc, double* pflux) {
+  return plan_sediment_host(p, sl0, n, wp, psfc, pflux, 8);
+}
+int mpdata_plan_sediment_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* wp, float* psfc, float* pflux) {
+  return plan_sediment_host(p, sl0, n, wp, psfc, pflux, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call).  The new interior of the block
+// goes through a scratch array of the call's own, which is freed when the work is done: the call returns after it.
+static int sediment_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* rho, const void* adz,
+                          const void* wp, void* psfc, void* pflux, void* stream, int eb) {
+  const int rc = array_sizes("mpdata_sediment_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
+    return set_err(MPDATA_EINVAL, "mpdata_sediment_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
+                   (long long)(sl0 + n), (long long)ncrms);
+  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_sediment_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
+  if (!wp) return set_err(MPDATA_EINVAL, "mpdata_sediment_device: null wp");
+  void* scratch = nullptr;
+  HIP_TRY(hipMalloc(&scratch, (size_t)n * nx * (nz - 1) * ntracers * eb));
+  hipError_t e = mpdata_sediment_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, wp, psfc, pflux, scratch, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(scratch);
+  HIP_TRY(e);
+  return 0;
+}
+int mpdata_sediment_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                           const double* adz, const double* wp, double* psfc, double* pflux, void* stream) {
+  return sediment_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, wp, psfc, pflux, stream, 8);
+}
+int mpdata_sediment_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                               const float* adz, const float* wp, float* psfc, float* pflux, void* stream) {
+  return sediment_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, wp, psfc, pflux, stream, 4);
 }
 }  // extern "C"

@@ -55,6 +55,10 @@ module mpdata_hip_mod
   ! form only -- it carries no reals of its own, so one binding serves both precisions; the per-precision host and array
   ! forms (mpdata_plan_subside[_f32], mpdata_subside[_f32]_device) have no Fortran interface yet
   public :: mpdata_plan_subside_device_c
+  ! sedimentation of a resident plan's tracers, in place (include/mpdata_hip.h section 3n): the device form only, one
+  ! binding for both precisions as for 3m; mpdata_plan_sediment[_f32] and mpdata_sediment[_f32]_device have no Fortran
+  ! interface yet
+  public :: mpdata_plan_sediment_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -459,6 +463,17 @@ module mpdata_hip_mod
       type(c_ptr), value :: plan
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: cb, cc, dsum
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! ---- sedimentation of f in place (include/mpdata_hip.h section 3n): wp(n, nx, nzm [, ntracers]), psfc(n, nx
+    ! [, ntracers]), pflux(n, nzm [, ntracers]) (c_null_ptr: skipped); device arrays of the plan's precision, asynchronous
+    ! on the plan's stream; windowed plans are supported
+    integer(c_int) function mpdata_plan_sediment_device_c(plan, sl0, n, wp, psfc, pflux, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_sediment_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: wp, psfc, pflux
       integer(c_int), value :: first_tracer, ntracers
     end function
   end interface

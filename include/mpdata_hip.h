@@ -646,6 +646,79 @@ int mpdata_subside_device(int64_t ncrms, int nx, int nz, int ntracers, double* f
 int mpdata_subside_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float* f, const float* cb, const float* cc,
                               float* dsum, void* stream);
 
+/* ---- 3n. Sedimentation of a resident plan's tracers, in place (the per-step operator a host model applies to its
+ * precipitating water: SAM's precip_fall, falling along k with a fall speed that differs in every cell).  This section is
+ * the specification; the reference tree has no such routine.  For instance sl in [sl0, sl0 + n), tracer t in
+ * [first_tracer, first_tracer + ntracers), interior column i = 1 .. nx, level k = 1 .. nzm, nzm = nz - 1:
+ *   Fz(i,k)   = wp(sl,i,k,t) * f(i,k)                      k = 1 .. nzm   (the flux through the LOWER face of cell k,
+ *                                                                          positive downward)
+ *   Fz(i,nz)  = +0                                                        (nothing enters through the top)
+ *   ir(k)     = 1 / (rho(sl,k) * adz(sl,k))                               (as in 3l; rho, adz are the plan's)
+ *   f(i,k)    = f(i,k) - (Fz(i,k) - Fz(i,k+1)) * ir(k)
+ *   psfc(sl,i,t)  = Fz(i,1)                                               (NULL: skipped) what reaches the surface
+ *   pflux(sl,k,t) : s = +0;  do i = 1, nx:  s = s + Fz(i,k)     k = 1 .. nzm   (NULL: skipped)
+ * Every f on the right-hand side is the value BEFORE the call (Jacobi).  Every operation is rounded once in the plan's
+ * precision, in exactly this association; nothing is contracted and the divide is IEEE, so EXACT and FAST plans give the
+ * same bits.  The library does not look at the sign of wp: in SAM's terms the caller folds rhow(k) v_t dtn / dz into it.
+ * wp = 0 keeps every bit of f, except that a -0.0 may come back as +0.0.  NaN and infinities are outside the contract.
+ * All arrays are of the plan's precision, reference layout, instance index fastest, leading dimension n (the block's
+ * first instance at index 0), tightly packed:
+ *   wp    (n, nx, nzm [, ntracers])   one field per tracer of the call, interior columns only; required
+ *   psfc  (n, nx [, ntracers])        may be NULL
+ *   pflux (n, nzm [, ntracers])       may be NULL
+ * Towards the rest of a plan:
+ *   halo marks   only interior columns change; halo columns are neither read nor written.  GIVEN plans: halos keep every
+ *     bit.  PERIODIC plans: no wrap is launched before the call, because nothing couples in x; the halo marks of the
+ *     range are cleared afterwards, so the next run or read-back hands out wrapped halos of the new field.
+ *   windowed plans (3e, nz > 238) are supported.  An owned level reads f(k+1), one level outside the owned range, so the
+ *     call first refreshes the seams of the tracers of the range that a run has left stale, as a run does.  It then
+ *     writes OWNED levels only, each with wp and ir of the tall level it stands for; psfc is written by the owner of tall
+ *     level 1, pflux by each level's owner.  The seam marks of the range are cleared afterwards.  wp is addressed by tall
+ *     level directly from the caller's array: nothing is cut into windows.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 whenever the block holds it (on a windowed plan the
+ *     phantom of the inner plan is restored behind the call, as in 3m).
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded; padding slots, neighbours in a tile,
+ *     instances and tracers outside the ranges, flux, u, w, rho, rhow, adz, the held-velocity flags, the boundary mode and
+ *     the timing pair keep every bit.  The call is outside the run's event pair; the plan need not hold velocities.
+ * A kernel of its own on every kind of plan, not fused into the run.  Wave-major and windowed plans: wp is read WHERE IT
+ * LIES -- no conversion pass, no byte of it written to device memory, the plan's diffusion buffer not used.  A workgroup
+ * owns the whole tiles of a group of 16 adjacent 8-byte elements of the instance axis (16 instances fp64, 32 fp32: a row
+ * of wp of the group is whole 128-byte lines in an aligned whole-plan call; fewer where the levels would not fit 40 KiB
+ * of LDS) and, per batch of columns, copies the group's rows of wp into LDS re-laid as [column][unit][level]; f is read
+ * once and written once, Fz(k+1) comes by a shuffle of the products just formed, at a wave's last lane from a load; psfc
+ * is one level's products, formed by a small kernel in front while f is the old field.
+ * Every load of f precedes a barrier and every store follows it, so the in-place update is race-free by construction.
+ * Reference-layout plans and the array forms write the new interior to a scratch array (the plan's diffusion buffer of
+ * 3l; an allocation of the call's own in the array forms) and copy it back by a second kernel on the same stream.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range, a null wp; in the array forms bad sizes
+ * (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null f, rho or adz, then a null wp.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3m (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.  psfc and pflux may both be NULL.
+ * Time on the MI355X (docs/EXPERIMENTS.md U, tools/sediment_bench.py), 65536 x 32 x 28, one tracer, cold: 0.324 ms fp64,
+ * 0.168 ms fp32 -- 4.2 / 4.0 TB/s of the algorithmic bytes (the interior of f read once and written once, wp read once:
+ * 3 nx nzm ncrms reals, 1.359 GB fp64).  Against the parent's calls in the same run: 0.75 x / 0.72 x
+ * mpdata_plan_export_device + mpdata_plan_import_device of f alone (the old route without the caller's kernel), 1.40 x /
+ * 1.44 x mpdata_plan_level_add_device (no per-cell field), 0.63 x / 0.62 x mpdata_plan_diffuse_device (a per-cell field of
+ * the same size through a conversion pass).  Said plainly: the rate is still BELOW the 4.7 / 4.4 TB/s at which diffuse moves
+ * all its bytes, the conversion pass included (by 10 % and 9 %), so the call is not bound by its bytes yet -- the staging
+ * through LDS with one barrier per batch and one per round is.  psfc and pflux together add 25 %, most of it the psfc
+ * kernel, whose reads of one level of f use two of seven 64-byte sectors of a column chunk. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_sediment_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* wp, void* psfc, void* pflux,
+                                int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3m host forms) */
+int mpdata_plan_sediment(mpdata_plan* plan, int64_t sl0, int64_t n, const double* wp, double* psfc, double* pflux);
+int mpdata_plan_sediment_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* wp, float* psfc, float* pflux);
+/* the same on instances [sl0, sl0+n) of reference-layout DEVICE arrays f(ncrms,-2:nx+3,1,nzm[,ntracers]), rho(ncrms,nzm),
+ * adz(ncrms,nzm) (leading dimension ncrms); wp, psfc, pflux as above (leading dimension n).  Enqueued on `stream`; the
+ * call allocates its scratch array and returns when the work is done and the scratch is freed. */
+int mpdata_sediment_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                           const double* adz, const double* wp, double* psfc, double* pflux, void* stream);
+int mpdata_sediment_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                               const float* adz, const float* wp, float* psfc, float* pflux, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
