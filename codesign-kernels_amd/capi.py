@@ -155,6 +155,14 @@ def lib():
         for name in ("mpdata_sediment_device", "mpdata_sediment_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 6 + [vp]
+        L.mpdata_plan_vsolve_device.restype = ci
+        L.mpdata_plan_vsolve_device.argtypes = [vp, i64, i64, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_vsolve", "mpdata_plan_vsolve_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp, dp]
+        for name in ("mpdata_vsolve_device", "mpdata_vsolve_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 4 + [vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -879,6 +887,26 @@ class Plan:
                                            ("pflux", pflux, (n, nzm), True))]
         _check(getattr(lib(), "mpdata_plan_sediment" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def vsolve(self, lo, di, up, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """Implicit vertical solve of f in place (include/mpdata_hip.h 3o) on the interior columns of instances [sl0, sl0+n)
+        (default: the rest of the plan from sl0): f(i,.) := x with lo(k) x(k-1) + di(k) x(k) + up(k) x(k+1) = f(i,k), without
+        pivoting, on the plan's stream (mpdata_plan_vsolve_device).  Reference-layout DEVICE tensors of the plan's
+        precision, shapes vsolve_shapes(n, nz): lo, di, up (nzm, n), shared by the columns and the tracers.  The tracers
+        are first_tracer .. +ntr-1, ntr = ntracers (else 1).  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        ntr, _ = self._block_ntr(None, ntracers)
+        sh = vsolve_shapes(n, self.dims[2])
+        ptrs = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("lo", lo), ("di", di), ("up", up))]
+        _check(lib().mpdata_plan_vsolve_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
+
+    def vsolve_host(self, lo, di, up, sl0=0, n=None):
+        """The same for all tracers from HOST arrays (numpy, Fortran order): lo, di, up (n, nzm), synchronous
+        (mpdata_plan_vsolve[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        ptrs = [None if a is None else self._block_host(a, name, (n, nzm)) for name, a in (("lo", lo), ("di", di), ("up", up))]
+        _check(getattr(lib(), "mpdata_plan_vsolve" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1056,6 +1084,32 @@ def sediment(f, rho, adz, wp, psfc=None, pflux=None, sl0=0, n=None, stream=None)
     ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("wp", wp), ("psfc", psfc), ("pflux", pflux))]
     fn = lib().mpdata_sediment_device if f.dtype == torch.float64 else lib().mpdata_sediment_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, *ptrs, _stream_handle(stream)))
+
+
+def vsolve_shapes(n, nz):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a vsolve call on n instances: lo, di, up
+    (nzm, n)."""
+    n, nz = int(n), int(nz)
+    return {"lo": (nz - 1, n), "di": (nz - 1, n), "up": (nz - 1, n)}
+
+
+def vsolve(f, lo, di, up, sl0=0, n=None, stream=None):
+    """Implicit vertical solve (include/mpdata_hip.h 3o) of instances [sl0, sl0+n) (default: the rest from sl0) of a
+    reference-layout DEVICE tensor f ([ntr,] nzm, nx+6, ncrms), float64 or float32, in place; lo, di, up of the same dtype
+    with the shapes of vsolve_shapes(n, nz).  Enqueued on `stream`; returns when the work is done (mpdata_vsolve_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"vsolve: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = vsolve_shapes(n, nzm + 1)
+    ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("lo", lo), ("di", di), ("up", up))]
+    fn = lib().mpdata_vsolve_device if f.dtype == torch.float64 else lib().mpdata_vsolve_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, *ptrs, _stream_handle(stream)))
 
 
 def subside_device(f, cb, cc, dsum=None, stream=None):

@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3n).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_sediment.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3o).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_vsolve.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays.
 #include <cstring>
 
@@ -12,6 +12,7 @@
 #include "mpdata_sediment.h"
 #include "mpdata_stats.h"
 #include "mpdata_subside.h"
+#include "mpdata_vsolve.h"
 
 using namespace mpd;
 
@@ -738,5 +739,103 @@ int mpdata_sediment_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t 
 int mpdata_sediment_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
                                const float* adz, const float* wp, float* psfc, float* pflux, void* stream) {
   return sediment_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, wp, psfc, pflux, stream, 4);
+}
+
+// ---- 3o: implicit vertical solve of f, in place.  Reads lo, di, up, rewrites the INTERIOR columns of f of the block's
+// instances and the tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not touched and no event is
+// recorded.
+//   halo marks  halo columns are neither read nor written, so no wrap is launched in front; afterwards a periodic plan's
+//               halos are copies of the OLD interior: the marks of the range are cleared and the next run or read-back
+//               wraps again;
+//   seam marks  the recurrence reads and writes OWNED levels only, which are right whatever the seams hold (as the
+//               column integrals of 3k argue): no refresh in front; afterwards the other copies are stale: the marks of
+//               the range are cleared and the next run refreshes them;
+//   phantom     follows the plan's last slot inside the kernel (mpdata_vsolve.h); on a windowed plan the kernel leaves it
+//               alone and the refresh of the inner plan follows as after a seam refresh.
+// Every kind of plan: a small kernel in front writes the factors p and g (2 n nzm reals) into the plan's diffusion buffer.
+static int plan_vsolve(mpdata_plan* p, int64_t sl0, int64_t n, const void* lo, const void* di, const void* up, int first, int count) {
+  const int nzm = p->nz - 1;
+  const size_t kb = (size_t)n * nzm * p->eb;
+  int rc = plan_dbuf(p, 2 * kb);
+  if (rc) return rc;
+  void* const pf = p->dbuf;
+  void* const gf = (char*)p->dbuf + kb;
+  HIP_TRY(mpdata_vsolve_factor(lo, di, up, p->eb, n, nzm, pf, gf, p->stream));
+  if (plan_walked(p)) {
+    MpdataVsolveJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.lo = lo; b.pg = pf;
+    HIP_TRY(mpdata_vsolve_wm(b, p->stream));
+    if (p->inner) {
+      memset(p->seam_ok + first, 0, (size_t)count);
+      if (sl0 + n == p->ncrms) rc = plan_phantom(p->inner, 0, first, count);
+      if (rc) return rc;
+    }
+  } else {
+    HIP_TRY(mpdata_vsolve_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, nzm, count, lo, pf, gf, p->stream));
+  }
+  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
+  return 0;
+}
+static int plan_vsolve_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* lo, const void* di,
+                             const void* up, int first, int count, int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!lo || !di || !up) return set_err(MPDATA_EINVAL, "%s: null %s", what, !lo ? "lo" : !di ? "di" : "up");
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_vsolve_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* lo, const void* di, const void* up, int first_tracer,
+                              int ntracers) {
+  const int rc = plan_vsolve_check("mpdata_plan_vsolve_device", p, sl0, n, lo, di, up, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_vsolve(p, sl0, n, lo, di, up, first_tracer, ntracers);
+}
+static int plan_vsolve_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* lo, const void* di, const void* up, int eb) {
+  int rc = plan_vsolve_check("mpdata_plan_vsolve", p, sl0, n, lo, di, up, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb;
+  HostArr a[3] = {{lo, kb, false}, {di, kb, false}, {up, kb, false}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_vsolve(p, sl0, n, a[0].dev, a[1].dev, a[2].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_vsolve(mpdata_plan* p, int64_t sl0, int64_t n, const double* lo, const double* di, const double* up) {
+  return plan_vsolve_host(p, sl0, n, lo, di, up, 8);
+}
+int mpdata_plan_vsolve_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* lo, const float* di, const float* up) {
+  return plan_vsolve_host(p, sl0, n, lo, di, up, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call).  The factors go through a
+// scratch array of the call's own, which is freed when the work is done: the call returns after it.
+static int vsolve_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* lo, const void* di,
+                        const void* up, void* stream, int eb) {
+  const int rc = array_sizes("mpdata_vsolve_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
+    return set_err(MPDATA_EINVAL, "mpdata_vsolve_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
+                   (long long)(sl0 + n), (long long)ncrms);
+  if (!f) return set_err(MPDATA_EINVAL, "mpdata_vsolve_device: null f");
+  if (!lo || !di || !up) return set_err(MPDATA_EINVAL, "mpdata_vsolve_device: null %s", !lo ? "lo" : !di ? "di" : "up");
+  const size_t kb = (size_t)n * (nz - 1) * eb;
+  void* scratch = nullptr;
+  HIP_TRY(hipMalloc(&scratch, 2 * kb));
+  void* const gf = (char*)scratch + kb;
+  hipError_t e = mpdata_vsolve_factor(lo, di, up, eb, n, nz - 1, scratch, gf, (hipStream_t)stream);
+  if (e == hipSuccess) e = mpdata_vsolve_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, lo, scratch, gf, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(scratch);
+  HIP_TRY(e);
+  return 0;
+}
+int mpdata_vsolve_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* lo,
+                         const double* di, const double* up, void* stream) {
+  return vsolve_array(ncrms, nx, nz, ntracers, sl0, n, f, lo, di, up, stream, 8);
+}
+int mpdata_vsolve_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* lo,
+                             const float* di, const float* up, void* stream) {
+  return vsolve_array(ncrms, nx, nz, ntracers, sl0, n, f, lo, di, up, stream, 4);
 }
 }  // extern "C"

@@ -59,6 +59,10 @@ module mpdata_hip_mod
   ! binding for both precisions as for 3m; mpdata_plan_sediment[_f32] and mpdata_sediment[_f32]_device have no Fortran
   ! interface yet
   public :: mpdata_plan_sediment_device_c
+  ! implicit vertical solve of a resident plan's tracers, in place (include/mpdata_hip.h section 3o): the device form only,
+  ! one binding for both precisions as for 3m / 3n; mpdata_plan_vsolve[_f32] and mpdata_vsolve[_f32]_device have no
+  ! Fortran interface yet
+  public :: mpdata_plan_vsolve_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -474,6 +478,17 @@ module mpdata_hip_mod
       type(c_ptr), value :: plan
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: wp, psfc, pflux
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! ---- implicit vertical solve of f in place (include/mpdata_hip.h section 3o): lo, di, up(n, nzm), shared by the
+    ! columns and the tracers; device arrays of the plan's precision, asynchronous on the plan's stream; windowed plans
+    ! are supported
+    integer(c_int) function mpdata_plan_vsolve_device_c(plan, sl0, n, lo, di, up, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_vsolve_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: lo, di, up
       integer(c_int), value :: first_tracer, ntracers
     end function
   end interface

@@ -719,6 +719,90 @@ int mpdata_sediment_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t 
 int mpdata_sediment_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
                                const float* adz, const float* wp, float* psfc, float* pflux, void* stream);
 
+/* ---- 3o. Implicit vertical solves of a resident plan's tracers, in place (the implicit half of a vertical operator of a
+ * host model: backward-Euler vertical diffusion, implicit subsidence, implicit damping or nudging -- a tridiagonal solve
+ * along k per column).  This section is the specification; the reference tree has no such routine.  For instance sl in
+ * [sl0, sl0 + n), tracer t in [first_tracer, first_tracer + ntracers), interior column i = 1 .. nx, nzm = nz - 1, the call
+ * replaces f(i,.) by the solution x of
+ *   lo(sl,k) x(k-1) + di(sl,k) x(k) + up(sl,k) x(k+1) = f(i,k)          k = 1 .. nzm
+ * computed exactly as follows, each statement one rounded operation in the plan's precision, nothing contracted, the
+ * divide IEEE:
+ *   per (sl,k), independent of column and tracer:
+ *     p(1) = 1 / di(1);                                          g(1) = up(1) * p(1)
+ *     k = 2 .. nzm:   m = lo(k) * g(k-1);  d = di(k) - m;  p(k) = 1 / d;  g(k) = up(k) * p(k)     (g(nzm) is not used)
+ *   per (sl,i,t), every f the value BEFORE the call:
+ *     y(1) = f(i,1) * p(1)
+ *     k = 2 .. nzm:   m = lo(k) * y(k-1);  r = f(i,k) - m;  y(k) = r * p(k)
+ *     x(nzm) = y(nzm)
+ *     k = nzm-1 .. 1: m = g(k) * x(k+1);   x(k) = y(k) - m
+ *     f(i,k) = x(k)
+ * lo, di, up (n, nzm): of the plan's precision, reference layout, instance index fastest, leading dimension n (the block's
+ * first instance at index 0), tightly packed, shared by all columns and all tracers of the call; lo(:,1) and up(:,nzm) are
+ * never read.  All three are required.
+ * NO PIVOTING: a matrix that needs none is the caller's duty -- diagonal dominance, as every implicit diffusion or upwind
+ * matrix has.  A zero pivot, NaN and infinities are outside the contract.  EXACT and FAST plans give the same bits.
+ * lo = up = 0, di = 1 keeps every bit of f, except that a -0.0 may come back as +0.0 (0 * y is -0.0 for a negative y, and
+ * -0.0 - -0.0 = +0.0).  In the caller's terms: lo = -a(k), up = -c(k), di = 1 + a(k) + c(k) is backward-Euler vertical
+ * diffusion with a horizontally uniform diffusivity (the caller folds dtn K / dz^2 and the density weights into a and c: INTEGRATION.md); it is
+ * also the implicit counterpart of 3m's cb, cc.  The library does not look at signs.
+ * Towards the rest of a plan:
+ *   halo marks   only interior columns are read or written.  No wrap is launched before the call, because nothing couples
+ *     in x.  GIVEN plans: halos keep every bit.  PERIODIC plans: the halo marks of the range are cleared afterwards, so the
+ *     next run or read-back hands out wrapped halos of the new field.
+ *   windowed plans (3e, nz > 238) are supported.  Only OWNED levels are read and written, each with the coefficients of
+ *     the tall level it stands for; the coefficients are addressed by tall level in the caller's arrays: nothing is cut
+ *     into windows.  Owned levels are right whatever the seams hold (as 3k argues), so no seam refresh is needed in
+ *     front; the seam marks of the range are cleared afterwards.  The recurrence crosses the windows in both directions:
+ *     a workgroup walks the windows of its instances upward with y(k-1) carried, then downward with x(k+1) carried.  The
+ *     merged result is the tall solve bit for bit.  This costs a second read and write of f on tall plans; a plain plan
+ *     reads f once and writes it once.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 whenever the block holds it (on a windowed plan the
+ *     phantom of the inner plan is restored behind the call, as in 3m / 3n).
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded; padding slots, neighbours in a group,
+ *     instances and tracers outside the ranges, flux, u, w, rho, rhow, adz, the held-velocity flags, the boundary mode and
+ *     the timing pair keep every bit.  The call is outside the run's event pair; the plan need not hold velocities.
+ * Kernels of their own on every kind of plan, not fused into the run.  A small kernel in front forms p and g once per call
+ * (one thread per instance, sequential in k) into the plan's diffusion buffer of 3l (2 n nzm reals; an allocation of the
+ * call's own in the array forms), so the divides stay out of the hot kernel and every column takes the same bits.
+ * Wave-major and windowed plans: the lanes of the plan layout run along k, the recurrence too, so a workgroup stages the
+ * column slots of 16 adjacent 8-byte elements of the instance axis (fewer where the levels would not fit 40 KiB of LDS)
+ * and a batch of columns through LDS as 3k does, together with lo, p, g of those instances; a lane per (instance element,
+ * column) sweeps up and down in LDS in place, and the waves store LDS back to f as the same linear streams.  Every global
+ * load of a stage precedes a barrier and every global store follows the sweeps' barrier; workgroups own disjoint elements:
+ * the in-place update is race-free by construction.  Reference-layout plans and the array forms: one thread per instance
+ * and (column, tracer) row owns its column and sweeps it in place.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range, a null lo, di or up; in the array forms
+ * bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null f, then a null lo, di or up.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3n (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md V, tools/vsolve_bench.py), 65536 x 32 x 28, one tracer, cold: 0.263 ms fp64,
+ * 0.166 ms fp32 (the factor kernel included) -- 3.4 / 2.7 TB/s of the algorithmic bytes (the interior of f read once and
+ * written once: 2 nx nzm ncrms reals, 0.906 GB fp64).  Against the parent's calls in the same run: 0.62 x / 0.74 x
+ * mpdata_plan_export_device + mpdata_plan_import_device of f alone (the old route without the caller's kernel), 1.99 x /
+ * 2.20 x mpdata_plan_column_path_device (the same staging, read only: the call costs two of them), 1.15 x / 1.44 x
+ * mpdata_plan_level_add_device (the same bytes and six halo columns more, no staging).  A block of 64 instances: 0.018 ms.
+ * Said plainly: the call is bound by the staging through LDS and its two barriers, not by its bytes -- only half of a
+ * workgroup's lanes sweep (16 instances x 8 columns), and level_add moves 1.4 x the rate.  Tall plans are worse than the
+ * plan: at 4096 x 32 x 300 (6 windows of 56 levels) 1.00 ms fp64, 0.70 ms fp32, 0.63 / 0.45 TB/s, 2.8 x / 2.3 x the export +
+ * import of f -- 5.5 x the plain time per byte where two passes explain 2 x: a batch is 2 columns there, so 32 of 256 lanes
+ * sweep, and lo, p, g are staged again for every window and pass.  On a tall plan the call still saves the caller's kernel
+ * and the host-side bookkeeping, not time. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_vsolve_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* lo, const void* di, const void* up,
+                              int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3n host forms) */
+int mpdata_plan_vsolve(mpdata_plan* plan, int64_t sl0, int64_t n, const double* lo, const double* di, const double* up);
+int mpdata_plan_vsolve_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* lo, const float* di, const float* up);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm[,ntracers]) (leading
+ * dimension ncrms); lo, di, up as above (leading dimension n).  Enqueued on `stream`; the call allocates its scratch array
+ * and returns when the work is done and the scratch is freed. */
+int mpdata_vsolve_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* lo,
+                         const double* di, const double* up, void* stream);
+int mpdata_vsolve_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* lo,
+                             const float* di, const float* up, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
