@@ -25,6 +25,7 @@ EINVAL, EUNSUPPORTED, ESTATE, ECOMM = -1, -2, -3, -4   # MPDATA_E* of include/mp
 LAYOUT_REFERENCE, LAYOUT_WAVEMAJOR = 0, 1
 BOUNDARY_GIVEN, BOUNDARY_PERIODIC = 0, 1   # MPDATA_BOUNDARY_* (include/mpdata_hip.h section 3a)
 LEVEL_ADD, LEVEL_ADD_CLIP = 0, 1           # MPDATA_LEVEL_ADD* (include/mpdata_hip.h section 3i)
+CELL_ADD, CELL_ADD_CLIP = 0, 1             # MPDATA_CELL_ADD* (include/mpdata_hip.h section 3p)
 
 _lib = None
 
@@ -163,6 +164,14 @@ def lib():
         for name in ("mpdata_vsolve_device", "mpdata_vsolve_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 4 + [vp]
+        L.mpdata_plan_cell_add_device.restype = ci
+        L.mpdata_plan_cell_add_device.argtypes = [vp, i64, i64, vp, ctypes.c_double, ci, vp, ci, ci]
+        for name, cf in (("mpdata_plan_cell_add", ctypes.c_double), ("mpdata_plan_cell_add_f32", ctypes.c_float)):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, cf, ci, dp]
+        for name, cf in (("mpdata_cell_add_device", ctypes.c_double), ("mpdata_cell_add_f32_device", ctypes.c_float)):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, cf, ci, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -907,6 +916,34 @@ class Plan:
         ptrs = [None if a is None else self._block_host(a, name, (n, nzm)) for name, a in (("lo", lo), ("di", di), ("up", up))]
         _check(getattr(lib(), "mpdata_plan_vsolve" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def cell_add(self, s, c=1.0, mode=CELL_ADD, dsum=None, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """Per-cell sources of f in place (include/mpdata_hip.h 3p) on the interior columns of instances [sl0, sl0+n)
+        (default: the rest of the plan from sl0): f += c * s, the product and the sum each rounded once; mode CELL_ADD
+        (default) or CELL_ADD_CLIP (max(0, .) of the sum), on the plan's stream (mpdata_plan_cell_add_device).
+        Reference-layout DEVICE tensors of the plan's precision, shapes cell_add_shapes(n, nx, nz, ntr): s ([ntr,] nzm, nx,
+        n), one field per tracer, read where it lies; dsum ([ntr,] nzm, n) or None (skipped), the increment actually
+        applied summed over the interior columns.  c is rounded once to the plan's precision.  The tracers are
+        first_tracer .. +ntr-1, ntr = ntracers, or the leading axis of a 4-d s (else 1); dsum carries that axis exactly
+        when s does.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        nx, nz = self.dims[1], self.dims[2]
+        lead = s[..., 0, :] if s is not None else dsum
+        ntr, axis = self._block_ntr(lead, ntracers)
+        sh = cell_add_shapes(n, nx, nz, ntr if axis else None)
+        ptrs = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("s", s), ("dsum", dsum))]
+        _check(lib().mpdata_plan_cell_add_device(self._p, int(sl0), n, ptrs[0], float(c), int(mode),
+                                                 ptrs[1], int(first_tracer), ntr))
+
+    def cell_add_host(self, s, c=1.0, mode=CELL_ADD, dsum=None, sl0=0, n=None):
+        """The same for all tracers from HOST arrays (numpy, Fortran order): s (n, nx, nzm[, ntracers]), dsum (n, nzm[,
+        ntracers]) or None (written), synchronous (mpdata_plan_cell_add[_f32])."""
+        n = self._block_n(sl0, n)
+        nx, nzm = self.dims[1], self.dims[2] - 1
+        ptrs = [None if a is None else self._block_host(a, name, want, True, out)
+                for name, a, want, out in (("s", s, (n, nx, nzm), False), ("dsum", dsum, (n, nzm), True))]
+        _check(getattr(lib(), "mpdata_plan_cell_add" + self._sfx)(self._p, int(sl0), n, ptrs[0], float(c),
+                                                                  int(mode), ptrs[1]))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1084,6 +1121,35 @@ def sediment(f, rho, adz, wp, psfc=None, pflux=None, sl0=0, n=None, stream=None)
     ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("wp", wp), ("psfc", psfc), ("pflux", pflux))]
     fn = lib().mpdata_sediment_device if f.dtype == torch.float64 else lib().mpdata_sediment_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, *ptrs, _stream_handle(stream)))
+
+
+def cell_add_shapes(n, nx, nz, ntracers=None):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a cell_add call on n instances: s
+    ([ntracers,] nzm, nx, n), dsum ([ntracers,] nzm, n); ntracers None: one tracer without the leading axis."""
+    lead = () if ntracers is None else (int(ntracers),)
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {"s": lead + (nz - 1, nx, n), "dsum": lead + (nz - 1, n)}
+
+
+def cell_add(f, s, c=1.0, mode=CELL_ADD, dsum=None, sl0=0, n=None, stream=None):
+    """Per-cell sources (include/mpdata_hip.h 3p) of instances [sl0, sl0+n) (default: the rest from sl0) of a
+    reference-layout DEVICE tensor f ([ntr,] nzm, nx+6, ncrms), float64 or float32, in place: f += c * s on the interior
+    columns, mode CELL_ADD (default) or CELL_ADD_CLIP; s, dsum of the same dtype with the shapes of cell_add_shapes(n, nx,
+    nz, ntr) (dsum may be None).  Asynchronous on `stream` (mpdata_cell_add_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"cell_add: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = cell_add_shapes(n, nxp6 - 6, nzm + 1, nt if f.dim() == 4 else None)
+    ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("s", s), ("dsum", dsum))]
+    fn = lib().mpdata_cell_add_device if f.dtype == torch.float64 else lib().mpdata_cell_add_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, ptrs[0], float(c), int(mode), ptrs[1],
+              _stream_handle(stream)))
 
 
 def vsolve_shapes(n, nz):

@@ -1,8 +1,9 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3o).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_vsolve.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3p).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_cell_add.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays.
 #include <cstring>
 
+#include "mpdata_cell_add.h"
 #include "mpdata_column_path.h"
 #include "mpdata_courant.h"
 #include "mpdata_diffuse.h"
@@ -70,6 +71,10 @@ int plan_uw_state(const char* what, const mpdata_plan* p, bool need_u, bool need
 int plan_state(const char* what, const mpdata_plan* p, int eb, bool need_u = false, bool need_w = false) {
   const int rc = eb ? plan_check(p, eb) : 0;
   return rc ? rc : plan_uw_state(what, p, need_u, need_w);
+}
+int cell_add_mode(const char* what, int mode) {
+  if (mode != MPDATA_CELL_ADD && mode != MPDATA_CELL_ADD_CLIP) return set_err(MPDATA_EINVAL, "%s: unknown mode %d", what, mode);
+  return 0;
 }
 int level_add_mode(const char* what, int mode) {
   if (mode != MPDATA_LEVEL_ADD && mode != MPDATA_LEVEL_ADD_CLIP) return set_err(MPDATA_EINVAL, "%s: unknown mode %d", what, mode);
@@ -837,5 +842,90 @@ int mpdata_vsolve_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl
 int mpdata_vsolve_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* lo,
                              const float* di, const float* up, void* stream) {
   return vsolve_array(ncrms, nx, nz, ntracers, sl0, n, f, lo, di, up, stream, 4);
+}
+
+// ---- 3p: per-cell sources of f, in place.  Reads s, rewrites the INTERIOR columns of f of the block's instances and the
+// tracer range; flux, u, w, rho, rhow, adz and the boundary mode are not touched and no event is recorded.
+//   halo marks  halo columns are neither read nor written, so no wrap is launched in front; afterwards a periodic plan's
+//               halos are copies of the OLD interior: the marks of the range are cleared and the next run or read-back
+//               wraps again;
+//   seam marks  the operator is pointwise and reads and writes OWNED levels only, which are right whatever the seams
+//               hold: no refresh in front; afterwards the other copies are stale: the marks of the range are cleared and
+//               the next run refreshes them;
+//   phantom     follows the plan's last slot inside the kernel (mpdata_cell_add.h); on a windowed plan the refresh of the
+//               inner plan follows as after a seam refresh.
+// Every kind of plan: s is read where it lies and f is updated in place; the diffusion buffer is not used.
+static int plan_cell_add(mpdata_plan* p, int64_t sl0, int64_t n, const void* s, double c, int mode, void* dsum, int first, int count) {
+  const int clip = mode == MPDATA_CELL_ADD_CLIP;
+  if (plan_walked(p)) {
+    MpdataCellAddJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.s = s; b.c = c; b.clip = clip; b.dsum = dsum;
+    HIP_TRY(mpdata_cell_add_wm(b, p->stream));
+    if (p->inner) {
+      memset(p->seam_ok + first, 0, (size_t)count);
+      const int rc = sl0 + n == p->ncrms ? plan_phantom(p->inner, 0, first, count) : 0;
+      if (rc) return rc;
+    }
+  } else {
+    HIP_TRY(mpdata_cell_add_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, s, c, clip, dsum, p->stream));
+  }
+  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
+  return 0;
+}
+static int plan_cell_add_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* s, int mode, int first,
+                               int count, int eb) {
+  int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!s) return set_err(MPDATA_EINVAL, "%s: null s", what);
+  rc = cell_add_mode(what, mode);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_cell_add_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* s, double c, int mode, void* dsum, int first_tracer,
+                                int ntracers) {
+  const int rc = plan_cell_add_check("mpdata_plan_cell_add_device", p, sl0, n, s, mode, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_cell_add(p, sl0, n, s, c, mode, dsum, first_tracer, ntracers);
+}
+static int plan_cell_add_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* s, double c, int mode, void* dsum, int eb) {
+  int rc = plan_cell_add_check("mpdata_plan_cell_add", p, sl0, n, s, mode, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * p->ntracers * eb;
+  HostArr a[2] = {{s, kb * p->nx, false}, {dsum, kb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_cell_add(p, sl0, n, a[0].dev, c, mode, a[1].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_cell_add(mpdata_plan* p, int64_t sl0, int64_t n, const double* s, double c, int mode, double* dsum) {
+  return plan_cell_add_host(p, sl0, n, s, c, mode, dsum, 8);
+}
+int mpdata_plan_cell_add_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* s, float c, int mode, float* dsum) {
+  return plan_cell_add_host(p, sl0, n, s, (double)c, mode, dsum, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): in place, asynchronous
+static int cell_add_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* s, double c, int mode,
+                          void* dsum, void* stream, int eb) {
+  int rc = array_sizes("mpdata_cell_add_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
+    return set_err(MPDATA_EINVAL, "mpdata_cell_add_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
+                   (long long)(sl0 + n), (long long)ncrms);
+  if (!f) return set_err(MPDATA_EINVAL, "mpdata_cell_add_device: null f");
+  if (!s) return set_err(MPDATA_EINVAL, "mpdata_cell_add_device: null s");
+  rc = cell_add_mode("mpdata_cell_add_device", mode);
+  if (rc) return rc;
+  HIP_TRY(mpdata_cell_add_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, s, c, mode == MPDATA_CELL_ADD_CLIP, dsum, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_cell_add_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* s, double c,
+                           int mode, double* dsum, void* stream) {
+  return cell_add_array(ncrms, nx, nz, ntracers, sl0, n, f, s, c, mode, dsum, stream, 8);
+}
+int mpdata_cell_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* s, float c,
+                               int mode, float* dsum, void* stream) {
+  return cell_add_array(ncrms, nx, nz, ntracers, sl0, n, f, s, (double)c, mode, dsum, stream, 4);
 }
 }  // extern "C"

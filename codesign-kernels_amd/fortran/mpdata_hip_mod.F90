@@ -63,6 +63,11 @@ module mpdata_hip_mod
   ! one binding for both precisions as for 3m / 3n; mpdata_plan_vsolve[_f32] and mpdata_vsolve[_f32]_device have no
   ! Fortran interface yet
   public :: mpdata_plan_vsolve_device_c
+  ! per-cell sources of a resident plan's tracers, in place (include/mpdata_hip.h section 3p): the device form only, one
+  ! binding for both precisions -- its one real, the factor c, is a double in C for both; mpdata_plan_cell_add[_f32] and
+  ! mpdata_cell_add[_f32]_device have no Fortran interface yet
+  public :: mpdata_plan_cell_add_device_c
+  integer(c_int), parameter, public :: MPDATA_CELL_ADD = 0, MPDATA_CELL_ADD_CLIP = 1
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -489,6 +494,25 @@ module mpdata_hip_mod
       type(c_ptr), value :: plan
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: lo, di, up
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+  end interface
+
+  ! an interface block of its own for the bindings that take a REAL by value (the factor c below): the block above holds
+  ! integers, handles and addresses only
+  interface
+    ! ---- per-cell sources of f in place (include/mpdata_hip.h section 3p): s(n, nx, nzm [, ntracers]), dsum(n, nzm
+    ! [, ntracers]) (c_null_ptr: skipped); device arrays of the plan's precision, asynchronous on the plan's stream; c is a
+    ! double for both precisions (rounded once to the plan's); mode MPDATA_CELL_ADD[_CLIP]; windowed plans are supported
+    integer(c_int) function mpdata_plan_cell_add_device_c(plan, sl0, n, s, c, mode, dsum, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_cell_add_device")
+      import :: c_int, c_int64_t, c_ptr, c_double
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: s
+      real(c_double), value :: c
+      integer(c_int), value :: mode
+      type(c_ptr), value :: dsum
       integer(c_int), value :: first_tracer, ntracers
     end function
   end interface

@@ -803,6 +803,85 @@ int mpdata_vsolve_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl
 int mpdata_vsolve_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* lo,
                              const float* di, const float* up, void* stream);
 
+/* ---- 3p. Per-cell sources of a resident plan's tracers, in place (the most general write path of a host model: an
+ * increment that differs in every cell -- radiative heating t(i,k) = t(i,k) + qrad(i,k) * dtn, the tendency of a
+ * microphysics or chemistry scheme the library does not own, a source confined to some columns, a perturbation; 3i
+ * applies only increments that are uniform in x).  This section is the specification; the reference tree has no such
+ * routine.  For instance sl in [sl0, sl0 + n), tracer t in [first_tracer, first_tracer + ntracers), interior column
+ * i = 1 .. nx, level k = 1 .. nzm, nzm = nz - 1, with b = sl - sl0:
+ *   p        = c * s(b,i,k,t)
+ *   g        = f(sl,i,k,t) + p
+ *   MPDATA_CELL_ADD_CLIP only:  g = max(0, g)
+ *   dsum(b,k,t) :  a = +0;  do i = 1, nx:  a = a + (g - f_old(sl,i,k,t))             (NULL: skipped)
+ *   f(sl,i,k,t) = g
+ * Every operation is rounded once in the plan's precision, in exactly this association; nothing is contracted, so EXACT
+ * and FAST plans give the same bits.  The factor c (a time step, a unit conversion) is passed by value, as a double to
+ * the device form, which serves both precisions; it is rounded ONCE to the plan's precision before use (c = 0.1 on an
+ * fp32 plan multiplies by (float)0.1).  MPDATA_CELL_ADD keeps the IEEE signs of zero (c = 0 or s = 0 keeps every bit of
+ * f, except that -0 + +0 = +0); under MPDATA_CELL_ADD_CLIP the sign of a zero f is unspecified, as in 3i, but dsum is
+ * still bit-defined: a running sum that starts at +0 never becomes -0.  NaN and infinities are outside the contract.
+ * dsum is the increment actually APPLIED, summed over the interior columns in rising order; under _CLIP it differs from
+ * c * s wherever the clip acted.  It is what a budget needs.
+ * All arrays are of the plan's precision, reference layout, instance index fastest, leading dimension n (the block's
+ * first instance at index 0), tightly packed, tracer slowest:
+ *   s    (n, nx, nzm [, ntracers])   one field per tracer of the call, interior columns only; required, only read
+ *   dsum (n, nzm [, ntracers])       may be NULL
+ * No byte outside these arrays is read or written.  Afterwards the plan behaves exactly as if the interior of f had been
+ * exported, changed as above and imported again.
+ * Towards the rest of a plan:
+ *   halo marks   only interior columns change; halo columns are neither read nor written.  GIVEN plans: halos keep every
+ *     bit.  PERIODIC plans: no wrap is launched, because nothing couples in x; the halo marks of the range are cleared
+ *     afterwards, so the next run or read-back hands out wrapped halos of the new field.
+ *   windowed plans (3e, nz > 238) are supported.  The operator is pointwise, so no seam refresh is needed in front: an
+ *     owned level is right whatever the seams hold (as 3k argues).  The scheme chosen: the call writes OWNED levels only,
+ *     each with s of the tall level it stands for, and clears the seam marks of the range afterwards; the next run
+ *     refreshes the other copies, whether the seams were fresh or stale at the call.  dsum of a level is written by that
+ *     level's owner.  s is addressed by tall level directly from the caller's array: nothing is cut into windows.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 whenever the block holds it (on a windowed plan the
+ *     phantom of the inner plan is restored behind the call, as in 3m / 3n).
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded -- no + 0.0 and no clip reach it: a
+ *     -0.0 or a negative value there stays; padding slots, neighbours in a tile, instances and tracers outside the
+ *     ranges, flux, u, w, rho, rhow, adz, the held-velocity flags, the boundary mode and the timing pair keep every bit.
+ *     The call is outside the run's event pair; the plan need not hold velocities.
+ * A kernel of its own on every kind of plan, not fused into the run.  Wave-major and windowed plans: s is read WHERE IT
+ * LIES, as 3n reads wp -- no conversion pass, no scratch buffer; f is read once and written once, s read once.  A
+ * workgroup owns the whole tiles of a group of 16 adjacent 8-byte elements of the instance axis (fewer where the levels
+ * would not fit 40 KiB of LDS) and, per batch of columns, copies the group's rows of s into one of TWO LDS buffers re-laid
+ * as [column][unit][level].  A lane reads and writes its own element of f only, so f needs no ordering; the one barrier
+ * of a batch orders the staging.  The kernel without dsum carries neither the sums nor their LDS.
+ * Reference-layout plans and the array forms: one thread per instance and (level, tracer) row, in place, no scratch array.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range, a null s, an unknown mode; in the array
+ * forms bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null f, then a null s, then the mode.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3o (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md W, tools/cell_add_bench.py, profiles/cell_add_bench.json), 65536 x 32 x 28, one
+ * tracer, cold: 0.319 ms fp64, 0.163 ms fp32 -- 4.3 / 4.2 TB/s of the algorithmic bytes (the interior of f read once and
+ * written once, s read once: 3 nx nzm ncrms reals, 1.359 GB fp64); the clip costs nothing, dsum 2 % fp64 and 15 % fp32.
+ * Against existing calls in the same run: 0.75 x / 0.70 x mpdata_plan_export_device + mpdata_plan_import_device of f alone
+ * (the old route without the caller's kernel), 1.40 x / 1.41 x mpdata_plan_level_add_device (no per-cell field), 1.01 x /
+ * 1.00 x mpdata_plan_sediment_device (the same bytes, a stencil, a second barrier per round and an edge load more).
+ * Said plainly: the call is NOT faster than sedimentation although it does less, so the barriers and the edge load were
+ * not what bounds 3n; what did move the time is loading the next batch's s into registers while a batch computes
+ * (0.396 -> 0.319 ms fp64).  Tall plans, 4096 x 32 x 300 (6 windows): 0.362 ms fp64, 0.251 ms fp32, 0.98 x / 0.82 x the
+ * export + import of f and 0.82 x / 0.86 x sedimentation -- on a tall fp64 plan the call saves the caller's kernel and the
+ * bookkeeping, hardly time. */
+#define MPDATA_CELL_ADD 0
+#define MPDATA_CELL_ADD_CLIP 1
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_cell_add_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* s, double c, int mode, void* dsum,
+                                int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3o host forms) */
+int mpdata_plan_cell_add(mpdata_plan* plan, int64_t sl0, int64_t n, const double* s, double c, int mode, double* dsum);
+int mpdata_plan_cell_add_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* s, float c, int mode, float* dsum);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm[,ntracers]) (leading
+ * dimension ncrms); s, dsum as above (leading dimension n).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_cell_add_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* s,
+                           double c, int mode, double* dsum, void* stream);
+int mpdata_cell_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* s,
+                               float c, int mode, float* dsum, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
