@@ -172,6 +172,14 @@ def lib():
         for name, cf in (("mpdata_cell_add_device", ctypes.c_double), ("mpdata_cell_add_f32_device", ctypes.c_float)):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, cf, ci, dp, vp]
+        L.mpdata_plan_column_step_device.restype = ci
+        L.mpdata_plan_column_step_device.argtypes = [vp, i64, i64, vp, ctypes.c_double, ci] + [vp] * 7 + [ci, ci]
+        for name, cf in (("mpdata_plan_column_step", ctypes.c_double), ("mpdata_plan_column_step_f32", ctypes.c_float)):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, cf, ci] + [dp] * 7
+        for name, cf in (("mpdata_column_step_device", ctypes.c_double), ("mpdata_column_step_f32_device", ctypes.c_float)):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, dp, dp, cf, ci] + [dp] * 7 + [vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -944,6 +952,40 @@ class Plan:
         _check(getattr(lib(), "mpdata_plan_cell_add" + self._sfx)(self._p, int(sl0), n, ptrs[0], float(c),
                                                                   int(mode), ptrs[1]))
 
+    def column_step_device(self, s=None, c=1.0, mode=CELL_ADD, cb=None, cc=None, wp=None, psfc=None, lo=None, di=None, up=None,
+                           sl0=0, n=None, first_tracer=0, ntracers=None):
+        """The fused column step of f in place (include/mpdata_hip.h 3q) on the interior columns of instances [sl0, sl0+n)
+        (default: the rest of the plan from sl0): up to four stages in the fixed order source (s, c, mode: 3p), subside (cb,
+        cc: 3m), sediment (wp, psfc: 3n), vsolve (lo, di, up: 3o), a stage present exactly when its tensors are given, with
+        one read and one write of f, on the plan's stream (mpdata_plan_column_step_device).  Bit for bit the sequence of
+        the single calls on the interior columns; halo columns are not touched and no horizontal sum is formed.
+        Reference-layout DEVICE tensors of the plan's precision, shapes column_step_shapes(n, nx, nz, ntr): s, wp ([ntr,]
+        nzm, nx, n), psfc ([ntr,] nx, n) or None, cb, cc, lo, di, up (nzm, n).  The tracers are first_tracer .. +ntr-1, ntr
+        = ntracers, or the leading axis of a 4-d s or wp (else 1).  Windowed plans are refused (EUNSUPPORTED)."""
+        n = self._block_n(sl0, n)
+        nx, nz = self.dims[1], self.dims[2]
+        lead = s[..., 0, :] if s is not None else (wp[..., 0, :] if wp is not None else psfc)
+        ntr, axis = self._block_ntr(lead, ntracers)
+        sh = column_step_shapes(n, nx, nz, ntr if axis else None)
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt())
+             for k, t in (("s", s), ("cb", cb), ("cc", cc), ("wp", wp), ("psfc", psfc), ("lo", lo), ("di", di), ("up", up))}
+        _check(lib().mpdata_plan_column_step_device(self._p, int(sl0), n, P["s"], float(c), int(mode), P["cb"], P["cc"], P["wp"],
+                                                    P["psfc"], P["lo"], P["di"], P["up"], int(first_tracer), ntr))
+
+    def column_step(self, s=None, c=1.0, mode=CELL_ADD, cb=None, cc=None, wp=None, psfc=None, lo=None, di=None, up=None, sl0=0,
+                    n=None):
+        """The same for all tracers from HOST arrays (numpy, Fortran order): s, wp (n, nx, nzm[, ntracers]), psfc (n, nx[,
+        ntracers]) or None (written), cb, cc, lo, di, up (n, nzm), synchronous (mpdata_plan_column_step[_f32])."""
+        n = self._block_n(sl0, n)
+        nx, nzm = self.dims[1], self.dims[2] - 1
+        P = {name: None if a is None else self._block_host(a, name, want, tr, out)
+             for name, a, want, tr, out in (("s", s, (n, nx, nzm), True, False), ("wp", wp, (n, nx, nzm), True, False),
+                                            ("psfc", psfc, (n, nx), True, True), ("cb", cb, (n, nzm), False, False),
+                                            ("cc", cc, (n, nzm), False, False), ("lo", lo, (n, nzm), False, False),
+                                            ("di", di, (n, nzm), False, False), ("up", up, (n, nzm), False, False))}
+        _check(getattr(lib(), "mpdata_plan_column_step" + self._sfx)(self._p, int(sl0), n, P["s"], float(c), int(mode), P["cb"],
+                                                                     P["cc"], P["wp"], P["psfc"], P["lo"], P["di"], P["up"]))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1150,6 +1192,43 @@ def cell_add(f, s, c=1.0, mode=CELL_ADD, dsum=None, sl0=0, n=None, stream=None):
     fn = lib().mpdata_cell_add_device if f.dtype == torch.float64 else lib().mpdata_cell_add_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, ptrs[0], float(c), int(mode), ptrs[1],
               _stream_handle(stream)))
+
+
+def column_step_shapes(n, nx, nz, ntracers=None):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a column_step call on n instances: s, wp
+    ([ntracers,] nzm, nx, n), psfc ([ntracers,] nx, n), cb, cc, lo, di, up (nzm, n); ntracers None: one tracer without the
+    leading axis."""
+    lead = () if ntracers is None else (int(ntracers),)
+    n, nx, nz = int(n), int(nx), int(nz)
+    sh = {k: (nz - 1, n) for k in ("cb", "cc", "lo", "di", "up")}
+    sh.update({"s": lead + (nz - 1, nx, n), "wp": lead + (nz - 1, nx, n), "psfc": lead + (nx, n)})
+    return sh
+
+
+def column_step_device(f, rho=None, adz=None, s=None, c=1.0, mode=CELL_ADD, cb=None, cc=None, wp=None, psfc=None, lo=None, di=None,
+                       up=None, sl0=0, n=None, stream=None):
+    """The fused column step (include/mpdata_hip.h 3q) of instances [sl0, sl0+n) (default: the rest from sl0) of a
+    reference-layout DEVICE tensor f ([ntr,] nzm, nx+6, ncrms), float64 or float32, in place, with rho, adz (nzm, ncrms)
+    required only with wp; the stages' tensors of the same dtype with the shapes of column_step_shapes(n, nx, nz, ntr), a
+    stage present exactly when its tensors are given.  Enqueued on `stream`; with lo, di, up the call returns when the work
+    is done (mpdata_column_step_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"column_step: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    pr = None if rho is None else _dev_ptr(rho, (nzm, ncrms), "rho", f.dtype)
+    pa = None if adz is None else _dev_ptr(adz, (nzm, ncrms), "adz", f.dtype)
+    sh = column_step_shapes(n, nxp6 - 6, nzm + 1, nt if f.dim() == 4 else None)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype)
+         for k, t in (("s", s), ("cb", cb), ("cc", cc), ("wp", wp), ("psfc", psfc), ("lo", lo), ("di", di), ("up", up))}
+    fn = lib().mpdata_column_step_device if f.dtype == torch.float64 else lib().mpdata_column_step_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, P["s"], float(c), int(mode), P["cb"], P["cc"], P["wp"],
+              P["psfc"], P["lo"], P["di"], P["up"], _stream_handle(stream)))
 
 
 def vsolve_shapes(n, nz):

@@ -1,10 +1,11 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3p).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_cell_add.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3q).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_column_step.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays.
 #include <cstring>
 
 #include "mpdata_cell_add.h"
 #include "mpdata_column_path.h"
+#include "mpdata_column_step.h"
 #include "mpdata_courant.h"
 #include "mpdata_diffuse.h"
 #include "mpdata_level_add.h"
@@ -927,5 +928,147 @@ int mpdata_cell_add_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t 
 int mpdata_cell_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* s, float c,
                                int mode, float* dsum, void* stream) {
   return cell_add_array(ncrms, nx, nz, ntracers, sl0, n, f, s, (double)c, mode, dsum, stream, 4);
+}
+
+// ---- 3q: the fused column step of f, in place: source, subside, sediment, vsolve in this order, each stage present with
+// its arrays.  Rewrites the INTERIOR columns of f of the block's instances and the tracer range; flux, u, w, rho, rhow, adz
+// and the boundary mode are not touched and no event is recorded.
+//   halo marks  halo columns are neither read nor written (3m alone also updates them: the one difference from the
+//               sequence of single calls besides the horizontal sums), so no wrap is launched in front; afterwards a
+//               periodic plan's halos are copies of an OLD interior: the marks of the range are cleared and the next run or
+//               read-back wraps again;
+//   windowed    refused in the check: stages 2 and 3 need fresh seams of the field stage 1 leaves, stage 4 crosses the
+//               windows twice;
+//   phantom     follows the plan's last slot inside the kernel (mpdata_column_step.h).
+// With stage 4 a small kernel in front writes the factors p and g (2 n nzm reals) into the plan's diffusion buffer, as 3o;
+// with stage 3 on a wave-major plan another writes 1 / (rho * adz) (n nzm reals) behind them.
+struct ColumnStepArgs {
+  const void* s; double c; int mode;
+  const void *cb, *cc, *wp; void* psfc;
+  const void *lo, *di, *up;
+};
+static int plan_column_step(mpdata_plan* p, int64_t sl0, int64_t n, const ColumnStepArgs& x, int first, int count) {
+  const int nzm = p->nz - 1;
+  MpdataColumnStepArrays a;
+  a.s = x.s; a.c = x.c; a.clip = x.s && x.mode == MPDATA_CELL_ADD_CLIP;
+  a.cb = x.cb; a.cc = x.cc; a.wp = x.wp; a.psfc = x.psfc; a.lo = x.lo; a.pg = nullptr;
+  const size_t kb = (size_t)n * nzm * p->eb;   // the diffusion buffer: p, g, then 1 / (rho * adz) of a plan-layout call
+  if (x.lo || (x.wp && plan_walked(p))) {
+    const int rc = plan_dbuf(p, 3 * kb);
+    if (rc) return rc;
+  }
+  if (x.lo) {
+    HIP_TRY(mpdata_vsolve_factor(x.lo, x.di, x.up, p->eb, n, nzm, p->dbuf, (char*)p->dbuf + kb, p->stream));
+    a.pg = p->dbuf;
+  }
+  if (plan_walked(p)) {
+    MpdataColumnStepJob b;
+    b.j = wm_job(p, 0, nullptr, first, count);
+    kc_rho_adz(p, b);
+    b.sel = block_sel(p, sl0, n);
+    b.ir = x.wp ? (char*)p->dbuf + 2 * kb : nullptr;
+    b.a = a;
+    HIP_TRY(mpdata_column_step_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_column_step_ref(ref_f(p, first), p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, nzm, count, a, p->stream));
+  }
+  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
+  return 0;
+}
+// the NULLs and the mode of a call, for the plan forms and the array forms alike
+static int column_step_stages(const char* what, const ColumnStepArgs& x) {
+  const int nv = (x.lo != nullptr) + (x.di != nullptr) + (x.up != nullptr);
+  if (!x.s && !x.cb && !x.cc && !x.wp && !nv && !x.psfc) return set_err(MPDATA_EINVAL, "%s: no stage present (s, cb and cc, wp, lo di up are all NULL)", what);
+  if (!x.cb != !x.cc) return set_err(MPDATA_EINVAL, "%s: %s without %s", what, x.cb ? "cb" : "cc", x.cb ? "cc" : "cb");
+  if (nv == 1 || nv == 2) return set_err(MPDATA_EINVAL, "%s: null %s (lo, di and up go together)", what, !x.lo ? "lo" : !x.di ? "di" : "up");
+  if (x.psfc && !x.wp) return set_err(MPDATA_EINVAL, "%s: psfc without wp", what);
+  return x.s ? cell_add_mode(what, x.mode) : 0;
+}
+static int plan_column_step_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const ColumnStepArgs& x, int first,
+                                  int count, int eb) {
+  int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  rc = column_step_stages(what, x);
+  if (rc) return rc;
+  if (p->inner)
+    return set_err(MPDATA_EUNSUPPORTED, "%s on a windowed plan (nz = %d > 238): the stages would need the seams refreshed between "
+                                        "them; not built yet -- use the single calls", what, p->nz);
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_column_step_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* s, double c, int mode, const void* cb,
+                                   const void* cc, const void* wp, void* psfc, const void* lo, const void* di, const void* up,
+                                   int first_tracer, int ntracers) {
+  const ColumnStepArgs x = {s, c, mode, cb, cc, wp, psfc, lo, di, up};
+  const int rc = plan_column_step_check("mpdata_plan_column_step_device", p, sl0, n, x, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_column_step(p, sl0, n, x, first_tracer, ntracers);
+}
+static int plan_column_step_host(mpdata_plan* p, int64_t sl0, int64_t n, const ColumnStepArgs& x, int eb) {
+  int rc = plan_column_step_check("mpdata_plan_column_step", p, sl0, n, x, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb, xb = (size_t)n * p->nx * p->ntracers * eb;
+  HostArr a[8] = {{x.s, xb * (p->nz - 1), false}, {x.cb, kb, false}, {x.cc, kb, false}, {x.wp, xb * (p->nz - 1), false},
+                  {x.psfc, xb, true}, {x.lo, kb, false}, {x.di, kb, false}, {x.up, kb, false}};
+  rc = stage_in(p, a);
+  const ColumnStepArgs d = {a[0].dev, x.c, x.mode, a[1].dev, a[2].dev, a[3].dev, a[4].dev, a[5].dev, a[6].dev, a[7].dev};
+  if (!rc) rc = plan_column_step(p, sl0, n, d, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_column_step(mpdata_plan* p, int64_t sl0, int64_t n, const double* s, double c, int mode, const double* cb,
+                            const double* cc, const double* wp, double* psfc, const double* lo, const double* di, const double* up) {
+  const ColumnStepArgs x = {s, c, mode, cb, cc, wp, psfc, lo, di, up};
+  return plan_column_step_host(p, sl0, n, x, 8);
+}
+int mpdata_plan_column_step_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* s, float c, int mode, const float* cb,
+                                const float* cc, const float* wp, float* psfc, const float* lo, const float* di, const float* up) {
+  const ColumnStepArgs x = {s, (double)c, mode, cb, cc, wp, psfc, lo, di, up};
+  return plan_column_step_host(p, sl0, n, x, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): in place.  Without stage 4 the
+// call is asynchronous; with it the factors go through a scratch array of the call's own, which is freed when the work is
+// done: the call returns after it.
+static int column_step_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* rho,
+                             const void* adz, const ColumnStepArgs& x, void* stream, int eb) {
+  const char* const what = "mpdata_column_step_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
+    return set_err(MPDATA_EINVAL, "%s: instances [%lld, %lld) outside the arrays' %lld", what, (long long)sl0, (long long)(sl0 + n),
+                   (long long)ncrms);
+  if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  rc = column_step_stages(what, x);
+  if (rc) return rc;
+  if (x.wp && (!rho || !adz)) return set_err(MPDATA_EINVAL, "%s: null %s (required with wp)", what, !rho ? "rho" : "adz");
+  MpdataColumnStepArrays a;
+  a.s = x.s; a.c = x.c; a.clip = x.s && x.mode == MPDATA_CELL_ADD_CLIP;
+  a.cb = x.cb; a.cc = x.cc; a.wp = x.wp; a.psfc = x.psfc; a.lo = x.lo; a.pg = nullptr;
+  if (!x.lo) {
+    HIP_TRY(mpdata_column_step_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, a, (hipStream_t)stream));
+    return 0;
+  }
+  const size_t kb = (size_t)n * (nz - 1) * eb;
+  void* scratch = nullptr;
+  HIP_TRY(hipMalloc(&scratch, 2 * kb));
+  a.pg = scratch;
+  hipError_t e = mpdata_vsolve_factor(x.lo, x.di, x.up, eb, n, nz - 1, scratch, (char*)scratch + kb, (hipStream_t)stream);
+  if (e == hipSuccess) e = mpdata_column_step_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, a, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(scratch);
+  HIP_TRY(e);
+  return 0;
+}
+int mpdata_column_step_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                              const double* adz, const double* s, double c, int mode, const double* cb, const double* cc,
+                              const double* wp, double* psfc, const double* lo, const double* di, const double* up, void* stream) {
+  const ColumnStepArgs x = {s, c, mode, cb, cc, wp, psfc, lo, di, up};
+  return column_step_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, x, stream, 8);
+}
+int mpdata_column_step_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                                  const float* adz, const float* s, float c, int mode, const float* cb, const float* cc,
+                                  const float* wp, float* psfc, const float* lo, const float* di, const float* up, void* stream) {
+  const ColumnStepArgs x = {s, (double)c, mode, cb, cc, wp, psfc, lo, di, up};
+  return column_step_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, x, stream, 4);
 }
 }  // extern "C"

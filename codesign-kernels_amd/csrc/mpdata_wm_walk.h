@@ -1,6 +1,7 @@
-// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3p:
-// the ten kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
-// mpdata_column_path.hip, mpdata_diffuse.hip, mpdata_subside.hip, mpdata_sediment.hip, mpdata_vsolve.hip, mpdata_cell_add.hip; their host side is mpdata_plan_blocks.hip): the selector
+// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3q:
+// the eleven kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
+// mpdata_column_path.hip, mpdata_diffuse.hip, mpdata_subside.hip, mpdata_sediment.hip, mpdata_vsolve.hip, mpdata_cell_add.hip,
+// mpdata_column_step.hip; their host side is mpdata_plan_blocks.hip): the selector
 // of the block, the element traits and the launch geometry.  Each of those files keeps its kernel whole -- the map wave -> (tracer, tile,
 // element of the column chunk), the map slot -> (instance, tall level) and its march: moving the two maps into functions
 // of this header changes the instructions of the plan-layout kernels (docs/EXPERIMENTS.md N), so they stay where
@@ -31,7 +32,7 @@ struct MpdataBlockSel {
   int W, nz;
 };
 
-// everything below is for the ten kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
+// everything below is for the eleven kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
 // selector alone
 namespace wm_walk {
 

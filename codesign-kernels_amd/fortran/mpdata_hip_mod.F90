@@ -68,6 +68,10 @@ module mpdata_hip_mod
   ! mpdata_cell_add[_f32]_device have no Fortran interface yet
   public :: mpdata_plan_cell_add_device_c
   integer(c_int), parameter, public :: MPDATA_CELL_ADD = 0, MPDATA_CELL_ADD_CLIP = 1
+  ! fused column step of a resident plan's tracers, in place (include/mpdata_hip.h section 3q): the device form only, one
+  ! binding for both precisions, next to 3p's in the interface block of the bindings with a real by value;
+  ! mpdata_plan_column_step[_f32] and mpdata_column_step[_f32]_device have no Fortran interface yet
+  public :: mpdata_plan_column_step_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -513,6 +517,21 @@ module mpdata_hip_mod
       real(c_double), value :: c
       integer(c_int), value :: mode
       type(c_ptr), value :: dsum
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! ---- the fused column step of f in place (include/mpdata_hip.h section 3q): source (s, c, mode), subside (cb, cc),
+    ! sediment (wp, psfc), vsolve (lo, di, up) in this order, a stage present exactly when its arrays are not c_null_ptr;
+    ! s, wp(n, nx, nzm [, ntracers]), psfc(n, nx [, ntracers]), cb, cc, lo, di, up(n, nzm); device arrays of the plan's
+    ! precision, asynchronous on the plan's stream; c is a double for both precisions; windowed plans are refused
+    integer(c_int) function mpdata_plan_column_step_device_c(plan, sl0, n, s, c, mode, cb, cc, wp, psfc, lo, di, up, &
+        first_tracer, ntracers) bind(C, name="mpdata_plan_column_step_device")
+      import :: c_int, c_int64_t, c_ptr, c_double
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: s
+      real(c_double), value :: c
+      integer(c_int), value :: mode
+      type(c_ptr), value :: cb, cc, wp, psfc, lo, di, up
       integer(c_int), value :: first_tracer, ntracers
     end function
   end interface

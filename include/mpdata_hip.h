@@ -882,6 +882,100 @@ int mpdata_cell_add_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t 
 int mpdata_cell_add_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* s,
                                float c, int mode, float* dsum, void* stream);
 
+/* ---- 3q. A fused column step of a resident plan's tracers, in place (what a host model does to every column after the
+ * advection step: tendencies and forcing, large-scale vertical advection, precipitation fall, the implicit vertical
+ * operator -- 3p, 3m, 3n and 3o as ONE call with one read of f and one write, no intermediate field in device memory).
+ * This section is the specification; the reference tree has no such routine.  For instance sl in [sl0, sl0 + n), tracer t
+ * in [first_tracer, first_tracer + ntracers), INTERIOR column i = 1 .. nx, level k = 1 .. nzm, nzm = nz - 1, b = sl - sl0,
+ * the call applies up to four stages in this FIXED ORDER.  Each stage reads the field the stage before left; inside a
+ * stage every f on the right is the value BEFORE that stage (Jacobi), exactly as in the single calls:
+ *   1. source    present when s != NULL            (3p)   p = c * s(b,i,k,t);  g = f(i,k) + p;  MPDATA_CELL_ADD_CLIP only:
+ *                                                         g = max(0, g);  f(i,k) = g
+ *   2. subside   present when cb, cc != NULL       (3m)   kb = max(1,k-1), kc = min(nzm,k+1):
+ *                                                         f(i,k) = f(i,k) - (cb(b,k) * (f(i,k) - f(i,kb)) + cc(b,k) * (f(i,kc) - f(i,k)))
+ *   3. sediment  present when wp != NULL           (3n)   Fz(k) = wp(b,i,k,t) * f(i,k);  Fz(nz) = +0;  ir(k) = 1 / (rho(sl,k) * adz(sl,k));
+ *                                                         f(i,k) = f(i,k) - (Fz(k) - Fz(k+1)) * ir(k)
+ *                                                         psfc(b,i,t) = Fz(1), of the field that ENTERS this stage (NULL: skipped)
+ *   4. vsolve    present when lo, di, up != NULL   (3o)   the factors p, g and the sweeps y, x exactly as 3o states them
+ * The order is SAM's: tendencies and forcing, then precipitation fall, then the implicit vertical operator.  A caller that
+ * needs another order makes two calls.  Every operation is rounded once in the plan's precision, in the association the
+ * single sections state, nothing contracted, the divides IEEE: EXACT and FAST plans give the same bits.  c is a double by
+ * value, rounded ONCE to the plan's precision; mode is MPDATA_CELL_ADD or MPDATA_CELL_ADD_CLIP and is ignored without s.
+ * On the interior columns the result is BIT FOR BIT what the sequence of the present single calls gives (mpdata_plan_
+ * cell_add_device, mpdata_plan_subside_device, mpdata_plan_sediment_device, mpdata_plan_vsolve_device), the absent stages
+ * left out.  The call deliberately differs from that sequence in two places:
+ *   halo slots       3m alone also updates the six halo slots.  The fused call neither reads nor writes halo columns at
+ *     all.  GIVEN plans: halos keep every bit.  PERIODIC plans: no wrap is launched in front, and the halo marks of the
+ *     tracer range are cleared afterwards -- what the next run or read-back sees is identical to the sequence.
+ *   horizontal sums  3p's and 3m's dsum and 3n's pflux are NOT offered.  They are sums over i in rising order, and in this
+ *     staging the columns of a level lie on different lanes and in different workgroups.  A caller takes them from the
+ *     single calls on a statistics step; f comes out the same.
+ * All arrays are of the plan's precision, reference layout, instance index fastest, leading dimension n (the block's first
+ * instance at index 0), tightly packed, tracer slowest:
+ *   s, wp                (n, nx, nzm [, ntracers])   one field per tracer of the call, only read
+ *   psfc                 (n, nx [, ntracers])        may be NULL; only with wp
+ *   cb, cc, lo, di, up   (n, nzm)                    shared by the columns and the tracers; lo(:,1), up(:,nzm) never read
+ * No byte outside these arrays is read or written.
+ * Towards the rest of a plan, as 3o states it: the phantom half of an odd fp32 plan (3f) follows instance ncrms - 1
+ * whenever the block holds it; the partner of a split fp32 pair is stored back as loaded -- no + 0.0 and no clip reach it;
+ * padding slots, neighbours in a group, instances and tracers outside the ranges, flux, u, w, rho, rhow, adz, the
+ * held-velocity flags, the boundary mode and the timing pair keep every bit.  The call is outside the run's event pair;
+ * the plan need not hold velocities.
+ * Kernels of their own (mpdata_column_step.hip), specialised on the set of present stages: an absent stage costs nothing.
+ * Wave-major plans: the geometry and the copy stage of 3o -- a workgroup stages the column slots of 16 adjacent 8-byte
+ * elements of the instance axis (fewer where the levels would not fit 40 KiB of LDS) and a batch of columns in LDS as
+ * [column][unit][level]; a lane per (unit, column) sweeps its column in LDS in place: stages 1 - 3 and the forward sweep
+ * of stage 4 share ONE upward pass with the old neighbours carried in registers, the backward sweep is a second pass; then
+ * the waves store LDS back.  s, wp and the coefficient rows are read by the sweeping lanes straight from the caller's
+ * arrays, the unit fastest (a row of 16 units is one 128-byte line); only 1 / (rho * adz) is a row of LDS.  No conversion
+ * pass, no scratch in device memory but the 2 n nzm factors of stage 4 in the plan's diffusion buffer, as 3o.  Race
+ * freedom: DESIGN.md 4.20.  Reference-layout plans and the array forms: one thread per instance and (column, tracer) row
+ * owns its column and sweeps it in place in device memory; no scratch array.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range (as 3p); no stage present; exactly one of
+ * cb, cc; one or two of lo, di, up; psfc without wp; an unknown mode while s is given; in the array forms bad sizes, a block
+ * outside the arrays, a null f, then the same, then a null rho or adz with wp.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3p (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0); a
+ * WINDOWED plan (3e: nz > 238 with tall columns on) -- the named follow-up: stages 2 and 3 need fresh seams of the field
+ * stage 1 leaves, stage 4 crosses the windows twice, and tall plans are where 3o already loses to the round trip.  Use the
+ * single calls there.
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md X, tools/column_step_bench.py, profiles/column_step_bench.json), 65536 x 32 x 28,
+ * one tracer, cold, all four stages: 0.593 ms fp64, 0.417 ms fp32 -- 3.1 / 2.2 TB/s of the algorithmic bytes (f read and
+ * written once, s and wp read once: 4 nx nzm ncrms reals, 1.81 GB fp64) -- against 1.147 / 0.622 ms for the four single
+ * calls in the same run: 0.52 x / 0.67 x their sum (1.37 x / 1.77 x the export + import of f alone).  psfc costs nothing.
+ * The single-stage forms against their siblings: source 0.91 x / 0.96 x mpdata_plan_cell_add_device, subside 1.17 x /
+ * 1.47 x mpdata_plan_subside_device, sediment 1.04 x / 1.25 x mpdata_plan_sediment_device, vsolve 1.37 x / 1.31 x
+ * mpdata_plan_vsolve_device.  Said plainly: the fused call halves the fp64 time of the chain but reaches 0.59 ms where
+ * the bytes alone would allow 0.43 ms at 3n's rate, and a caller with ONE stage other than the source is better served by
+ * the single call: 176 of 256 lanes sweep (16 units x 11 columns; 3o has 128), but every sweeping lane fetches its
+ * coefficient rows and its s and wp level by level from L2 three levels ahead of a dependent chain, where 3m streams f
+ * without LDS and 3o reads its rows from LDS. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_column_step_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* s, double c, int mode,
+                                   const void* cb, const void* cc, const void* wp, void* psfc, const void* lo, const void* di,
+                                   const void* up, int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3p host forms) */
+int mpdata_plan_column_step(mpdata_plan* plan, int64_t sl0, int64_t n, const double* s, double c, int mode, const double* cb,
+                            const double* cc, const double* wp, double* psfc, const double* lo, const double* di,
+                            const double* up);
+int mpdata_plan_column_step_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* s, float c, int mode, const float* cb,
+                                const float* cc, const float* wp, float* psfc, const float* lo, const float* di,
+                                const float* up);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm[,ntracers]) (leading
+ * dimension ncrms) with rho, adz (ncrms, nzm), required only with wp; the other arrays as above (leading dimension n).
+ * Enqueued on `stream`, 64-bit offsets; asynchronous without stage 4 -- with it the call allocates the factors' scratch
+ * array and returns when the work is done and the scratch is freed. */
+int mpdata_column_step_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                              const double* adz, const double* s, double c, int mode, const double* cb, const double* cc,
+                              const double* wp, double* psfc, const double* lo, const double* di, const double* up,
+                              void* stream);
+int mpdata_column_step_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                                  const float* adz, const float* s, float c, int mode, const float* cb, const float* cc,
+                                  const float* wp, float* psfc, const float* lo, const float* di, const float* up,
+                                  void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
