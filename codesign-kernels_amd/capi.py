@@ -180,6 +180,14 @@ def lib():
         for name, cf in (("mpdata_column_step_device", ctypes.c_double), ("mpdata_column_step_f32_device", ctypes.c_float)):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, dp, dp, cf, ci] + [dp] * 7 + [vp]
+        L.mpdata_plan_relax_device.restype = ci
+        L.mpdata_plan_relax_device.argtypes = [vp, i64, i64, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_relax", "mpdata_plan_relax_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp, dp]
+        for name in ("mpdata_relax_device", "mpdata_relax_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 4 + [vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -986,6 +994,31 @@ class Plan:
         _check(getattr(lib(), "mpdata_plan_column_step" + self._sfx)(self._p, int(sl0), n, P["s"], float(c), int(mode), P["cb"],
                                                                      P["cc"], P["wp"], P["psfc"], P["lo"], P["di"], P["up"]))
 
+    def relax(self, c, target=None, mean=None, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """Relaxation of f to a level profile in place (include/mpdata_hip.h 3r) on the interior columns of instances [sl0,
+        sl0+n) (default: the rest of the plan from sl0): f -= c * (f - m), with m = target, or without a target the
+        horizontal mean of f itself (the sum of level_stats over nx, one rounded divide); levels with c == 0 keep every
+        bit; on the plan's stream (mpdata_plan_relax_device).  Reference-layout DEVICE tensors of the plan's precision,
+        shapes relax_shapes(n, nx, nz, ntr): c (nzm, n), shared by the columns and the tracers; target ([ntr,] nzm, n) or
+        None; mean ([ntr,] nzm, n) or None (skipped), written with m in both modes.  The tracers are first_tracer ..
+        +ntr-1, ntr = ntracers, or the leading axis of a 3-d target or mean (else 1); target and mean carry that axis
+        together.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        nx, nz = self.dims[1], self.dims[2]
+        ntr, axis = self._block_ntr(target if target is not None else mean, ntracers)
+        sh = relax_shapes(n, nx, nz, ntr if axis else None)
+        ptrs = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("c", c), ("target", target), ("mean", mean))]
+        _check(lib().mpdata_plan_relax_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
+
+    def relax_host(self, c, target=None, mean=None, sl0=0, n=None):
+        """The same for all tracers from HOST arrays (numpy, Fortran order): c (n, nzm), target (n, nzm[, ntracers]) or
+        None, mean (n, nzm[, ntracers]) or None (written), synchronous (mpdata_plan_relax[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        ptrs = [None if a is None else self._block_host(a, name, (n, nzm), tr, out)
+                for name, a, tr, out in (("c", c, False, False), ("target", target, True, False), ("mean", mean, True, True))]
+        _check(getattr(lib(), "mpdata_plan_relax" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1229,6 +1262,35 @@ def column_step_device(f, rho=None, adz=None, s=None, c=1.0, mode=CELL_ADD, cb=N
     fn = lib().mpdata_column_step_device if f.dtype == torch.float64 else lib().mpdata_column_step_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, P["s"], float(c), int(mode), P["cb"], P["cc"], P["wp"],
               P["psfc"], P["lo"], P["di"], P["up"], _stream_handle(stream)))
+
+
+def relax_shapes(n, nx, nz, ntracers=None):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a relax call on n instances: c (nzm, n),
+    target and mean ([ntracers,] nzm, n); ntracers None: one tracer without the leading axis.  (nx is taken as the other
+    shape functions take it; no array of the call has a column axis.)"""
+    lead = () if ntracers is None else (int(ntracers),)
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {"c": (nz - 1, n), "target": lead + (nz - 1, n), "mean": lead + (nz - 1, n)}
+
+
+def relax(f, c, target=None, mean=None, sl0=0, n=None, stream=None):
+    """Relaxation to a level profile (include/mpdata_hip.h 3r) of instances [sl0, sl0+n) (default: the rest from sl0) of a
+    reference-layout DEVICE tensor f ([ntr,] nzm, nx+6, ncrms), float64 or float32, in place: f -= c * (f - m) on the
+    interior columns, m = target or, without one, the horizontal mean of f; c, target, mean of the same dtype with the
+    shapes of relax_shapes(n, nx, nz, ntr) (target, mean may be None).  Asynchronous on `stream` (mpdata_relax_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"relax: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = relax_shapes(n, nxp6 - 6, nzm + 1, nt if f.dim() == 4 else None)
+    ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("c", c), ("target", target), ("mean", mean))]
+    fn = lib().mpdata_relax_device if f.dtype == torch.float64 else lib().mpdata_relax_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, *ptrs, _stream_handle(stream)))
 
 
 def vsolve_shapes(n, nz):

@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3q).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_column_step.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3r).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_relax.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays.
 #include <cstring>
 
@@ -10,6 +10,7 @@
 #include "mpdata_diffuse.h"
 #include "mpdata_level_add.h"
 #include "mpdata_plan_priv.h"
+#include "mpdata_relax.h"
 #include "mpdata_scale_uw.h"
 #include "mpdata_sediment.h"
 #include "mpdata_stats.h"
@@ -1071,4 +1072,86 @@ int mpdata_column_step_f32_device(int64_t ncrms, int nx, int nz, int ntracers, i
   const ColumnStepArgs x = {s, (double)c, mode, cb, cc, wp, psfc, lo, di, up};
   return column_step_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, x, stream, 4);
 }
+
+// ---- 3r: relaxation of f to a level profile, in place: f = f - c * (f - m), m the given target or the horizontal mean of
+// f.  Reads c and target, writes mean, rewrites the INTERIOR columns of f of the block's instances and the tracer range;
+// flux, u, w, rho, rhow, adz and the boundary mode are not touched and no event is recorded.
+//   halo marks  halo columns are neither read nor written, so no wrap is launched in front; afterwards a periodic plan's
+//               halos are copies of the OLD interior: the marks of the range are cleared and the next run or read-back
+//               wraps again;
+//   seam marks  given m the operator is pointwise, and m is formed from the owned level's own columns: the call reads
+//               and writes OWNED levels only, which are right whatever the seams hold: no refresh in front; afterwards the
+//               other copies are stale: the marks of the range are cleared and the next run refreshes them;
+//   phantom     follows the plan's last slot inside the kernel (mpdata_relax.h); on a windowed plan the refresh of the
+//               inner plan follows as after a seam refresh.
+// Every kind of plan: c and target are read where they lie and f is updated in place; the diffusion buffer is not used.
+static int plan_relax(mpdata_plan* p, int64_t sl0, int64_t n, const void* c, const void* target, void* mean, int first, int count) {
+  if (plan_walked(p)) {
+    MpdataRelaxJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.c = c; b.target = target; b.mean = mean;
+    HIP_TRY(mpdata_relax_wm(b, p->stream));
+    if (p->inner) {
+      memset(p->seam_ok + first, 0, (size_t)count);
+      const int rc = sl0 + n == p->ncrms ? plan_phantom(p->inner, 0, first, count) : 0;
+      if (rc) return rc;
+    }
+  } else {
+    HIP_TRY(mpdata_relax_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, c, target, mean, p->stream));
+  }
+  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
+  return 0;
+}
+static int plan_relax_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* c, int first, int count, int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!c) return set_err(MPDATA_EINVAL, "%s: null c", what);
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_relax_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* c, const void* target, void* mean, int first_tracer,
+                             int ntracers) {
+  const int rc = plan_relax_check("mpdata_plan_relax_device", p, sl0, n, c, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_relax(p, sl0, n, c, target, mean, first_tracer, ntracers);
+}
+static int plan_relax_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* c, const void* target, void* mean, int eb) {
+  int rc = plan_relax_check("mpdata_plan_relax", p, sl0, n, c, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb;
+  HostArr a[3] = {{c, kb, false}, {target, kb * p->ntracers, false}, {mean, kb * p->ntracers, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_relax(p, sl0, n, a[0].dev, a[1].dev, a[2].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_relax(mpdata_plan* p, int64_t sl0, int64_t n, const double* c, const double* target, double* mean) {
+  return plan_relax_host(p, sl0, n, c, target, mean, 8);
+}
+int mpdata_plan_relax_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* c, const float* target, float* mean) {
+  return plan_relax_host(p, sl0, n, c, target, mean, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): in place, asynchronous
+static int relax_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* c, const void* target,
+                       void* mean, void* stream, int eb) {
+  const int rc = array_sizes("mpdata_relax_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
+    return set_err(MPDATA_EINVAL, "mpdata_relax_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
+                   (long long)(sl0 + n), (long long)ncrms);
+  if (!f) return set_err(MPDATA_EINVAL, "mpdata_relax_device: null f");
+  if (!c) return set_err(MPDATA_EINVAL, "mpdata_relax_device: null c");
+  HIP_TRY(mpdata_relax_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, c, target, mean, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_relax_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* c,
+                        const double* target, double* mean, void* stream) {
+  return relax_array(ncrms, nx, nz, ntracers, sl0, n, f, c, target, mean, stream, 8);
+}
+int mpdata_relax_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* c,
+                            const float* target, float* mean, void* stream) {
+  return relax_array(ncrms, nx, nz, ntracers, sl0, n, f, c, target, mean, stream, 4);
+}
+
 }  // extern "C"

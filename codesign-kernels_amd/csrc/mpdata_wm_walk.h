@@ -1,7 +1,7 @@
-// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3q:
-// the eleven kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
+// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3r:
+// the twelve kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
 // mpdata_column_path.hip, mpdata_diffuse.hip, mpdata_subside.hip, mpdata_sediment.hip, mpdata_vsolve.hip, mpdata_cell_add.hip,
-// mpdata_column_step.hip; their host side is mpdata_plan_blocks.hip): the selector
+// mpdata_column_step.hip, mpdata_relax.hip; their host side is mpdata_plan_blocks.hip): the selector
 // of the block, the element traits and the launch geometry.  Each of those files keeps its kernel whole -- the map wave -> (tracer, tile,
 // element of the column chunk), the map slot -> (instance, tall level) and its march: moving the two maps into functions
 // of this header changes the instructions of the plan-layout kernels (docs/EXPERIMENTS.md N), so they stay where
@@ -21,7 +21,7 @@
 //   sl0, n, ncrms: the block and the plan's size in REAL instances.  Slots that are no instance of the block -- the
 //     padding of the last tile, the phantom half of an odd fp32 plan, the partner of a pair the block's ends split, a
 //     neighbour in the tile -- reach no output and keep their bits (the one exception: the phantom follows the last slot in the calls that
-//     rewrite the plan, mpdata_level_add.h, mpdata_scale_uw.h).
+//     rewrite the plan, mpdata_level_add.h, mpdata_scale_uw.h, mpdata_relax.h).
 //   ipe: reals per 8-byte element -- 1 (fp64), 2 (fp32 plans: pairs of adjacent instances)
 //   W = 1: the layout job describes the plan itself, nz = j.nlev + 1.
 //   W > 1: the layout job describes the INNER plan of a windowed plan (mpdata_windows.h): slot q = sl * W + h is window
@@ -32,7 +32,7 @@ struct MpdataBlockSel {
   int W, nz;
 };
 
-// everything below is for the eleven kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
+// everything below is for the twelve kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
 // selector alone
 namespace wm_walk {
 

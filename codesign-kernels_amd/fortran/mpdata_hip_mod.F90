@@ -72,6 +72,10 @@ module mpdata_hip_mod
   ! binding for both precisions, next to 3p's in the interface block of the bindings with a real by value;
   ! mpdata_plan_column_step[_f32] and mpdata_column_step[_f32]_device have no Fortran interface yet
   public :: mpdata_plan_column_step_device_c
+  ! relaxation of a resident plan's tracers to a level profile, in place (include/mpdata_hip.h section 3r): the device form
+  ! only, one binding for both precisions -- it carries no reals of its own; it stands in the second interface block, next
+  ! to 3p's and 3q's; mpdata_plan_relax[_f32] and mpdata_relax[_f32]_device have no Fortran interface yet
+  public :: mpdata_plan_relax_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -532,6 +536,18 @@ module mpdata_hip_mod
       real(c_double), value :: c
       integer(c_int), value :: mode
       type(c_ptr), value :: cb, cc, wp, psfc, lo, di, up
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! ---- relaxation of f to a level profile in place (include/mpdata_hip.h section 3r): f = f - c * (f - m), m = target
+    ! or, with target = c_null_ptr, the horizontal mean of f; c(n, nzm), target, mean(n, nzm [, ntracers]) (mean
+    ! c_null_ptr: skipped); device arrays of the plan's precision, asynchronous on the plan's stream; windowed plans are
+    ! supported
+    integer(c_int) function mpdata_plan_relax_device_c(plan, sl0, n, c, target, mean, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_relax_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: c, target, mean
       integer(c_int), value :: first_tracer, ntracers
     end function
   end interface

@@ -976,6 +976,88 @@ int mpdata_column_step_f32_device(int64_t ncrms, int nx, int nz, int ntracers, i
                                   const float* wp, float* psfc, const float* lo, const float* di, const float* up,
                                   void* stream);
 
+/* ---- 3r. Relaxation of a resident plan's tracers to a level profile, in place (Newtonian relaxation, the last per-step
+ * operator of a host model that forced f out of a plan: SAM's damping layer under the model top, t(i,k) = t(i,k) -
+ * dtn * tau(k) * (t(i,k) - t0(k)) with t0 the horizontal mean of the field itself, and nudging towards a given profile.
+ * The update scales each cell's deviation, so it is no per-level increment (3i), and 3p could apply it only from a
+ * per-cell array the caller would have to form from f).  This section is the specification; the reference tree has no
+ * such routine.  For instance sl in [sl0, sl0 + n), tracer t in [first_tracer, first_tracer + ntracers), level
+ * k = 1 .. nzm, nzm = nz - 1, interior column i = 1 .. nx, with b = sl - sl0:
+ *   target == NULL :  s = +0;  do i = 1, nx:  s = s + f_old(sl,i,k,t)        (the sum of 3g, in that order)
+ *                     m = s / nx                                             (nx converted exactly; ONE divide)
+ *   target != NULL :  m = target(b,k,t)
+ *   mean(b,k,t) = m                                                          (NULL: skipped; written in both modes)
+ *   c(b,k) == 0 (either sign):  f(sl,:,k,t) keeps every bit -- the level is not rewritten
+ *   else, per i:      d = f_old(sl,i,k,t) - m;  p = c(b,k) * d;  f(sl,i,k,t) = f_old(sl,i,k,t) - p
+ * Every operation is rounded ONCE in the plan's precision, in exactly this association; nothing is contracted, so EXACT
+ * and FAST plans give the same bits.  The divide is the IEEE one, correctly rounded in both precisions: on an fp32 plan
+ * m is NOT float(double(s) / nx) and not s times a rounded reciprocal.  NaN and infinities are outside the contract.
+ * c = 1 does not make the field uniform bit for bit: f - (f - m) is m only up to the two roundings.
+ * All arrays are of the plan's precision, reference layout, instance index fastest, leading dimension n (the block's
+ * first instance at index 0), tightly packed, tracer slowest:
+ *   c      (n, nzm)                shared by the columns and the tracers, as 3o shares its coefficients; required, only read
+ *   target (n, nzm [, ntracers])   only read; may be NULL (relax to the horizontal mean)
+ *   mean   (n, nzm [, ntracers])   only written; may be NULL
+ * No byte outside these arrays is read or written.  Afterwards the plan behaves exactly as if the interior of f had been
+ * exported, changed as above and imported again.
+ * Towards the rest of a plan:
+ *   halo marks   only interior columns are read and written; halo columns are neither.  GIVEN plans: halos keep every
+ *     bit.  PERIODIC plans: no wrap is launched, because the mean is taken over the interior alone; the halo marks of the
+ *     range are cleared afterwards, so the next run or read-back hands out wrapped halos of the new field.
+ *   windowed plans (3e, nz > 238) are supported.  Given m the operator is pointwise in k, and m is the sum of the level's
+ *     own interior columns, so no seam refresh is needed in front: an owned level is right whatever the seams hold (as
+ *     3k argues).  The scheme chosen: the call reads and writes OWNED levels only, each with c and the target of the tall
+ *     level it stands for, and clears the seam marks of the range afterwards; the next run refreshes the other copies,
+ *     whether the seams were fresh or stale at the call.  mean of a level is written by that level's owner.  c, target
+ *     and mean are addressed by tall level directly in the caller's arrays: nothing is cut into windows.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 whenever the block holds it (on a windowed plan the
+ *     phantom of the inner plan is restored behind the call, as in 3m / 3n / 3p).
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded: a -0.0 there stays; padding slots,
+ *     neighbours in a tile, instances and tracers outside the ranges, flux, u, w, rho, rhow, adz, the held-velocity
+ *     flags, the boundary mode and the timing pair keep every bit.  The call is outside the run's event pair; the plan
+ *     need not hold velocities.
+ * A kernel of its own on every kind of plan (mpdata_relax.hip), not fused into the run.  Wave-major and windowed plans: a
+ * lane owns one (instance, level) element and walks its interior column slots (the walk of 3g and 3i), so the horizontal
+ * sum is lane-local: no LDS, no barrier, no cross-lane traffic, and no ordering to argue -- a lane touches the columns of
+ * its own element only.  With a target: ONE walk that loads and stores f, m and c in registers; a wave whose elements
+ * all have c == 0 loads nothing.  Without one, two forms: nx <= 32, the KEPT form -- the nx columns of
+ * the lane's element are loaded into registers once (64 registers at nx = 32, fully unrolled, no scratch), summed,
+ * updated and stored, so f is read from HBM once; nx > 32, the RE-READ form -- the summing walk of 3g, the divide, then
+ * the updating walk over the same columns; that its second read of f is served by L2 is a supposition: not counted.
+ * Both forms give the same bits.  Reference-layout plans and the array forms: one thread per instance and (level,
+ * tracer) row, two loops over i, in place, no scratch array.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range, a null c; in the array forms bad sizes
+ * (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null f, then a null c.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3q (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md Y, tools/relax_bench.py, profiles/relax_bench.json), 65536 x 32 x 28, one tracer,
+ * cold: to the mean 0.203 ms fp64, 0.102 ms fp32; to a target 0.205 / 0.109 ms -- 4.5 / 4.4 and 4.4 / 4.1 TB/s of the
+ * algorithmic bytes (the interior of f read once and written once: 2 nx nzm ncrms reals, 0.906 GB fp64).  Against existing
+ * calls in the same run, mean mode / target mode: (a) 0.47 x / 0.48 x fp64 and 0.46 x / 0.49 x fp32
+ * mpdata_plan_export_device + mpdata_plan_import_device of f alone (the old route without the caller's kernel); (b) 0.59 x /
+ * 0.60 x and 0.61 x / 0.65 x mpdata_plan_level_stats_device (sum) + mpdata_plan_level_add_device; (c) 0.90 x / 0.90 x and
+ * 0.88 x / 0.94 x mpdata_plan_level_add_device alone.  With 25 tracers: 5.49 / 5.55 ms fp64, 2.62 / 2.75 ms fp32 (0.54 x (a),
+ * 0.62 x (b), 0.84 x (c) in fp64).  Tall plans, 4096 x 32 x 300 (6 windows): 0.147 / 0.154 ms fp64, 0.078 / 0.086 ms fp32,
+ * 0.39 x / 0.41 x (a), 0.59 x / 0.61 x (b), 0.91 x / 0.95 x (c) in fp64.  The KEPT form against the RE-READ form at the same
+ * shapes: 0.203 against 0.224 ms fp64, 0.102 / 0.117 fp32, 0.147 / 0.181 and 0.078 / 0.095 tall -- 7 % to 19 %, where three
+ * runs of one form differ by 3 % at most; with 25 tracers in fp64 no gain beyond that spread.  Said plainly: both modes are
+ * below (c) only because they move 32 of its 38 columns; per byte neither reaches level_add's rate (4.7 TB/s), and target
+ * mode, with 8 loads in flight per lane where the kept form has 32, is the slower of the two although it does less. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_relax_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* c, const void* target, void* mean,
+                             int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3q host forms) */
+int mpdata_plan_relax(mpdata_plan* plan, int64_t sl0, int64_t n, const double* c, const double* target, double* mean);
+int mpdata_plan_relax_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* c, const float* target, float* mean);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm[,ntracers]) (leading
+ * dimension ncrms); c, target, mean as above (leading dimension n).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_relax_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* c,
+                        const double* target, double* mean, void* stream);
+int mpdata_relax_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* c,
+                            const float* target, float* mean, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
