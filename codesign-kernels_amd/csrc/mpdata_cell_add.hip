@@ -29,7 +29,7 @@ namespace {
 
 using namespace wm_walk;
 
-constexpr int LDS_ELEMS = 5120;   // 8-byte elements of LDS per workgroup at most (40 KiB: room for four workgroups per CU)
+// (LDS_ELEMS, the LDS of a workgroup at most, and the column groups of the launch: mpdata_wm_walk.h)
 
 __device__ inline double pos(double a) { return fmax(a, 0.0); }
 __device__ inline float pos(float a) { return fmaxf(a, 0.0f); }
@@ -335,8 +335,15 @@ hipError_t mpdata_cell_add_wm(const MpdataCellAddJob& b, hipStream_t stream) {
   if (e != hipSuccess) return e;
   // As in mpdata_sediment_wm: what follows holds for every plan mpdata_plan_create makes, so none of these returns is
   // reached today; a new tiling that breaks one of them must extend the kernel, and fails here, before any launch.
-  if (wg.nslice > 4 || b.sel.W > 65535) return hipErrorInvalidValue;   // (a tile is a workgroup's at most; gridDim.y)
-  const int nx = j.ncol_p - 6, slp = j.slp, W = b.sel.W, tpw = 4 / wg.nslice;
+  // Two buffers of s and, with dsum, the running sums; 16 units, fewer where two columns of the group's levels do not
+  // fit twice.
+  const int slp = j.slp, W = b.sel.W;
+  ColGroups cg;
+  // (unit, tile and slot-in-LDS arithmetic of the kernel is in int)
+  if (!col_groups_tiled(j, b.sel, wg, LDS_ELEMS, /*fixed*/ W > 1 ? 4 : 0, /*rows*/ 0, /*bufs*/ 2, /*sums*/ b.dsum != nullptr,
+                        /*wide*/ false, &cg) ||
+      (long long)j.ncol_p * j.main_e + j.chunk > 2147483647LL)
+    return hipErrorInvalidValue;
   CellArgs g;
   g.f = j.prv; g.s = b.s; g.dsum = b.dsum; g.c = b.c; g.clip = b.clip;
   g.n = b.sel.n; g.sl0 = b.sel.sl0; g.nslots = b.sel.ncrms * W;
@@ -344,40 +351,14 @@ hipError_t mpdata_cell_add_wm(const MpdataCellAddJob& b, hipStream_t stream) {
   g.chunk = (int)j.chunk; g.main_e = (int)j.main_e; g.ncol_p = j.ncol_p; g.nlev = j.nlev; g.slp = slp;
   g.W = W; g.nz = b.sel.nz;
   g.t0 = (int)wg.t0; g.t1 = (int)(wg.t0 + wg.ntile - 1);
-  g.ns = j.nlev | 1;
   g.nslice = wg.nslice;
-  // 16 units: a row of s of the group is whole 128-byte lines; fewer where two buffers of two columns of the group's
-  // levels and the running sums do not fit the LDS
-  g.UG = slp > 16 ? slp : 16;
-  size_t lds_elems;
-  for (;;) {
-    const long long per_col = (long long)g.UG * g.ns;
-    g.nround = (g.UG / slp + tpw - 1) / tpw;
-    const long long fixed = (b.dsum ? (long long)g.nround * 256 : 0) + (W > 1 ? 4 : 0);
-    long long cb = (LDS_ELEMS - fixed) / (2 * per_col);
-    if (cb < 0) cb = 0;
-    if (cb > NB) cb = NB;
-    if (cb > nx) cb = nx;
-    g.CB = (int)cb;
-    lds_elems = (size_t)(2 * cb * per_col + fixed);
-    if (g.CB >= 2 || g.CB >= nx || g.UG <= slp) break;
-    g.UG /= 2;
-  }
-  g.ush = 0;
-  while ((1 << g.ush) < g.UG) ++g.ush;
-  if (g.CB < 1 || g.UG % slp || (1 << g.ush) != g.UG || g.UG * b.sel.ipe > 256 || lds_elems > (size_t)LDS_ELEMS) return hipErrorInvalidValue;
+  col_groups_fill(cg, &g);
+  g.ush = cg.ush; g.nround = cg.nround;
   // (W > 1: the halves of a pair are windows, not adjacent instances)
   const bool pairs = b.sel.ipe == 2 && W == 1 && b.sel.sl0 % 2 == 0 && b.sel.n % 2 == 0 && reinterpret_cast<uintptr_t>(b.s) % 8 == 0;
-  const long long ue_last = (long long)g.t1 / W * slp + slp - 1;
-  g.g0 = (int)((long long)g.t0 / W * slp / g.UG);
-  const long long ngroup = ue_last / g.UG - g.g0 + 1;
-  // (unit, tile and slot-in-LDS arithmetic of the kernel is in int)
-  if (ngroup > 2147483647LL / j.ntr || ue_last + g.UG > 2147483647LL || (long long)j.ncol_p * j.main_e + j.chunk > 2147483647LL)
-    return hipErrorInvalidValue;
-  g.ngroup = (int)ngroup;
   void (*k)(CellArgs) = b.sel.ipe == 1 ? (b.dsum ? wm_kernel<double, true>(W > 1, true) : wm_kernel<double, false>(W > 1, true))
                                        : (b.dsum ? wm_kernel<float2, true>(W > 1, pairs) : wm_kernel<float2, false>(W > 1, pairs));
-  hipLaunchKernelGGL(k, dim3((unsigned)(g.ngroup * j.ntr), (unsigned)W), dim3(256), lds_elems * 8, stream, g);
+  hipLaunchKernelGGL(k, dim3((unsigned)(g.ngroup * j.ntr), (unsigned)W), dim3(256), (size_t)cg.lds_e * 8, stream, g);
   return hipGetLastError();
 }
 
@@ -388,11 +369,10 @@ hipError_t mpdata_cell_add_ref(void* f, int elem_bytes, long long ld, long long 
   const long long rows = (long long)nlev * ntr;
   dim3 grid;
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((ref_cell_add_kernel<double>), grid, dim3(256), 0, stream, static_cast<double*>(f), ld, sl0, n, nx, rows,
-                       static_cast<const double*>(s), c, clip, static_cast<double*>(dsum));
-  else
-    hipLaunchKernelGGL((ref_cell_add_kernel<float>), grid, dim3(256), 0, stream, static_cast<float*>(f), ld, sl0, n, nx, rows,
-                       static_cast<const float*>(s), c, clip, static_cast<float*>(dsum));
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((ref_cell_add_kernel<R>), grid, dim3(256), 0, stream, static_cast<R*>(f), ld, sl0, n, nx, rows,
+                       static_cast<const R*>(s), c, clip, static_cast<R*>(dsum));
+    return hipGetLastError();
+  });
 }

@@ -20,11 +20,11 @@ namespace {
 
 using namespace wm_walk;
 
-constexpr int LDS_ELEMS = 4096;   // 8-byte elements of LDS per workgroup (32 KiB: five workgroups per CU)
+constexpr int CP_LDS_ELEMS = 4096;   // 8-byte elements of LDS per workgroup (32 KiB: five workgroups per CU)
 
-// The workgroups of the plan-layout kernel.  A UNIT is one 8-byte element of the instance axis (an instance, or the pair
-// 2 * ue, 2 * ue + 1 of an fp32 plan): slot ue % slp of tile ue / slp, or, in a windowed plan, the tiles ue * W ..
-// ue * W + W - 1.  A workgroup takes UG adjacent units (a multiple of slp) and CB adjacent columns.
+// The workgroups of the plan-layout kernel: column groups (mpdata_wm_walk.h: units, groups of UG units, batches of CB
+// columns) as col_groups_batched makes them; the tiles, the first group and the number of groups in long long -- the
+// kernel counts units in long long.
 struct CpGeom {
   long long t0, t1;   // tiles the block touches
   long long g0;       // first group
@@ -224,13 +224,11 @@ __global__ void __launch_bounds__(256) column_mass_kernel(const R* path, const l
 hipError_t column_mass(const void* path, int elem_bytes, long long n, int nx, int ntr, void* mass, hipStream_t stream) {
   dim3 grid, block(256);
   if (ref_block_grid(n, ntr, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((column_mass_kernel<double>), grid, block, 0, stream, static_cast<const double*>(path), n, nx, ntr,
-                       static_cast<double*>(mass));
-  else
-    hipLaunchKernelGGL((column_mass_kernel<float>), grid, block, 0, stream, static_cast<const float*>(path), n, nx, ntr,
-                       static_cast<float*>(mass));
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((column_mass_kernel<R>), grid, block, 0, stream, static_cast<const R*>(path), n, nx, ntr, static_cast<R*>(mass));
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
@@ -241,31 +239,20 @@ hipError_t mpdata_column_path_wm(const MpdataColumnPathJob& b, hipStream_t strea
   if (!b.rho || !b.adz || !b.path || j.prv_col0 != 0 || j.ncols != j.ncol_p || b.kc_tile_stride < j.chunk) return hipErrorInvalidValue;
   hipError_t e = wm_block_grid(j, b.sel, j.ntr, &wg);
   if (e != hipSuccess) return e;
-  const int nx = j.ncol_p - 6, slp = j.slp, W = b.sel.W;
+  // one row of rho * adz next to the columns: 16 units = one 128-byte line of path per column; the kernel counts units
+  // in long long
+  ColGroups cg;
+  if (!col_groups_batched(j, b.sel, wg, CP_LDS_ELEMS, /*fixed*/ 0, /*rows*/ 1, /*unit_mul*/ 0, &cg)) return hipErrorInvalidValue;
   CpGeom g;
   g.t0 = wg.t0; g.t1 = wg.t0 + wg.ntile - 1;
-  g.ns = j.nlev | 1;
-  // 16 units = one 128-byte line of path per column (32 where a tile holds 8: a tile per wave while staging); fewer
-  // where the levels of 16 fill the LDS
-  g.UG = slp >= 8 ? 4 * slp : 16;
-  while (g.UG > slp && (long long)g.UG * g.ns * 2 > LDS_ELEMS) g.UG /= 2;
-  if (g.UG % slp || (long long)g.UG * g.ns * 2 > LDS_ELEMS || g.UG > 256) return hipErrorInvalidValue;
-  int cbmax = (int)(LDS_ELEMS / ((long long)g.UG * g.ns)) - 1;
-  if (cbmax > 256 / g.UG) cbmax = 256 / g.UG;
-  if (cbmax > nx) cbmax = nx;
-  g.ncb = (nx + cbmax - 1) / cbmax;
-  g.CB = (nx + g.ncb - 1) / g.ncb;   // even batches
-  const long long ue_first = g.t0 / W * slp, ue_last = g.t1 / W * slp + slp - 1;
-  g.g0 = ue_first / g.UG;
-  g.ngroup = ue_last / g.UG - g.g0 + 1;
-  if (g.ngroup > 2147483647LL / ((long long)j.ntr * g.ncb)) return hipErrorInvalidValue;
+  col_groups_fill(cg, &g);
+  g.ncb = cg.ncb;
   const unsigned blocks = (unsigned)(g.ngroup * j.ntr * g.ncb);
-  const size_t lds = (size_t)(g.CB + 1) * g.UG * g.ns * 8;
-  hipLaunchKernelGGL(b.sel.ipe == 1 ? wm_column_path_kernel<double> : wm_column_path_kernel<float2>, dim3(blocks), dim3(256), lds, stream,
-                     b, g);
+  hipLaunchKernelGGL(b.sel.ipe == 1 ? wm_column_path_kernel<double> : wm_column_path_kernel<float2>, dim3(blocks), dim3(256),
+                     (size_t)cg.lds_e * 8, stream, b, g);
   e = hipGetLastError();
   if (e != hipSuccess || !b.mass) return e;
-  return column_mass(b.path, 8 / b.sel.ipe, b.sel.n, nx, j.ntr, b.mass, stream);
+  return column_mass(b.path, 8 / b.sel.ipe, b.sel.n, j.ncol_p - 6, j.ntr, b.mass, stream);
 }
 
 hipError_t mpdata_column_path_ref(const void* f, const void* rho, const void* adz, int elem_bytes, long long ld, long long sl0,
@@ -276,13 +263,12 @@ hipError_t mpdata_column_path_ref(const void* f, const void* rho, const void* ad
   const long long rows = (long long)nx * ntr;
   dim3 grid, block(256);
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((ref_column_path_kernel<double>), grid, block, 0, stream, static_cast<const double*>(f), static_cast<const double*>(rho),
-                       static_cast<const double*>(adz), ld, sl0, n, nx, nlev, rows, static_cast<double*>(path));
-  else
-    hipLaunchKernelGGL((ref_column_path_kernel<float>), grid, block, 0, stream, static_cast<const float*>(f), static_cast<const float*>(rho),
-                       static_cast<const float*>(adz), ld, sl0, n, nx, nlev, rows, static_cast<float*>(path));
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((ref_column_path_kernel<R>), grid, block, 0, stream, static_cast<const R*>(f), static_cast<const R*>(rho),
+                       static_cast<const R*>(adz), ld, sl0, n, nx, nlev, rows, static_cast<R*>(path));
+    return hipGetLastError();
+  });
   if (e != hipSuccess || !mass) return e;
   return column_mass(path, elem_bytes, n, nx, ntr, mass, stream);
 }

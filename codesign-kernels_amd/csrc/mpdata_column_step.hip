@@ -25,7 +25,7 @@ namespace {
 
 using namespace wm_walk;
 
-constexpr int LDS_ELEMS = 5120;   // 8-byte elements of LDS per workgroup at most (40 KiB: room for four workgroups per CU)
+// (LDS_ELEMS, the LDS of a workgroup at most, and the column groups of the launch: mpdata_wm_walk.h)
 constexpr int LA = 3;             // levels of operands read ahead of the chain
 enum { SRC = 1, SUB = 2, SED = 4, VS = 8 };   // the stages of a kernel's template argument
 
@@ -407,7 +407,7 @@ template <typename R2>
 hipError_t wm_launch(const MpdataColumnStepJob& b, const WmGrid& wg, const int st, hipStream_t stream) {
   typedef typename Elem<R2>::R R;
   const MpdataLayoutJob& j = b.j;
-  const int nx = j.ncol_p - 6, slp = j.slp;
+  const int slp = j.slp;
   CsArgs<R> g;
   g.f = j.prv;
   g.q = coef<R>(b.a, b.sel.n, j.nlev);
@@ -416,31 +416,15 @@ hipError_t wm_launch(const MpdataColumnStepJob& b, const WmGrid& wg, const int s
   g.tstride = j.prv_tstride; g.tile_stride = j.prv_tile_stride;
   g.t0 = (int)wg.t0; g.t1 = (int)(wg.t0 + wg.ntile - 1);
   g.chunk = (int)j.chunk; g.main_e = (int)j.main_e; g.ncol_p = j.ncol_p; g.nlev = j.nlev; g.slp = slp;
-  g.ns = j.nlev | 1;
-  // 16 units: a coefficient row of the group is a whole 128-byte line (32 where a tile holds 8: a tile per wave while
-  // staging); fewer where one column of 16 does not fit the LDS
-  g.UG = slp >= 8 ? 4 * slp : 16;
-  const int lds_e = LDS_ELEMS - NPAR;   // (the array addresses)
-  while (g.UG > slp && (long long)g.UG * g.ns > lds_e) g.UG /= 2;
-  g.ush = 0;
-  while ((1 << g.ush) < g.UG) ++g.ush;
-  if (g.UG % slp || (1 << g.ush) != g.UG || (long long)g.UG * g.ns > lds_e || g.UG > 256 || j.chunk > 2147483647LL ||
-      j.main_e > 2147483647LL)
+  // the columns and the array addresses alone: the coefficients are read where they lie
+  ColGroups cg;
+  if (j.chunk > 2147483647LL || j.main_e > 2147483647LL ||
+      !col_groups_batched(j, b.sel, wg, LDS_ELEMS, /*fixed*/ NPAR, /*rows*/ 0, /*unit_mul*/ 1, &cg))
     return hipErrorInvalidValue;
-  int cbmax = (int)(lds_e / ((long long)g.UG * g.ns));
-  if (cbmax > 256 / g.UG) cbmax = 256 / g.UG;
-  if (cbmax > nx) cbmax = nx;
-  g.ncb = (nx + cbmax - 1) / cbmax;
-  g.CB = (nx + g.ncb - 1) / g.ncb;   // even batches
-  const long long ue_first = (long long)g.t0 * slp, ue_last = (long long)g.t1 * slp + slp - 1;
-  g.g0 = (int)(ue_first / g.UG);
-  const long long ngroup = ue_last / g.UG - g.g0 + 1;
-  // (unit, tile and block arithmetic of the kernel is in int)
-  if (ngroup > 2147483647LL / ((long long)j.ntr * g.ncb) || ue_last + g.UG > 2147483647LL) return hipErrorInvalidValue;
-  g.ngroup = (int)ngroup;
-  const unsigned blocks = (unsigned)(ngroup * j.ntr * g.ncb);
-  const size_t lds = ((size_t)g.CB * g.UG * g.ns + NPAR) * 8;
-  if (lds > (size_t)LDS_ELEMS * 8) return hipErrorInvalidValue;
+  col_groups_fill(cg, &g);
+  g.ncb = cg.ncb; g.ush = cg.ush;
+  const unsigned blocks = (unsigned)(cg.ngroup * j.ntr * g.ncb);
+  const size_t lds = (size_t)cg.lds_e * 8;
   if (st & SED) {
     dim3 grid;
     if (ref_block_grid(b.sel.n, j.nlev, &grid) != hipSuccess) return hipErrorInvalidValue;
@@ -475,11 +459,10 @@ hipError_t mpdata_column_step_ref(void* f, const void* rho, const void* adz, int
   const long long rows = (long long)nx * ntr;
   dim3 grid;
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL(ref_kernel<double>(st), grid, dim3(256), 0, stream, static_cast<double*>(f), static_cast<const double*>(rho),
-                       static_cast<const double*>(adz), coef<double>(a, n, nlev), ld, sl0, nx, nlev, rows);
-  else
-    hipLaunchKernelGGL(ref_kernel<float>(st), grid, dim3(256), 0, stream, static_cast<float*>(f), static_cast<const float*>(rho),
-                       static_cast<const float*>(adz), coef<float>(a, n, nlev), ld, sl0, nx, nlev, rows);
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL(ref_kernel<R>(st), grid, dim3(256), 0, stream, static_cast<R*>(f), static_cast<const R*>(rho),
+                       static_cast<const R*>(adz), coef<R>(a, n, nlev), ld, sl0, nx, nlev, rows);
+    return hipGetLastError();
+  });
 }

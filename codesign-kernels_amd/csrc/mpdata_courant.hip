@@ -187,13 +187,11 @@ hipError_t mpdata_courant_ref(const void* u, const void* w, const void* rho, con
     const hipError_t e = hipMemsetAsync(cinst, 0, (size_t)n * elem_bytes, stream);
     if (e != hipSuccess) return e;
   }
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((ref_courant_kernel<double>), grid, block, 0, stream, static_cast<const double*>(u), static_cast<const double*>(w),
-                       static_cast<const double*>(rho), static_cast<const double*>(adz), ld, sl0, n, nx, nzm, static_cast<double*>(clev),
-                       static_cast<unsigned long long*>(cinst));
-  else
-    hipLaunchKernelGGL((ref_courant_kernel<float>), grid, block, 0, stream, static_cast<const float*>(u), static_cast<const float*>(w),
-                       static_cast<const float*>(rho), static_cast<const float*>(adz), ld, sl0, n, nx, nzm, static_cast<float*>(clev),
-                       static_cast<unsigned int*>(cinst));
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((ref_courant_kernel<R>), grid, block, 0, stream, static_cast<const R*>(u), static_cast<const R*>(w),
+                       static_cast<const R*>(rho), static_cast<const R*>(adz), ld, sl0, n, nx, nzm, static_cast<R*>(clev),
+                       static_cast<typename Real<R>::U*>(cinst));
+    return hipGetLastError();
+  });
 }

@@ -287,6 +287,7 @@ hipError_t mpdata_diffuse_ref(void* f, const void* rho, const void* adz, int ele
   const long long rows = (long long)nlev * ntr;
   dim3 grid;
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  return elem_bytes == 8 ? ref_launch<double>(f, rho, adz, ld, sl0, n, nx, nlev, rows, tkh, cx, cz, sb, st, zflux, scratch, grid, stream)
-                         : ref_launch<float>(f, rho, adz, ld, sl0, n, nx, nlev, rows, tkh, cx, cz, sb, st, zflux, scratch, grid, stream);
+  return ref_real(elem_bytes, [&](auto r) {
+    return ref_launch<decltype(r)>(f, rho, adz, ld, sl0, n, nx, nlev, rows, tkh, cx, cz, sb, st, zflux, scratch, grid, stream);
+  });
 }

@@ -132,13 +132,9 @@ hipError_t mpdata_level_add_ref(void* f, int elem_bytes, long long ld, long long
   const long long rows = (long long)nlev * ntr;
   dim3 grid, block(256);
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((ref_level_add_kernel<double>), grid, block, 0, stream, static_cast<double*>(f), ld, sl0, n, nx, rows,
-                       static_cast<const double*>(d), clip);
-  else if (elem_bytes == 4)
-    hipLaunchKernelGGL((ref_level_add_kernel<float>), grid, block, 0, stream, static_cast<float*>(f), ld, sl0, n, nx, rows,
-                       static_cast<const float*>(d), clip);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((ref_level_add_kernel<R>), grid, block, 0, stream, static_cast<R*>(f), ld, sl0, n, nx, rows, static_cast<const R*>(d), clip);
+    return hipGetLastError();
+  });
 }

@@ -1,6 +1,7 @@
 // mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3r).  Host
 // code only: the kernels are in mpdata_stats.hip .. mpdata_relax.hip.  A call is its kernel file, a dispatch on the
-// layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays.
+// layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
+// the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
 
 #include "mpdata_cell_add.h"
@@ -88,6 +89,33 @@ int array_sizes(const char* what, int64_t ncrms, int nx, int nz, const int* ntra
   if (!ntracers) return set_err(MPDATA_EINVAL, "%s: bad sizes ncrms=%lld nx=%d nz=%d (need >=1,>=1,>=2)", what, (long long)ncrms, nx, nz);
   return set_err(MPDATA_EINVAL, "%s: bad sizes ncrms=%lld nx=%d nz=%d ntracers=%d (need >=1,>=1,>=2,>=1)", what, (long long)ncrms, nx,
                  nz, *ntracers);
+}
+// the instance range of an array form that takes a block
+int array_block(const char* what, int64_t ncrms, int64_t sl0, int64_t n) {
+  if (n >= 1 && sl0 >= 0 && sl0 <= ncrms - n) return 0;
+  return set_err(MPDATA_EINVAL, "%s: instances [%lld, %lld) outside the arrays' %lld", what, (long long)sl0, (long long)(sl0 + n),
+                 (long long)ncrms);
+}
+// the end of an array form whose work (e: what issuing it returned) goes through a scratch array of the call's own: the
+// array is freed when the work is done, so the call returns after it
+int scratch_done(void* scratch, void* stream, hipError_t e) {
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(scratch);
+  HIP_TRY(e);
+  return 0;
+}
+// the marks of the tracer range after a call has rewritten owned levels (SEAMS: the other copies of a windowed plan are
+// stale, and the inner plan's phantom follows a block that ends the plan, as after a seam refresh) or interior columns
+// (HALOS: a periodic plan's halos are copies of the old interior) of f of the block
+enum { SEAMS = 1, HALOS = 2 };
+int plan_rewrote(mpdata_plan* p, int64_t sl0, int64_t n, int first, int count, int marks) {
+  if ((marks & SEAMS) && p->inner) {
+    memset(p->seam_ok + first, 0, (size_t)count);
+    const int rc = sl0 + n == p->ncrms ? plan_phantom(p->inner, 0, first, count) : 0;
+    if (rc) return rc;
+  }
+  if ((marks & HALOS) && p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
+  return 0;
 }
 
 // ---- Host forms (all tracers, synchronous): the host arrays of a call go through the plan's block staging buffer, in
@@ -495,8 +523,7 @@ static int plan_diffuse(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh,
     HIP_TRY(mpdata_diffuse_ref(ref_f(p, first), p->rho, p->adz, p->eb, p->ncrms, sl0, n, nx, nzm, count, tkh, cx, cz, sb, st, zflux,
                                p->dbuf, p->stream));
   }
-  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
-  return 0;
+  return plan_rewrote(p, sl0, n, first, count, HALOS);
 }
 static int plan_diffuse_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cx,
                               const void* cz, int first, int count, int eb) {
@@ -539,21 +566,16 @@ int mpdata_plan_diffuse_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float*
 // goes through a scratch array of the call's own, which is freed when the work is done: the call returns after it.
 static int diffuse_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* rho, const void* adz,
                          const void* tkh, const void* cx, const void* cz, const void* sb, const void* st, void* zflux, void* stream, int eb) {
-  const int rc = array_sizes("mpdata_diffuse_device", ncrms, nx, nz, &ntracers);
+  int rc = array_sizes("mpdata_diffuse_device", ncrms, nx, nz, &ntracers);
   if (rc) return rc;
-  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
-    return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
-                   (long long)(sl0 + n), (long long)ncrms);
+  rc = array_block("mpdata_diffuse_device", ncrms, sl0, n);
+  if (rc) return rc;
   if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
   if (!tkh || !cx || !cz) return set_err(MPDATA_EINVAL, "mpdata_diffuse_device: null %s", !tkh ? "tkh" : !cx ? "cx" : "cz");
   void* scratch = nullptr;
   HIP_TRY(hipMalloc(&scratch, (size_t)n * nx * (nz - 1) * ntracers * eb));
-  hipError_t e = mpdata_diffuse_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tkh, cx, cz, sb, st, zflux, scratch,
-                                    (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(scratch);
-  HIP_TRY(e);
-  return 0;
+  return scratch_done(scratch, stream, mpdata_diffuse_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tkh, cx, cz, sb, st, zflux,
+                                                          scratch, (hipStream_t)stream));
 }
 int mpdata_diffuse_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
                           const double* adz, const double* tkh, const double* cx, const double* cz, const double* sb, const double* st,
@@ -578,24 +600,19 @@ int mpdata_diffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64
 // Reference-layout plans: the plan's diffusion buffer takes the new rows (mpdata_subside.h).
 static int plan_subside(mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, void* dsum, int first, int count) {
   if (plan_walked(p)) {
-    int rc = plan_seams(p, first, count);
+    const int rc = plan_seams(p, first, count);
     if (rc) return rc;
     MpdataSubsideJob b;
     b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
     b.sel = block_sel(p, sl0, n);
     b.cb = cb; b.cc = cc; b.dsum = dsum;
     HIP_TRY(mpdata_subside_wm(b, p->stream));
-    if (p->inner) {
-      memset(p->seam_ok + first, 0, (size_t)count);
-      if (sl0 + n == p->ncrms) rc = plan_phantom(p->inner, 0, first, count);
-      if (rc) return rc;
-    }
   } else {
     const int rc = plan_dbuf(p, (size_t)n * (p->nx + 6) * (p->nz - 1) * count * p->eb);
     if (rc) return rc;
     HIP_TRY(mpdata_subside_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, cb, cc, dsum, p->dbuf, p->stream));
   }
-  return 0;
+  return plan_rewrote(p, sl0, n, first, count, SEAMS);
 }
 static int plan_subside_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* cb, const void* cc, int first,
                               int count, int eb) {
@@ -637,11 +654,8 @@ static int subside_array(int64_t ncrms, int nx, int nz, int ntracers, void* f, c
   if (!cb || !cc) return set_err(MPDATA_EINVAL, "mpdata_subside_device: null %s", !cb ? "cb" : "cc");
   void* scratch = nullptr;
   HIP_TRY(hipMalloc(&scratch, (size_t)ncrms * (nx + 6) * (nz - 1) * ntracers * eb));
-  hipError_t e = mpdata_subside_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, cb, cc, dsum, scratch, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(scratch);
-  HIP_TRY(e);
-  return 0;
+  return scratch_done(scratch, stream,
+                      mpdata_subside_ref(f, eb, ncrms, 0, ncrms, nx, nz - 1, ntracers, cb, cc, dsum, scratch, (hipStream_t)stream));
 }
 int mpdata_subside_device(int64_t ncrms, int nx, int nz, int ntracers, double* f, const double* cb, const double* cc, double* dsum,
                           void* stream) {
@@ -667,7 +681,7 @@ int mpdata_subside_f32_device(int64_t ncrms, int nx, int nz, int ntracers, float
 // Reference-layout plans: the buffer takes the new interior.
 static int plan_sediment(mpdata_plan* p, int64_t sl0, int64_t n, const void* wp, void* psfc, void* pflux, int first, int count) {
   if (plan_walked(p)) {
-    int rc = plan_seams(p, first, count);
+    const int rc = plan_seams(p, first, count);
     if (rc) return rc;
     const mpdata_plan* q = wm_plan(p);
     MpdataSedimentJob b;
@@ -676,19 +690,13 @@ static int plan_sediment(mpdata_plan* p, int64_t sl0, int64_t n, const void* wp,
     b.sel = block_sel(p, sl0, n);
     b.wp = wp; b.psfc = psfc; b.pflux = pflux;
     HIP_TRY(mpdata_sediment_wm(b, p->stream));
-    if (p->inner) {
-      memset(p->seam_ok + first, 0, (size_t)count);
-      if (sl0 + n == p->ncrms) rc = plan_phantom(p->inner, 0, first, count);
-      if (rc) return rc;
-    }
   } else {
     const int rc = plan_dbuf(p, (size_t)n * p->nx * (p->nz - 1) * count * p->eb);
     if (rc) return rc;
     HIP_TRY(mpdata_sediment_ref(ref_f(p, first), p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, wp, psfc, pflux,
                                 p->dbuf, p->stream));
   }
-  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
-  return 0;
+  return plan_rewrote(p, sl0, n, first, count, SEAMS | HALOS);
 }
 static int plan_sediment_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* wp, int first, int count,
                                int eb) {
@@ -724,20 +732,16 @@ int mpdata_plan_sediment_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float
 // goes through a scratch array of the call's own, which is freed when the work is done: the call returns after it.
 static int sediment_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* rho, const void* adz,
                           const void* wp, void* psfc, void* pflux, void* stream, int eb) {
-  const int rc = array_sizes("mpdata_sediment_device", ncrms, nx, nz, &ntracers);
+  int rc = array_sizes("mpdata_sediment_device", ncrms, nx, nz, &ntracers);
   if (rc) return rc;
-  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
-    return set_err(MPDATA_EINVAL, "mpdata_sediment_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
-                   (long long)(sl0 + n), (long long)ncrms);
+  rc = array_block("mpdata_sediment_device", ncrms, sl0, n);
+  if (rc) return rc;
   if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_sediment_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
   if (!wp) return set_err(MPDATA_EINVAL, "mpdata_sediment_device: null wp");
   void* scratch = nullptr;
   HIP_TRY(hipMalloc(&scratch, (size_t)n * nx * (nz - 1) * ntracers * eb));
-  hipError_t e = mpdata_sediment_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, wp, psfc, pflux, scratch, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(scratch);
-  HIP_TRY(e);
-  return 0;
+  return scratch_done(scratch, stream, mpdata_sediment_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, wp, psfc, pflux, scratch,
+                                                           (hipStream_t)stream));
 }
 int mpdata_sediment_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
                            const double* adz, const double* wp, double* psfc, double* pflux, void* stream) {
@@ -763,7 +767,7 @@ int mpdata_sediment_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int6
 static int plan_vsolve(mpdata_plan* p, int64_t sl0, int64_t n, const void* lo, const void* di, const void* up, int first, int count) {
   const int nzm = p->nz - 1;
   const size_t kb = (size_t)n * nzm * p->eb;
-  int rc = plan_dbuf(p, 2 * kb);
+  const int rc = plan_dbuf(p, 2 * kb);
   if (rc) return rc;
   void* const pf = p->dbuf;
   void* const gf = (char*)p->dbuf + kb;
@@ -774,16 +778,10 @@ static int plan_vsolve(mpdata_plan* p, int64_t sl0, int64_t n, const void* lo, c
     b.sel = block_sel(p, sl0, n);
     b.lo = lo; b.pg = pf;
     HIP_TRY(mpdata_vsolve_wm(b, p->stream));
-    if (p->inner) {
-      memset(p->seam_ok + first, 0, (size_t)count);
-      if (sl0 + n == p->ncrms) rc = plan_phantom(p->inner, 0, first, count);
-      if (rc) return rc;
-    }
   } else {
     HIP_TRY(mpdata_vsolve_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, nzm, count, lo, pf, gf, p->stream));
   }
-  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
-  return 0;
+  return plan_rewrote(p, sl0, n, first, count, SEAMS | HALOS);
 }
 static int plan_vsolve_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* lo, const void* di,
                              const void* up, int first, int count, int eb) {
@@ -819,11 +817,10 @@ int mpdata_plan_vsolve_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* 
 // scratch array of the call's own, which is freed when the work is done: the call returns after it.
 static int vsolve_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* lo, const void* di,
                         const void* up, void* stream, int eb) {
-  const int rc = array_sizes("mpdata_vsolve_device", ncrms, nx, nz, &ntracers);
+  int rc = array_sizes("mpdata_vsolve_device", ncrms, nx, nz, &ntracers);
   if (rc) return rc;
-  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
-    return set_err(MPDATA_EINVAL, "mpdata_vsolve_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
-                   (long long)(sl0 + n), (long long)ncrms);
+  rc = array_block("mpdata_vsolve_device", ncrms, sl0, n);
+  if (rc) return rc;
   if (!f) return set_err(MPDATA_EINVAL, "mpdata_vsolve_device: null f");
   if (!lo || !di || !up) return set_err(MPDATA_EINVAL, "mpdata_vsolve_device: null %s", !lo ? "lo" : !di ? "di" : "up");
   const size_t kb = (size_t)n * (nz - 1) * eb;
@@ -832,10 +829,7 @@ static int vsolve_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0
   void* const gf = (char*)scratch + kb;
   hipError_t e = mpdata_vsolve_factor(lo, di, up, eb, n, nz - 1, scratch, gf, (hipStream_t)stream);
   if (e == hipSuccess) e = mpdata_vsolve_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, lo, scratch, gf, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(scratch);
-  HIP_TRY(e);
-  return 0;
+  return scratch_done(scratch, stream, e);
 }
 int mpdata_vsolve_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* lo,
                          const double* di, const double* up, void* stream) {
@@ -865,16 +859,10 @@ static int plan_cell_add(mpdata_plan* p, int64_t sl0, int64_t n, const void* s, 
     b.sel = block_sel(p, sl0, n);
     b.s = s; b.c = c; b.clip = clip; b.dsum = dsum;
     HIP_TRY(mpdata_cell_add_wm(b, p->stream));
-    if (p->inner) {
-      memset(p->seam_ok + first, 0, (size_t)count);
-      const int rc = sl0 + n == p->ncrms ? plan_phantom(p->inner, 0, first, count) : 0;
-      if (rc) return rc;
-    }
   } else {
     HIP_TRY(mpdata_cell_add_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, s, c, clip, dsum, p->stream));
   }
-  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
-  return 0;
+  return plan_rewrote(p, sl0, n, first, count, SEAMS | HALOS);
 }
 static int plan_cell_add_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* s, int mode, int first,
                                int count, int eb) {
@@ -912,9 +900,8 @@ static int cell_add_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t s
                           void* dsum, void* stream, int eb) {
   int rc = array_sizes("mpdata_cell_add_device", ncrms, nx, nz, &ntracers);
   if (rc) return rc;
-  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
-    return set_err(MPDATA_EINVAL, "mpdata_cell_add_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
-                   (long long)(sl0 + n), (long long)ncrms);
+  rc = array_block("mpdata_cell_add_device", ncrms, sl0, n);
+  if (rc) return rc;
   if (!f) return set_err(MPDATA_EINVAL, "mpdata_cell_add_device: null f");
   if (!s) return set_err(MPDATA_EINVAL, "mpdata_cell_add_device: null s");
   rc = cell_add_mode("mpdata_cell_add_device", mode);
@@ -973,8 +960,7 @@ static int plan_column_step(mpdata_plan* p, int64_t sl0, int64_t n, const Column
   } else {
     HIP_TRY(mpdata_column_step_ref(ref_f(p, first), p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, nzm, count, a, p->stream));
   }
-  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
-  return 0;
+  return plan_rewrote(p, sl0, n, first, count, HALOS);
 }
 // the NULLs and the mode of a call, for the plan forms and the array forms alike
 static int column_step_stages(const char* what, const ColumnStepArgs& x) {
@@ -1035,9 +1021,8 @@ static int column_step_array(int64_t ncrms, int nx, int nz, int ntracers, int64_
   const char* const what = "mpdata_column_step_device";
   int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
   if (rc) return rc;
-  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
-    return set_err(MPDATA_EINVAL, "%s: instances [%lld, %lld) outside the arrays' %lld", what, (long long)sl0, (long long)(sl0 + n),
-                   (long long)ncrms);
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
   if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
   rc = column_step_stages(what, x);
   if (rc) return rc;
@@ -1055,10 +1040,7 @@ static int column_step_array(int64_t ncrms, int nx, int nz, int ntracers, int64_
   a.pg = scratch;
   hipError_t e = mpdata_vsolve_factor(x.lo, x.di, x.up, eb, n, nz - 1, scratch, (char*)scratch + kb, (hipStream_t)stream);
   if (e == hipSuccess) e = mpdata_column_step_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, a, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(scratch);
-  HIP_TRY(e);
-  return 0;
+  return scratch_done(scratch, stream, e);
 }
 int mpdata_column_step_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
                               const double* adz, const double* s, double c, int mode, const double* cb, const double* cc,
@@ -1092,16 +1074,10 @@ static int plan_relax(mpdata_plan* p, int64_t sl0, int64_t n, const void* c, con
     b.sel = block_sel(p, sl0, n);
     b.c = c; b.target = target; b.mean = mean;
     HIP_TRY(mpdata_relax_wm(b, p->stream));
-    if (p->inner) {
-      memset(p->seam_ok + first, 0, (size_t)count);
-      const int rc = sl0 + n == p->ncrms ? plan_phantom(p->inner, 0, first, count) : 0;
-      if (rc) return rc;
-    }
   } else {
     HIP_TRY(mpdata_relax_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, c, target, mean, p->stream));
   }
-  if (p->boundary == MPDATA_BOUNDARY_PERIODIC) memset(p->halo_ok + first, 0, (size_t)count);
-  return 0;
+  return plan_rewrote(p, sl0, n, first, count, SEAMS | HALOS);
 }
 static int plan_relax_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* c, int first, int count, int eb) {
   const int rc = block_ranges(what, p, sl0, n, first, count, eb);
@@ -1135,11 +1111,10 @@ int mpdata_plan_relax_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* c
 // the same on reference-layout device arrays (arguments checked before any device call): in place, asynchronous
 static int relax_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* c, const void* target,
                        void* mean, void* stream, int eb) {
-  const int rc = array_sizes("mpdata_relax_device", ncrms, nx, nz, &ntracers);
+  int rc = array_sizes("mpdata_relax_device", ncrms, nx, nz, &ntracers);
   if (rc) return rc;
-  if (n < 1 || sl0 < 0 || sl0 > ncrms - n)
-    return set_err(MPDATA_EINVAL, "mpdata_relax_device: instances [%lld, %lld) outside the arrays' %lld", (long long)sl0,
-                   (long long)(sl0 + n), (long long)ncrms);
+  rc = array_block("mpdata_relax_device", ncrms, sl0, n);
+  if (rc) return rc;
   if (!f) return set_err(MPDATA_EINVAL, "mpdata_relax_device: null f");
   if (!c) return set_err(MPDATA_EINVAL, "mpdata_relax_device: null c");
   HIP_TRY(mpdata_relax_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, c, target, mean, (hipStream_t)stream));

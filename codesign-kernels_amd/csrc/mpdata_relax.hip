@@ -275,13 +275,10 @@ hipError_t mpdata_relax_ref(void* f, int elem_bytes, long long ld, long long sl0
   const long long rows = (long long)nlev * ntr;
   dim3 grid, block(256);
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((ref_relax_kernel<double>), grid, block, 0, stream, static_cast<double*>(f), ld, sl0, n, nx, nlev, rows,
-                       static_cast<const double*>(c), static_cast<const double*>(target), static_cast<double*>(mean));
-  else if (elem_bytes == 4)
-    hipLaunchKernelGGL((ref_relax_kernel<float>), grid, block, 0, stream, static_cast<float*>(f), ld, sl0, n, nx, nlev, rows,
-                       static_cast<const float*>(c), static_cast<const float*>(target), static_cast<float*>(mean));
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((ref_relax_kernel<R>), grid, block, 0, stream, static_cast<R*>(f), ld, sl0, n, nx, nlev, rows,
+                       static_cast<const R*>(c), static_cast<const R*>(target), static_cast<R*>(mean));
+    return hipGetLastError();
+  });
 }

@@ -114,13 +114,10 @@ hipError_t mpdata_scale_uw_ref(void* a, int elem_bytes, long long ld, long long 
   if (!a || !s || ld < 1 || sl0 < 0 || n < 1 || sl0 + n > ld || ncols < 1 || nlevs < 1) return hipErrorInvalidValue;
   dim3 grid, block(256);
   if (ref_block_grid(n, nlevs, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((ref_scale_uw_kernel<double>), grid, block, 0, stream, static_cast<double*>(a), ld, sl0, n, ncols, (long long)nlevs,
-                       static_cast<const double*>(s));
-  else if (elem_bytes == 4)
-    hipLaunchKernelGGL((ref_scale_uw_kernel<float>), grid, block, 0, stream, static_cast<float*>(a), ld, sl0, n, ncols, (long long)nlevs,
-                       static_cast<const float*>(s));
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((ref_scale_uw_kernel<R>), grid, block, 0, stream, static_cast<R*>(a), ld, sl0, n, ncols, (long long)nlevs,
+                       static_cast<const R*>(s));
+    return hipGetLastError();
+  });
 }

@@ -32,7 +32,7 @@ namespace {
 
 using namespace wm_walk;
 
-constexpr int LDS_ELEMS = 5120;   // 8-byte elements of LDS per workgroup at most (40 KiB: room for four workgroups per CU)
+// (LDS_ELEMS, the LDS of a workgroup at most, and the column groups of the launch: mpdata_wm_walk.h)
 
 __device__ inline double lane_down(const double v) { return __shfl_down(v, 1); }  // the value of lane + 1
 __device__ inline float2 lane_down(const float2 v) { return make_float2(__shfl_down(v.x, 1), __shfl_down(v.y, 1)); }
@@ -395,8 +395,15 @@ hipError_t mpdata_sediment_wm(const MpdataSedimentJob& b, hipStream_t stream) {
   // What follows holds for every plan mpdata_plan_create makes -- slp is 1, 2, 4 or 8, a chunk is 237 elements at most
   // (four slices), wm_block_grid has checked slp == 1 on a windowed plan -- so none of these returns is reached today; a
   // new tiling that breaks one of them must extend the kernel, and fails here, before any launch, until it does.
-  if (wg.nslice > 4 || b.sel.W > 65535) return hipErrorInvalidValue;   // (a tile is a workgroup's at most: 256 elements of a chunk; gridDim.y)
-  const int nx = j.ncol_p - 6, slp = j.slp, W = b.sel.W, tpw = 4 / wg.nslice;
+  // One buffer of wp, the row of quotients and the running sums, 32 units where a tile holds 8; fewer units where two
+  // columns of the group's levels do not fit next to them.
+  const int nx = j.ncol_p - 6, slp = j.slp, W = b.sel.W;
+  ColGroups cg;
+  // (unit, tile and slot-in-LDS arithmetic of the kernel is in int)
+  if (!col_groups_tiled(j, b.sel, wg, LDS_ELEMS, /*fixed*/ W > 1 ? 4 : 0, /*rows*/ 1, /*bufs*/ 1, /*sums*/ true, /*wide*/ true,
+                        &cg) ||
+      (long long)j.ncol_p * j.main_e + j.chunk > 2147483647LL)
+    return hipErrorInvalidValue;
   SedArgs g;
   g.f = j.prv; g.wp = b.wp; g.rho = b.rho; g.adz = b.adz; g.psfc = b.psfc; g.pflux = b.pflux;
   g.n = b.sel.n; g.sl0 = b.sel.sl0; g.nslots = b.sel.ncrms * W;
@@ -404,35 +411,12 @@ hipError_t mpdata_sediment_wm(const MpdataSedimentJob& b, hipStream_t stream) {
   g.chunk = (int)j.chunk; g.main_e = (int)j.main_e; g.ncol_p = j.ncol_p; g.nlev = j.nlev; g.slp = slp;
   g.W = W; g.nz = b.sel.nz;
   g.t0 = (int)wg.t0; g.t1 = (int)(wg.t0 + wg.ntile - 1);
-  g.ns = j.nlev | 1;
   g.nslice = wg.nslice;
-  // 16 units: a row of wp of the group is whole 128-byte lines (32 units where a tile holds 8: a tile per wave); fewer
-  // where two columns of the group's levels, the quotients and the running sums do not fit the LDS
-  g.UG = slp >= 8 ? 4 * slp : 16;
-  for (;;) {
-    const long long per_col = (long long)g.UG * g.ns;
-    g.nround = (g.UG / slp + tpw - 1) / tpw;
-    const long long left = LDS_ELEMS - per_col - (long long)g.nround * 256 - (W > 1 ? 4 : 0);
-    long long cb = left > 0 ? left / per_col : 0;
-    if (cb > NB) cb = NB;
-    if (cb > nx) cb = nx;
-    g.CB = (int)cb;
-    if (g.CB >= 2 || g.CB >= nx || g.UG <= slp) break;
-    g.UG /= 2;
-  }
-  g.ush = 0;
-  while ((1 << g.ush) < g.UG) ++g.ush;
-  if (g.CB < 1 || g.UG % slp || (1 << g.ush) != g.UG || g.UG * b.sel.ipe > 256) return hipErrorInvalidValue;
+  col_groups_fill(cg, &g);
+  g.ush = cg.ush; g.nround = cg.nround;
   // (W > 1: the halves of a pair are windows, not adjacent instances)
   const bool pairs = b.sel.ipe == 2 && W == 1 && b.sel.sl0 % 2 == 0 && b.sel.n % 2 == 0 && reinterpret_cast<uintptr_t>(b.wp) % 8 == 0;
-  const long long ue_last = (long long)g.t1 / W * slp + slp - 1;
-  g.g0 = (int)((long long)g.t0 / W * slp / g.UG);
-  const long long ngroup = ue_last / g.UG - g.g0 + 1;
-  // (unit, tile and slot-in-LDS arithmetic of the kernel is in int)
-  if (ngroup > 2147483647LL / j.ntr || ue_last + g.UG > 2147483647LL || (long long)j.ncol_p * j.main_e + j.chunk > 2147483647LL)
-    return hipErrorInvalidValue;
-  g.ngroup = (int)ngroup;
-  const size_t lds = ((size_t)(g.CB + 1) * g.UG * g.ns + (size_t)g.nround * 256 + (W > 1 ? 4 : 0)) * 8;
+  const size_t lds = (size_t)cg.lds_e * 8;
   void (*k)(SedArgs) = b.sel.ipe == 1 ? (W > 1 ? wm_sediment_kernel<double, true, true> : wm_sediment_kernel<double, false, true>)
                        : W > 1        ? wm_sediment_kernel<float2, true, false>
                        : pairs        ? wm_sediment_kernel<float2, false, true>
@@ -457,6 +441,7 @@ hipError_t mpdata_sediment_ref(void* f, const void* rho, const void* adz, int el
   const long long rows = (long long)nlev * ntr;
   dim3 grid;
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  return elem_bytes == 8 ? ref_launch<double>(f, rho, adz, ld, sl0, n, nx, nlev, rows, wp, psfc, pflux, scratch, grid, stream)
-                         : ref_launch<float>(f, rho, adz, ld, sl0, n, nx, nlev, rows, wp, psfc, pflux, scratch, grid, stream);
+  return ref_real(elem_bytes, [&](auto r) {
+    return ref_launch<decltype(r)>(f, rho, adz, ld, sl0, n, nx, nlev, rows, wp, psfc, pflux, scratch, grid, stream);
+  });
 }

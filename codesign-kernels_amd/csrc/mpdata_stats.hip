@@ -136,13 +136,10 @@ hipError_t mpdata_stats_ref(const void* f, int elem_bytes, long long ld, long lo
   const long long rows = (long long)nlev * ntr;
   dim3 grid, block(256);
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((ref_level_stats_kernel<double>), grid, block, 0, stream, static_cast<const double*>(f), ld, sl0, n, nx, rows,
-                       static_cast<double*>(sum), static_cast<double*>(mn), static_cast<double*>(mx));
-  else if (elem_bytes == 4)
-    hipLaunchKernelGGL((ref_level_stats_kernel<float>), grid, block, 0, stream, static_cast<const float*>(f), ld, sl0, n, nx, rows,
-                       static_cast<float*>(sum), static_cast<float*>(mn), static_cast<float*>(mx));
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((ref_level_stats_kernel<R>), grid, block, 0, stream, static_cast<const R*>(f), ld, sl0, n, nx, rows, static_cast<R*>(sum),
+                       static_cast<R*>(mn), static_cast<R*>(mx));
+    return hipGetLastError();
+  });
 }

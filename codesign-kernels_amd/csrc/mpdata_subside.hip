@@ -240,6 +240,5 @@ hipError_t mpdata_subside_ref(void* f, int elem_bytes, long long ld, long long s
   const long long rows = (long long)nlev * ntr;
   dim3 grid;
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  return elem_bytes == 8 ? ref_launch<double>(f, ld, sl0, n, nx, nlev, rows, cb, cc, dsum, scratch, grid, stream)
-                         : ref_launch<float>(f, ld, sl0, n, nx, nlev, rows, cb, cc, dsum, scratch, grid, stream);
+  return ref_real(elem_bytes, [&](auto r) { return ref_launch<decltype(r)>(f, ld, sl0, n, nx, nlev, rows, cb, cc, dsum, scratch, grid, stream); });
 }

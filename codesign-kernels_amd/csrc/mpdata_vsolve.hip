@@ -30,7 +30,7 @@ namespace {
 
 using namespace wm_walk;
 
-constexpr int LDS_ELEMS = 5120;   // 8-byte elements of LDS per workgroup at most (40 KiB: room for four workgroups per CU)
+// (LDS_ELEMS, the LDS of a workgroup at most, and the column groups of the launch: mpdata_wm_walk.h)
 
 // The workgroups of the plan-layout kernel.  A UNIT is one 8-byte element of the instance axis (an instance, or the pair
 // 2 * ue, 2 * ue + 1 of an fp32 plan): slot ue % slp of tile ue / slp, or, in a windowed plan, the tiles ue * W ..
@@ -370,13 +370,12 @@ hipError_t mpdata_vsolve_factor(const void* lo, const void* di, const void* up, 
   if (!lo || !di || !up || !p || !g || n < 1 || nlev < 1 || (elem_bytes != 4 && elem_bytes != 8)) return hipErrorInvalidValue;
   dim3 grid;
   if (ref_block_grid(n, 1, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((vsolve_factor_kernel<double>), grid, dim3(256), 0, stream, static_cast<const double*>(lo), static_cast<const double*>(di),
-                       static_cast<const double*>(up), n, nlev, static_cast<double*>(p), static_cast<double*>(g));
-  else
-    hipLaunchKernelGGL((vsolve_factor_kernel<float>), grid, dim3(256), 0, stream, static_cast<const float*>(lo), static_cast<const float*>(di),
-                       static_cast<const float*>(up), n, nlev, static_cast<float*>(p), static_cast<float*>(g));
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((vsolve_factor_kernel<R>), grid, dim3(256), 0, stream, static_cast<const R*>(lo), static_cast<const R*>(di),
+                       static_cast<const R*>(up), n, nlev, static_cast<R*>(p), static_cast<R*>(g));
+    return hipGetLastError();
+  });
 }
 
 hipError_t mpdata_vsolve_wm(const MpdataVsolveJob& b, hipStream_t stream) {
@@ -385,7 +384,7 @@ hipError_t mpdata_vsolve_wm(const MpdataVsolveJob& b, hipStream_t stream) {
   if (!b.lo || !b.pg || j.prv_col0 != 0 || j.ncols != j.ncol_p) return hipErrorInvalidValue;
   const hipError_t e = wm_block_grid(j, b.sel, j.ntr, &wg);
   if (e != hipSuccess) return e;
-  const int nx = j.ncol_p - 6, slp = j.slp, W = b.sel.W;
+  const int slp = j.slp, W = b.sel.W;
   VsArgs g;
   g.f = j.prv; g.lo = b.lo; g.pg = b.pg;
   g.n = b.sel.n; g.sl0 = b.sel.sl0; g.ncrms = b.sel.ncrms;
@@ -393,30 +392,17 @@ hipError_t mpdata_vsolve_wm(const MpdataVsolveJob& b, hipStream_t stream) {
   g.t0 = (int)wg.t0; g.t1 = (int)(wg.t0 + wg.ntile - 1);
   g.chunk = (int)j.chunk; g.main_e = (int)j.main_e; g.ncol_p = j.ncol_p; g.nlev = j.nlev; g.slp = slp;
   g.W = W; g.nz = b.sel.nz;
-  g.ns = j.nlev | 1;
-  // 16 units: the coefficient rows of the group are whole 128-byte lines (32 where a tile holds 8: a tile per wave while
-  // staging); fewer where one column and the three coefficient rows of 16 do not fit the LDS
   if (W > 128 || (W > 1 && j.chunk > 64)) return hipErrorInvalidValue;   // (the window table: a thread per slot of a unit; nz < 7000)
-  const int win_e = W > 1 ? 2 * W * b.sel.ipe : 0, lds_e = LDS_ELEMS - win_e;   // the window table: 16 bytes per slot of a unit
-  g.UG = slp >= 8 ? 4 * slp : 16;
-  while (g.UG > slp && (long long)g.UG * g.ns * 4 > lds_e) g.UG /= 2;
-  g.ush = 0;
-  while ((1 << g.ush) < g.UG) ++g.ush;
-  if (g.UG % slp || (1 << g.ush) != g.UG || (long long)g.UG * g.ns * 4 > lds_e || g.UG > 256 || j.chunk > 2147483647LL || j.main_e > 2147483647LL)
+  const int win_e = W > 1 ? 2 * W * b.sel.ipe : 0;   // the window table: 16 bytes per slot of a unit
+  // the three coefficient rows next to the columns; the kernel forms the tiles of a windowed plan from units, in int
+  ColGroups cg;
+  if (j.chunk > 2147483647LL || j.main_e > 2147483647LL ||
+      !col_groups_batched(j, b.sel, wg, LDS_ELEMS, /*fixed*/ win_e, /*rows*/ 3, /*unit_mul*/ W, &cg))
     return hipErrorInvalidValue;
-  int cbmax = (int)(lds_e / ((long long)g.UG * g.ns)) - 3;
-  if (cbmax > 256 / g.UG) cbmax = 256 / g.UG;
-  if (cbmax > nx) cbmax = nx;
-  g.ncb = (nx + cbmax - 1) / cbmax;
-  g.CB = (nx + g.ncb - 1) / g.ncb;   // even batches
-  const long long ue_first = (long long)g.t0 / W * slp, ue_last = (long long)g.t1 / W * slp + slp - 1;
-  g.g0 = (int)(ue_first / g.UG);
-  const long long ngroup = ue_last / g.UG - g.g0 + 1;
-  // (unit, tile and block arithmetic of the kernel is in int)
-  if (ngroup > 2147483647LL / ((long long)j.ntr * g.ncb) || (ue_last + g.UG) * W > 2147483647LL) return hipErrorInvalidValue;
-  g.ngroup = (int)ngroup;
-  const unsigned blocks = (unsigned)(ngroup * j.ntr * g.ncb);
-  const size_t lds = ((size_t)(g.CB + 3) * g.UG * g.ns + (size_t)win_e) * 8;
+  col_groups_fill(cg, &g);
+  g.ncb = cg.ncb; g.ush = cg.ush;
+  const unsigned blocks = (unsigned)(cg.ngroup * j.ntr * g.ncb);
+  const size_t lds = (size_t)cg.lds_e * 8;
   void (*k)(VsArgs) = b.sel.ipe == 1 ? (W > 1 ? wm_vsolve_kernel<double, true> : wm_vsolve_kernel<double, false>)
                                      : (W > 1 ? wm_vsolve_kernel<float2, true> : wm_vsolve_kernel<float2, false>);
   hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, stream, g);
@@ -431,11 +417,10 @@ hipError_t mpdata_vsolve_ref(void* f, int elem_bytes, long long ld, long long sl
   const long long rows = (long long)nx * ntr;
   dim3 grid;
   if (ref_block_grid(n, rows, &grid) != hipSuccess) return hipErrorInvalidValue;
-  if (elem_bytes == 8)
-    hipLaunchKernelGGL((ref_vsolve_kernel<double>), grid, dim3(256), 0, stream, static_cast<double*>(f), static_cast<const double*>(lo),
-                       static_cast<const double*>(p), static_cast<const double*>(g), ld, sl0, n, nx, nlev, rows);
-  else
-    hipLaunchKernelGGL((ref_vsolve_kernel<float>), grid, dim3(256), 0, stream, static_cast<float*>(f), static_cast<const float*>(lo),
-                       static_cast<const float*>(p), static_cast<const float*>(g), ld, sl0, n, nx, nlev, rows);
-  return hipGetLastError();
+  return ref_real(elem_bytes, [&](auto r) {
+    typedef decltype(r) R;
+    hipLaunchKernelGGL((ref_vsolve_kernel<R>), grid, dim3(256), 0, stream, static_cast<R*>(f), static_cast<const R*>(lo),
+                       static_cast<const R*>(p), static_cast<const R*>(g), ld, sl0, n, nx, nlev, rows);
+    return hipGetLastError();
+  });
 }

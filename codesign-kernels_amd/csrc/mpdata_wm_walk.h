@@ -1,11 +1,14 @@
 // mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3r:
 // the twelve kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
 // mpdata_column_path.hip, mpdata_diffuse.hip, mpdata_subside.hip, mpdata_sediment.hip, mpdata_vsolve.hip, mpdata_cell_add.hip,
-// mpdata_column_step.hip, mpdata_relax.hip; their host side is mpdata_plan_blocks.hip): the selector
-// of the block, the element traits and the launch geometry.  Each of those files keeps its kernel whole -- the map wave -> (tracer, tile,
-// element of the column chunk), the map slot -> (instance, tall level) and its march: moving the two maps into functions
-// of this header changes the instructions of the plan-layout kernels (docs/EXPERIMENTS.md N), so they stay where
-// they are until that form has been timed.
+// mpdata_column_step.hip, mpdata_relax.hip; their host side is mpdata_plan_blocks.hip): the selector of the block, the
+// element traits, and on the host side the tile grid, the column-group geometry of the five kernels that stage columns
+// through LDS (col_groups_batched, col_groups_tiled), the LDS limit of a workgroup and the precision dispatch of the
+// reference-layout launches (ref_real).  The host side is free to share: a launcher fills its kernel's argument struct
+// from the result and the kernel is compiled as before.  Each of those files still keeps its kernel whole -- the map
+// wave -> (tracer, tile, element of the column chunk), the map slot -> (instance, tall level) and its march: moving
+// the two maps into functions of this header changes the instructions of the plan-layout kernels (docs/EXPERIMENTS.md
+// N), so they stay where they are until that form has been timed.
 //   A wave owns 64 elements of a tile's column chunk ([tile][column][instance][level], the whole 128-byte lines of every
 //   column first, the rests behind them: mpdata_layout.h) and walks the column slots as linear streams, NB columns in
 //   flight.  The walk knows the storage layout only: LPS 8 .. 64, the one-instance-per-tile forms above 64 levels
@@ -98,6 +101,111 @@ inline hipError_t ref_block_grid(const long long n, const long long rows, dim3* 
   if (gx > 2147483647LL) return hipErrorInvalidValue;
   *grid = dim3((unsigned)gx, (unsigned)(rows < 65535 ? rows : 65535));
   return hipSuccess;
+}
+// ... and its precision: launch(R{}) with R = double or float by the bytes of a real (neither: refused), so that a
+// launch is written once -- `typedef decltype(r) R;` inside the generic lambda names the type
+template <typename F>
+inline hipError_t ref_real(const int elem_bytes, F&& launch) {
+  return elem_bytes == 8 ? launch(double{}) : elem_bytes == 4 ? launch(float{}) : hipErrorInvalidValue;
+}
+
+// ---- column groups: the workgroups of the kernels that stage whole columns of a group of instances through LDS
+// (mpdata_column_path.hip, mpdata_vsolve.hip, mpdata_column_step.hip: columns in batches; mpdata_sediment.hip,
+// mpdata_cell_add.hip: CB columns in flight, a tile per wave).  A UNIT is one 8-byte element of the instance axis (an
+// instance, or the pair 2 * ue, 2 * ue + 1 of an fp32 plan): slot ue % slp of tile ue / slp, or, in a windowed plan, the
+// tiles ue * W .. ue * W + W - 1.  A workgroup takes UG adjacent units (a power of two, a multiple of slp) and CB
+// adjacent columns, re-laid in LDS as [column][unit][ns] with an odd level stride ns.  16 units make a row of a
+// per-instance array of the group whole 128-byte lines (32 where a tile holds 8: a tile per wave while staging); fewer
+// where the LDS does not hold them.
+constexpr int LDS_ELEMS = 5120;   // 8-byte elements of LDS per workgroup at most (40 KiB: room for four workgroups per CU)
+
+struct ColGroups {
+  int UG, ush;              // units of a group, UG = 1 << ush
+  int CB, ncb;              // columns of a batch; batches (tiled: 1)
+  int ns;                   // level stride in LDS (odd)
+  int nround;               // tiled: tiles per wave
+  long long g0, ngroup;     // first group, groups (both fit an int where the units do: UG >= slp)
+  long long lds_e;          // 8-byte elements of LDS of the launch
+};
+
+// the result into the fields all five argument structs have (g0, ngroup: int; long long in column_path's)
+template <typename Args>
+inline void col_groups_fill(const ColGroups& c, Args* a) {
+  a->UG = c.UG; a->CB = c.CB; a->ns = c.ns;
+  a->g0 = static_cast<decltype(a->g0)>(c.g0); a->ngroup = static_cast<decltype(a->ngroup)>(c.ngroup);
+}
+
+// what the two rules share, behind UG, CB, ncb and lds_e: the groups the block's tiles touch and the union of the
+// launchers' guards.  unit_mul: what the kernel multiplies a unit by in int arithmetic -- 1, W where it forms tiles of a
+// windowed plan from units (mpdata_vsolve.hip), 0 where it counts units in long long (mpdata_column_path.hip: its groups
+// may lie beyond 2^31 units, and it goes on running such a plan).
+//   UG is a power of two: it starts at 16 or 4 * slp and halves, and slp is 1, 2, 4 or 8 in every plan mpdata_plan_create
+//     makes (64 / LPS; 1 above 64 levels and in the inner plan of a windowed one), so the test refuses no plan of the
+//     one launcher that did not have it (column_path divides where the others shift).
+//   lds_e <= budget follows from how both rules pick CB -- batched: CB + rows <= (budget - fixed) / (UG * ns); tiled:
+//     bufs * CB * UG * ns <= budget - held -- wherever CB >= 1, which both have checked: the test cannot fire today and
+//     stands guard over a rule that replaces one of them.
+inline bool col_groups_range(const MpdataLayoutJob& j, const MpdataBlockSel& b, const WmGrid& wg, const int budget, const int unit_mul,
+                             ColGroups* g) {
+  g->ush = 0;
+  while ((1 << g->ush) < g->UG) ++g->ush;   // (UG <= 256)
+  if ((1 << g->ush) != g->UG) return false;
+  const long long t1 = wg.t0 + wg.ntile - 1;
+  const long long ue_first = wg.t0 / b.W * j.slp, ue_last = t1 / b.W * j.slp + j.slp - 1;
+  g->g0 = ue_first / g->UG;
+  g->ngroup = ue_last / g->UG - g->g0 + 1;
+  // (blockIdx.x; unit and tile arithmetic of the kernels is in int)
+  return g->ngroup <= 2147483647LL / ((long long)j.ntr * g->ncb) && (ue_last + g->UG) * unit_mul <= 2147483647LL && g->lds_e <= budget;
+}
+
+// Columns in batches over blockIdx.x: next to CB columns the LDS holds `rows` coefficient rows [unit][ns] and `fixed`
+// elements (the window table, the array addresses); UG halves until one column and the rows fit, then the batches are
+// made even.  budget: LDS_ELEMS, or less for more workgroups per CU.  j, b, wg: as wm_block_grid took and made them.
+inline bool col_groups_batched(const MpdataLayoutJob& j, const MpdataBlockSel& b, const WmGrid& wg, const int budget, const int fixed,
+                               const int rows, const int unit_mul, ColGroups* g) {
+  const int nx = j.ncol_p - 6, slp = j.slp, room = budget - fixed;
+  g->ns = j.nlev | 1;
+  g->nround = 0;
+  g->UG = slp >= 8 ? 4 * slp : 16;
+  while (g->UG > slp && (long long)g->UG * g->ns * (1 + rows) > room) g->UG /= 2;
+  if (g->UG % slp || (long long)g->UG * g->ns * (1 + rows) > room || g->UG > 256) return false;
+  int cbmax = (int)(room / ((long long)g->UG * g->ns)) - rows;
+  if (cbmax > 256 / g->UG) cbmax = 256 / g->UG;   // (a lane per (column, unit) pair)
+  if (cbmax > nx) cbmax = nx;
+  g->ncb = (nx + cbmax - 1) / cbmax;
+  g->CB = (nx + g->ncb - 1) / g->ncb;   // even batches
+  g->lds_e = (long long)(g->CB + rows) * g->UG * g->ns + fixed;
+  return col_groups_range(j, b, wg, budget, unit_mul, g);
+}
+
+// A tile per wave, all columns in one workgroup, the windows over blockIdx.y: the LDS holds `bufs` buffers of CB <= NB
+// columns in flight, `rows` coefficient rows, with `sums` the running sums of nround tiles per wave (256 elements a
+// round) and `fixed` elements; UG halves until two columns fit.  wide: 32 units where a tile holds 8.  What the callers
+// say of their guards holds here: a tile is a workgroup's at most (nslice <= 4: 256 elements of a chunk), W <= 65535 is
+// gridDim.y, a lane per instance of the group; none is reached by a plan mpdata_plan_create makes, and a new tiling that
+// breaks one must extend the kernels and fails here, before any launch, until it does.
+inline bool col_groups_tiled(const MpdataLayoutJob& j, const MpdataBlockSel& b, const WmGrid& wg, const int budget, const int fixed,
+                             const int rows, const int bufs, const bool sums, const bool wide, ColGroups* g) {
+  if (wg.nslice > 4 || b.W > 65535) return false;
+  const int nx = j.ncol_p - 6, slp = j.slp, tpw = 4 / wg.nslice;
+  g->ns = j.nlev | 1;
+  g->ncb = 1;
+  g->UG = wide && slp >= 8 ? 4 * slp : slp > 16 ? slp : 16;
+  for (;;) {
+    const long long per_col = (long long)g->UG * g->ns;
+    g->nround = (g->UG / slp + tpw - 1) / tpw;
+    const long long held = fixed + rows * per_col + (sums ? (long long)g->nround * 256 : 0);
+    long long cb = (budget - held) / (bufs * per_col);
+    if (cb < 0) cb = 0;
+    if (cb > NB) cb = NB;
+    if (cb > nx) cb = nx;
+    g->CB = (int)cb;
+    g->lds_e = bufs * cb * per_col + held;
+    if (g->CB >= 2 || g->CB >= nx || g->UG <= slp) break;
+    g->UG /= 2;
+  }
+  if (g->CB < 1 || g->UG % slp || (long long)g->UG * b.ipe > 256) return false;
+  return col_groups_range(j, b, wg, budget, 1, g);
 }
 
 }  // namespace wm_walk

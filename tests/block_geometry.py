@@ -1,7 +1,7 @@
 """What tests/test_block_calls_geometry.py (GPU) and tests/test_block_calls_geometry_cpu.py share: the cases of the six
 calls on a block of instances (include/mpdata_hip.h 3g .. 3l) at sizes beyond one thread block, beyond 65535 rows, at
-hundreds of tiles and beyond 2^32 bytes; their inputs; the launch geometry restated from csrc/mpdata_wm_walk.h,
-csrc/mpdata_column_path.hip and csrc/mpdata_diffuse.hip; and `Truth`, the six numpy models applied to blocks of
+hundreds of tiles and beyond 2^32 bytes; their inputs; the launch geometry restated from csrc/mpdata_wm_walk.h (the tile
+grid and the column groups) and csrc/mpdata_diffuse.hip; and `Truth`, the six numpy models applied to blocks of
 reference-layout arrays.  The models themselves are those of tests/*_model.py, unchanged.
 """
 import numpy as np
@@ -124,7 +124,8 @@ def wm_geometry(shape, dtype, sl0, n, ntr, W=1, nz_w=None):
 
 
 def column_path_geometry(shape, dtype, sl0, n, W=1, nz_w=None):
-    """CpGeom of mpdata_column_path.hip -> dict(UG, CB, ncb, ngroup)"""
+    """col_groups_batched of mpdata_wm_walk.h as mpdata_column_path.hip calls it (4096 elements of LDS, one coefficient
+    row) -> dict(UG, CB, ncb, ngroup)"""
     ncrms, nx, nz = shape
     g = wm_geometry(shape, dtype, sl0, n, 1, W, nz_w)
     slp, ns = g["slp"], ((nz if W == 1 else nz_w) - 1) | 1

@@ -332,6 +332,7 @@ def test_new_kernels_do_not_spill_and_fit_the_lds_budget():
     assert {int(x) for x in re.findall(r"SGPRs Spill: (\d+)", txt)} == {0}
     assert {int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", txt)} == {0}      # (static: none; the dynamic size below)
     src = open(os.path.join(csrc, "mpdata_cell_add.hip")).read()
-    m = re.search(r"constexpr int LDS_ELEMS = (\d+);", src)
+    walk = open(os.path.join(csrc, "mpdata_wm_walk.h")).read()
+    m = re.search(r"constexpr int LDS_ELEMS = (\d+);", walk)                               # (the one statement of the limit)
     assert m and int(m.group(1)) * 8 <= 40 * 1024
-    assert "lds_elems > (size_t)LDS_ELEMS" in src                                          # the launch refuses more
+    assert "col_groups_tiled(j, b.sel, wg, LDS_ELEMS," in src and "g->lds_e <= budget" in walk     # the launch refuses more

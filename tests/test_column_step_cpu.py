@@ -278,9 +278,10 @@ def test_new_kernels_do_not_spill_and_fit_the_lds_budget():
         if "wm_column_step_kernel" in blk.split()[0]:
             assert int(re.search(r" VGPRs: (\d+)", blk).group(1)) <= 128
     src = open(os.path.join(csrc, "mpdata_column_step.hip")).read()
-    m = re.search(r"constexpr int LDS_ELEMS = (\d+);", src)
+    walk = open(os.path.join(csrc, "mpdata_wm_walk.h")).read()
+    m = re.search(r"constexpr int LDS_ELEMS = (\d+);", walk)                               # (the one statement of the limit)
     assert m and int(m.group(1)) * 8 <= 40 * 1024
-    assert "lds > (size_t)LDS_ELEMS * 8" in src                                              # the launch refuses more
+    assert "col_groups_batched(j, b.sel, wg, LDS_ELEMS," in src and "g->lds_e <= budget" in walk     # the launch refuses more
     assert "asm" not in re.sub(r"//.*", "", src)                                             # plain C++
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert re.search(r"mpdata_column_step\$\(O\):.*\n\t\$\(call CC_USAGE,-ffp-contract=off,", mk)

@@ -306,5 +306,7 @@ def test_new_kernels_do_not_spill_and_fit_the_lds_budget():
     assert {int(x) for x in re.findall(r"VGPRs Spill: (\d+)", txt)} == {0}
     assert {int(x) for x in re.findall(r"SGPRs Spill: (\d+)", txt)} == {0}
     src = open(os.path.join(csrc, "mpdata_sediment.hip")).read()
-    m = re.search(r"constexpr int LDS_ELEMS = (\d+);", src)
+    walk = open(os.path.join(csrc, "mpdata_wm_walk.h")).read()
+    m = re.search(r"constexpr int LDS_ELEMS = (\d+);", walk)                               # (the one statement of the limit)
     assert m and int(m.group(1)) * 8 <= 40 * 1024
+    assert "col_groups_tiled(j, b.sel, wg, LDS_ELEMS," in src and "g->lds_e <= budget" in walk     # the launch refuses more
