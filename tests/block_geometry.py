@@ -12,6 +12,7 @@ import diffuse_model as DM
 import level_add_model as AM
 import level_stats_model as LM
 import scale_uw_model as SM
+from util import bits  # (the tests take it from here)
 
 F64, F32 = np.float64, np.float32
 TB = 256            # threads of a block of the reference-layout kernels (x: instances)
@@ -41,11 +42,6 @@ def plan_arrays(inp):
     """the arrays as Plan.upload takes them: one tracer without the tracer axis"""
     T = inp["f"].shape[-1]
     return {k: (np.asfortranarray(v[..., 0]) if k in ("f", "flux") and T == 1 else v) for k, v in inp.items()}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 class Truth:

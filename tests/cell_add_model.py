@@ -10,6 +10,7 @@ sum g = f + p, under CLIP the maximum with zero, the difference g - f_old; the s
 import numpy as np
 
 from oracle.plan_model import EINVAL, ESTATE, EUNSUPPORTED, PlanModel
+from util import bits
 
 ADD, CLIP = 0, 1
 
@@ -52,11 +53,6 @@ def clipped_fraction(f, s, c):
     S = S.reshape(S.shape + (1,)) if S.ndim == 3 else S
     g = F[:, 3:F.shape[1] - 3] + F.dtype.type(c) * S
     return float(np.mean(g < 0))
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 # ---- inputs.  s: uniform in [-0.5, 0.5), another value per cell and tracer.  With |c| <= 1 a call adds at most a half

@@ -15,6 +15,7 @@ import sediment_model as SM
 import subside_model as UM
 import vsolve_model as VM
 from oracle.plan_model import EINVAL, ESTATE, EUNSUPPORTED, PlanModel
+from util import bits
 
 ADD, CLIP = CM.ADD, CM.CLIP
 STAGES = ("source", "subside", "sediment", "vsolve")
@@ -41,11 +42,6 @@ def column_step(f, rho=None, adz=None, s=None, c=1.0, mode=ADD, cb=None, cc=None
         g = VM.vsolve(g, lo, di, up)
     assert g.dtype == f.dtype and g.shape == f.shape
     return np.asfortranarray(g), psfc
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 # ---- inputs: the make_* helpers of the single sections, one seed per call

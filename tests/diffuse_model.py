@@ -11,6 +11,7 @@ of f_new differ from f; columns 0 and nx+1 are read.
 import numpy as np
 
 from oracle.plan_model import EINVAL, ESTATE, EUNSUPPORTED, PERIODIC, PlanModel
+from util import bits
 
 
 def diffuse(f, rho, adz, tkh, cx, cz, sb=None, st=None):
@@ -47,11 +48,6 @@ def diffuse(f, rho, adz, tkh, cx, cz, sb=None, st=None):
     if one_tracer:
         out, zflux = out[..., 0], zflux[..., 0]
     return np.asfortranarray(out), np.asfortranarray(zflux)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 # ---- inputs.  f: the raw signed fields of the oracle's generator (dist 3); halo columns come out of the same generator,

@@ -7,6 +7,8 @@ sum_reversed and sum_pairwise are the wrong orders the input guard of tests/test
 """
 import numpy as np
 
+from util import bits
+
 
 def level_stats(f):
     f = np.asarray(f)
@@ -38,11 +40,6 @@ def sum_pairwise(f):
     while len(parts) > 1:
         parts = [parts[j] + parts[j + 1] if j + 1 < len(parts) else parts[j] for j in range(0, len(parts), 2)]
     return parts[0]
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 def has_negative_zero(a):

@@ -11,6 +11,7 @@ index 3 .. nx+2) of f_new differ from f; halo columns are not read.
 import numpy as np
 
 from oracle.plan_model import EINVAL, ESTATE, EUNSUPPORTED, PlanModel
+from util import bits
 
 
 def relax(f, c, target=None):
@@ -54,11 +55,6 @@ def changed_fraction(f, c, target=None, sl0=0, n=None, first=0, ntr=None):
     new, _ = relax(blk, c, target)
     nx = F.shape[1] - 6
     return float(np.mean(bits(new[:, 3:nx + 3]) != bits(blk[:, 3:nx + 3])))
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 # ---- inputs.  c: zero on the lower half of the levels, uniform in (0, 1] above -- the shape of a damping layer; every

@@ -11,6 +11,7 @@ interior columns 1 .. nx (array index 3 .. nx+2) of f_new differ from f; halo co
 import numpy as np
 
 from oracle.plan_model import EINVAL, ESTATE, EUNSUPPORTED, PlanModel
+from util import bits
 
 
 def sediment(f, rho, adz, wp):
@@ -43,11 +44,6 @@ def sediment(f, rho, adz, wp):
     if one_tracer:
         out, psfc, pflux = out[..., 0], psfc[..., 0], pflux[..., 0]
     return np.asfortranarray(out), np.asfortranarray(psfc), np.asfortranarray(pflux)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 # ---- inputs.  wp: uniform in [-0.05, 0.2), another value per cell and tracer.  With rho, adz in [0.5, 1) the quotient

@@ -10,6 +10,7 @@ updated, the halo columns included.
 import numpy as np
 
 from oracle.plan_model import EINVAL, ESTATE, EUNSUPPORTED, PlanModel
+from util import bits
 
 
 def subside(f, cb, cc):
@@ -39,11 +40,6 @@ def subside(f, cb, cc):
     if one_tracer:
         out, dsum = out[..., 0], dsum[..., 0]
     return np.asfortranarray(out), np.asfortranarray(dsum)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 # ---- inputs.  cb, cc: random, of both signs, another value per instance and level, |.| < 0.3 so that a chain of calls

@@ -23,29 +23,16 @@ import block_geometry as G
 import diffuse_model as DM
 import level_add_model as AM
 import scale_uw_model as SM
+from plan_harness import BAND, _defaults, banded, tdt, upload
 from test_plan_column_path import paths
 from test_plan_courant import cour
 from test_plan_level_add import add
-from test_plan_level_stats import BAND, banded, stats, tdt, upload
+from test_plan_level_stats import stats
 from test_plan_scale_uw import scale
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 SEED = 700
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 def same_bits(a, b):

@@ -21,8 +21,8 @@ import block_geometry as G
 import courant_model as CM
 import diffuse_model as DM
 import scale_uw_model as SM
+from plan_harness import banded, reset_defaults
 from test_block_calls_geometry import bands_ok, same_bits
-from test_plan_level_stats import banded, tdt
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -33,17 +33,10 @@ DTYPES = pytest.mark.parametrize("dt", [G.F32, G.F64], ids=["f32-above-2^31-elem
 
 @pytest.fixture(autouse=True)
 def _defaults_and_free(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
     import torch
-    reset()
+    reset_defaults(mpdata)
     yield
-    reset()
+    reset_defaults(mpdata)
     gc.collect()
     torch.cuda.empty_cache()
 

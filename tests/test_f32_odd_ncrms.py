@@ -11,7 +11,8 @@ shapes that were MPDATA_EUNSUPPORTED or reference-layout plans before."""
 import numpy as np
 import pytest
 
-from test_plan_tall_columns import check, download, make, oracle_steps, upload, w_of
+from plan_harness import reset_defaults, upload
+from test_plan_tall_columns import check, download, make, oracle_steps, w_of
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -31,17 +32,10 @@ def M(mpdata):
 @pytest.fixture(autouse=True)
 def _odd(mpdata):
     """the switch on for the test; the library's defaults before and after"""
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
+    reset_defaults(mpdata)
     mpdata.set_f32_odd_ncrms(1)
     yield
-    reset()
+    reset_defaults(mpdata)
 
 
 VARIANTS = ["exact", "fast"]

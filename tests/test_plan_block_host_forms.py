@@ -24,6 +24,7 @@ import pytest
 
 import diffuse_model as DM
 import subside_model as SM
+from plan_harness import _defaults
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -42,20 +43,6 @@ KINDS = {
 SMALL = [k for k in KINDS if "tall" not in k]
 CASES = [pytest.param(k, b, id=f"{k}-sl{b[0]}n{b[1]}") for k, v in KINDS.items() for b in v[3]]
 CASES_NO_WINDOWS = [c for c in CASES if "tall" not in c.values[0]]
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 _INPUTS = {}

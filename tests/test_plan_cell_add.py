@@ -35,9 +35,10 @@ import numpy as np
 import pytest
 
 import cell_add_model as CM
+import plan_harness as H
 from oracle import plan_model as PM
+from plan_harness import BAND, _defaults, nan_banded, nan_out, upload
 from test_fortran_plan_calls import read_records, write_records
-from test_plan_level_stats import BAND, banded, tdt
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -74,20 +75,6 @@ def factor(name):
     return 0.1 if name == "f32-nz28-even" else 0.75
 
 
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
-
-
 _INPUTS = {}
 
 
@@ -100,19 +87,7 @@ def inputs(oracle, name):
 
 
 def new_plan(M, name, variant=None):
-    shape, T, dt, sw = KINDS[name]
-    M.set_variant(M.VARIANT_EXACT if variant is None else variant)
-    M.set_plan_layout(M.LAYOUT_REFERENCE if sw.get("ref") else M.LAYOUT_WAVEMAJOR)
-    M.set_tall_columns(int(bool(sw.get("tall"))))
-    M.set_f32_odd_ncrms(int(bool(sw.get("odd"))))
-    p = M.Plan(*shape, T, dtype=dt)
-    assert p.layout == (M.LAYOUT_REFERENCE if name in REF else M.LAYOUT_WAVEMAJOR), name
-    assert (p.level_windows > 1) == bool(sw.get("tall")), name
-    return p
-
-
-def upload(p, inp):
-    p.upload(inp["f"], inp["u"], inp["w"], inp["rho"], inp["rhow"], inp["adz"], inp["flux"])
+    return H.new_plan(M, KINDS[name], name, name in REF, bool(KINDS[name][3].get("tall")), variant)
 
 
 def model_of(oracle, name, inp=None):
@@ -123,37 +98,13 @@ def model_of(oracle, name, inp=None):
 
 
 def whole(M, p, name, what=("f", "flux")):
-    """the plan's whole export -> {name: Fortran array WITH a tracer axis}"""
-    import torch
-    shape, T, dt, _ = KINDS[name]
-    sh = M.shapes(*shape, T)
-    t = {k: torch.empty(sh[k], dtype=tdt(dt), device="cuda:0") for k in what}
-    p.export_device(**t)
-    p.sync()
-    return {k: to_host(v).reshape(to_host(v).shape + (() if T > 1 else (1,)), order="F") for k, v in t.items()}
+    return H.whole(M, p, KINDS[name], what)
 
 
 def s_of(name, k, n=None, ntr=None):
     """s (n, nx, nzm, ntr) of a block, another field per k"""
     shape, T, dt, _ = KINDS[name]
     return CM.make_s(shape[0] if n is None else n, shape[1], shape[2], T if ntr is None else ntr, dt, 500 + k)
-
-
-def nan_banded(a, shape):
-    """host array a -> (raw, view of torch `shape`): the bytes of a between two bands of BAND bytes of NaN"""
-    import torch
-    t = to_dev(a).reshape(-1)
-    pad = BAND // t.element_size()
-    raw = torch.full((t.numel() + 2 * pad,), float("nan"), dtype=t.dtype, device="cuda:0")
-    raw[pad:pad + t.numel()] = t
-    return raw, raw[pad:pad + t.numel()].view(tuple(shape))
-
-
-def nan_out(shape, dt):
-    """banded(shape, dt) with every element of the view NaN"""
-    raw, pristine, view = banded(shape, dt)
-    view.fill_(float("nan"))
-    return raw, pristine, view
 
 
 def cell_add(M, p, name, s, c, mode, sl0=0, n=None, first=0, ntr=None, dsum=True, lead=None, call=None):

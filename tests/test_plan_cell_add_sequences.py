@@ -9,17 +9,19 @@ the marks across calls: a windowed plan meets cell_add with fresh seams (behind 
 run) and with seams a call marked stale (behind another cell_add, a sediment, a subside or a vsolve), and the call that
 follows -- a sediment or a subside, which refresh stale seams before they read a neighbour level, a run -- must see the
 NEW field in every copy of a level; a periodic plan meets it with stale and with wrapped halos, and the run or read-back
-that follows must see wrapped copies of the NEW field."""
+that follows must see wrapped copies of the NEW field.
+
+The driver and the plain forms of the other ops: tests/plan_harness.py."""
 import numpy as np
 import pytest
 
 import cell_add_model as CM
 import level_add_model as AM
+import plan_harness as H
 import sediment_model as SM
 import subside_model as UM
 import vsolve_model as VM
-from test_plan_cell_add import nan_banded, nan_out
-from test_plan_level_stats import BAND, tdt
+from plan_harness import _defaults
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -37,142 +39,44 @@ class Model(AM.PlanModelAdd, UM.PlanModelSubside, SM.PlanModelSediment, VM.PlanM
     pass
 
 
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
+def cell_add(s, sl0, n, first, ntr):
+    """(both ops, cell_add and cell_add_clip) c drawn from three factors, then s between NaN bands, then dsum, asked for
+    with probability 0.7 (one draw), NaN-filled between patterned bands"""
+    import torch
+    mode = CM.CLIP if s.op == "cell_add_clip" else CM.ADD
+    c = float(s.rng.choice([0.75, -0.5, 0.1]))
+    a = CM.make_s(n, s.nx, s.nz, ntr, s.dt, s.seed_of_step())
+    sh = s.M.cell_add_shapes(n, s.nx, s.nz, ntr)
+    sraw, sview = H.nan_banded(a, sh["s"])
+    buf = H.nan_out(sh["dsum"], s.dt) if s.rng.random() < 0.7 else None
+    torch.cuda.synchronize()
+    assert s.code(s.p.cell_add, sview, c, mode, buf[2] if buf else None, sl0, n, first, ntr) is None
+    s.p.sync()
+    want = s.m.cell_add(a, c, mode, sl0=sl0, n=n, first=first, ntr=ntr)
+    if buf:
+        raw, pristine, view = buf
+        assert H.bands_kept(raw, pristine)
+        assert_bitwise(to_host(view), want, s.at("dsum", sl0, n, first, ntr))
+
+
+def cell_add_refused(s, sl0, n, first, ntr):
+    M, ncrms, T = s.M, s.ncrms, s.T
+    a = CM.make_s(1, s.nx, s.nz, 1, s.dt, s.seed_of_step())
+    bad = [(ncrms, 1, 0, 1, 0), (0, 1, T, 1, 0), (0, 1, 0, T + 1, 1), (0, 1, 0, 1, 2)][s.count[s.op] % 4]
+    got = s.code(s.p.cell_add, to_dev(a), 0.75, bad[4], None, bad[0], bad[1], bad[2], bad[3])
+    assert got == M.EINVAL == s.m.cell_add(a, 0.75, bad[4], sl0=bad[0], n=bad[1], first=bad[2], ntr=bad[3])
 
 
 @pytest.mark.parametrize("name,shape,T,dt,sw,seed", CASES, ids=[c[0] for c in CASES])
 def test_sequence_with_cell_add(mpdata, oracle, name, shape, T, dt, sw, seed):
-    import torch
-    M = mpdata
-    ncrms, nx, nz = shape
-    M.set_plan_layout(M.LAYOUT_REFERENCE if sw.get("ref") else M.LAYOUT_WAVEMAJOR)
-    M.set_tall_columns(int(bool(sw.get("tall"))))
-    M.set_f32_odd_ncrms(int(bool(sw.get("odd"))))
-    p = M.Plan(*shape, T, dtype=dt)
-    assert p.layout == (M.LAYOUT_REFERENCE if sw.get("ref") else M.LAYOUT_WAVEMAJOR)
-    assert (p.level_windows > 1) == bool(sw.get("tall"))
-    inp = CM.make_plan_inputs(oracle, shape, T, dt, 100 + seed)
-    p.upload(inp["f"], inp["u"], inp["w"], inp["rho"], inp["rhow"], inp["adz"], inp["flux"])
-    m = Model(oracle, *shape, T, dt)
-    assert m.upload({k: np.array(v, order="F") for k, v in inp.items()}) is None
-    rng = np.random.default_rng(seed)
+    s = H.Sequence(mpdata, oracle, Model, CM.make_plan_inputs, name, (shape, T, dt, sw), seed, ref=bool(sw.get("ref")),
+                   windows=bool(sw.get("tall")))
     # (a windowed plan: cell_add behind the import, behind a run, behind a cell_add, and in front of a sediment and a
     # subside, which refresh the seams it marked stale; a periodic one: stale halos, then a run and a block export right
     # behind the call)
-    script = ["cell_add", "run", "cell_add_clip", "cell_add", "sediment", "cell_add", "subside", "vsolve", "cell_add_clip",
-              "set_boundary", "run_tracers", "cell_add", "export_block", "cell_add_clip", "run", "cell_add", "export", "level_add",
-              "cell_add", "run", "import_block", "cell_add", "import", "cell_add_refused"]
-    script += [str(rng.choice(OPS)) for _ in range(STEPS - len(script))]
-    count = dict.fromkeys(OPS, 0)
-
-    def block():
-        sl0 = int(rng.integers(0, ncrms))
-        n = int(rng.integers(1, ncrms - sl0 + 1))
-        if rng.random() < 0.3:
-            sl0, n = 0, ncrms
-        first = int(rng.integers(0, T))
-        return sl0, n, first, int(rng.integers(1, T - first + 1))
-
-    def fresh_f(n, ntr, s):
-        per = [oracle.make_inputs(n, nx, nz, seed=1000 * seed + 10 * s + t, dist=oracle.DIST_RAW_SIGNED, dtype=dt)["f"] - dt(0.5)
-               for t in range(ntr)]
-        return per[0] if ntr == 1 else np.asfortranarray(np.stack(per, axis=-1))
-
-    def code(fn, *a, **kw):
-        """the call's return code: None, or the code of the MpdataError it raises"""
-        try:
-            fn(*a, **kw)
-        except M.MpdataError as e:
-            return e.code
-        return None
-
-    def export():
-        t = {k: torch.empty(M.shapes(*shape, T)[k], dtype=tdt(dt), device="cuda:0") for k in ("f", "flux")}
-        assert code(p.export_device, **t) is None
-        p.sync()
-        want = m.export_device()
-        for k in t:
-            assert_bitwise(to_host(t[k]), want[k], f"{name} step {i}: export of {k}")
-
-    for i, op in enumerate(script):
-        count[op] += 1
-        sl0, n, first, ntr = block()
-        if op == "run":
-            assert code(p.run) is None and m.run() is None
-        elif op == "run_tracers":
-            assert code(p.run, first, ntr) is None and m.run(first, ntr) is None
-        elif op == "export":
-            export()
-        elif op == "export_block":
-            sh = M.shapes(n, nx, nz, ntr)["f"]
-            t = torch.empty(sh, dtype=tdt(dt), device="cuda:0")
-            assert code(p.export_block, sl0, f=t, first_tracer=first) is None
-            p.sync()
-            want = m.export_block(sl0, n, ("f",), first, ntr)["f"]
-            assert_bitwise(to_host(t).reshape(want.shape, order="F"), want, f"{name} step {i}: export of block {sl0, n}")
-        elif op == "set_boundary":
-            mode = 1 - m.boundary
-            assert code(p.set_boundary, mode) is None and m.set_boundary(mode) is None
-            assert p.boundary == mode
-        elif op == "import":
-            f = fresh_f(ncrms, ntr, i)
-            assert code(p.import_device, f=to_dev(f), first_tracer=first) is None
-            assert m.import_device({"f": f}, first, ntr) is None
-        elif op == "import_block":
-            f = fresh_f(n, ntr, i)
-            assert code(p.import_block, sl0, f=to_dev(f), first_tracer=first) is None
-            assert m.import_block(sl0, n, {"f": f}, first, ntr) is None
-        elif op == "level_add":
-            S = float(np.max(np.abs(m.a["f"][sl0:sl0 + n, ..., first:first + ntr])))
-            d = np.asfortranarray((rng.uniform(-1.0, 1.0, (n, nz - 1, ntr)) * S).astype(dt))
-            assert code(p.level_add, to_dev(d), sl0, n, AM.ADD, first) is None
-            assert m.level_add(d, sl0, n, AM.ADD, first) is None
-        elif op == "subside":
-            cb, cc = UM.make_coeffs(n, nz, dt, seed * 100 + i)
-            assert code(p.subside, to_dev(cb), to_dev(cc), None, sl0, n, first, ntr) is None
-            assert m.subside(cb, cc, sl0=sl0, n=n, first=first, ntr=ntr) is not None
-        elif op == "sediment":
-            wp = SM.make_wp(n, nx, nz, ntr, dt, seed * 100 + i)
-            assert code(p.sediment, to_dev(wp), None, None, sl0, n, first, ntr) is None
-            assert not isinstance(m.sediment(wp, sl0=sl0, n=n, first=first, ntr=ntr), int)
-        elif op == "vsolve":
-            lo, di, up = VM.make_coeffs(n, nz, dt, seed * 100 + i)
-            assert code(p.vsolve, to_dev(lo), to_dev(di), to_dev(up), sl0, n, first, ntr) is None
-            assert m.vsolve(lo, di, up, sl0=sl0, n=n, first=first, ntr=ntr) is None
-        elif op == "cell_add_refused":
-            s = CM.make_s(1, nx, nz, 1, dt, seed * 100 + i)
-            bad = [(ncrms, 1, 0, 1, 0), (0, 1, T, 1, 0), (0, 1, 0, T + 1, 1), (0, 1, 0, 1, 2)][count[op] % 4]
-            got = code(p.cell_add, to_dev(s), 0.75, bad[4], None, bad[0], bad[1], bad[2], bad[3])
-            assert got == M.EINVAL == m.cell_add(s, 0.75, bad[4], sl0=bad[0], n=bad[1], first=bad[2], ntr=bad[3])
-        else:
-            mode = CM.CLIP if op == "cell_add_clip" else CM.ADD
-            c = float(rng.choice([0.75, -0.5, 0.1]))
-            s = CM.make_s(n, nx, nz, ntr, dt, seed * 100 + i)
-            sh = M.cell_add_shapes(n, nx, nz, ntr)
-            sraw, sview = nan_banded(s, sh["s"])
-            buf = nan_out(sh["dsum"], dt) if rng.random() < 0.7 else None
-            torch.cuda.synchronize()
-            assert code(p.cell_add, sview, c, mode, buf[2] if buf else None, sl0, n, first, ntr) is None
-            p.sync()
-            want = m.cell_add(s, c, mode, sl0=sl0, n=n, first=first, ntr=ntr)
-            if buf:
-                raw, pristine, view = buf
-                assert torch.equal(raw[:BAND], pristine[:BAND]) and torch.equal(raw[-BAND:], pristine[-BAND:])
-                assert_bitwise(to_host(view), want, f"{name} step {i}: dsum of block {sl0, n} tracers {first, ntr}")
-        assert m.finite()
-    i = len(script)
-    export()
+    count = s.play(["cell_add", "run", "cell_add_clip", "cell_add", "sediment", "cell_add", "subside", "vsolve", "cell_add_clip",
+                    "set_boundary", "run_tracers", "cell_add", "export_block", "cell_add_clip", "run", "cell_add", "export", "level_add",
+                    "cell_add", "run", "import_block", "cell_add", "import", "cell_add_refused"], OPS, STEPS,
+                   {"cell_add": cell_add, "cell_add_clip": cell_add, "cell_add_refused": cell_add_refused})
     assert count["cell_add"] + count["cell_add_clip"] >= 10 and count["run"] + count["run_tracers"] >= 4
     assert count["subside"] >= 1 and count["sediment"] >= 1 and count["vsolve"] >= 1 and count["level_add"] >= 1
-    p.close()

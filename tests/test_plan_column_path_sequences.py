@@ -16,6 +16,7 @@ import pytest
 
 import column_path_model as CP
 from oracle import plan_model as PM
+from plan_harness import _defaults
 from test_plan_column_path import paths, same
 from test_plan_level_add_sequences import draw_d, with_adds
 from test_plan_scale_uw_sequences import ScalePlayer, draw_s, with_scales
@@ -25,20 +26,6 @@ pytestmark = pytest.mark.gpu
 
 SEQ_KINDS = ("wm32", "tall-239")       # an EXACT wave-major plan and a windowed plan
 CASES = [(k, PM.SEEDS[k][0]) for k in SEQ_KINDS]
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 def with_paths(kind, seed, ops):

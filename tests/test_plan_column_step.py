@@ -26,13 +26,14 @@ import pytest
 
 import cell_add_model as CM
 import column_step_model as QM
+import plan_harness as H
 from oracle import plan_model as PM
+from plan_harness import BAND, _defaults, nan_banded, nan_out, upload
 from test_fortran_plan_calls import read_records, write_records
 from test_plan_cell_add import FAST as FAST_ALL
 from test_plan_cell_add import KINDS as KINDS_ALL
 from test_plan_cell_add import PERIODIC as PERIODIC_ALL
-from test_plan_cell_add import G, factor, inputs, nan_banded, nan_out, new_plan, same, snap, upload, whole
-from test_plan_level_stats import BAND
+from test_plan_cell_add import REF, G, factor, inputs, same, snap
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -45,18 +46,12 @@ ADD, CLIP = QM.ADD, QM.CLIP
 ORDER = ("s", "cb", "cc", "wp", "lo", "di", "up")
 
 
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
+def new_plan(M, name, variant=None):
+    return H.new_plan(M, KINDS[name], name, name in REF, False, variant)
+
+
+def whole(M, p, name, what=("f", "flux")):
+    return H.whole(M, p, KINDS[name], what)
 
 
 def test_the_kinds_and_their_runs():

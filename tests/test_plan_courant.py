@@ -14,24 +14,11 @@ import pytest
 
 import courant_model as CM
 import level_stats_model as LM
-from test_plan_level_stats import BAND, banded, chunk_kind, new_plan, tdt, upload
+from plan_harness import BAND, _defaults, banded, tdt, upload
+from test_plan_level_stats import chunk_kind, new_plan
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 BOTH = ("clev", "cinst")

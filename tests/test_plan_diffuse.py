@@ -16,8 +16,9 @@ import numpy as np
 import pytest
 
 import diffuse_model as DM
+import plan_harness as H
 from oracle import plan_model as PM
-from test_plan_level_stats import BAND, banded, tdt
+from plan_harness import BAND, _defaults, banded, tdt, upload
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -39,20 +40,6 @@ KINDS = {
 SEED = 100
 
 
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
-
-
 _INPUTS = {}
 
 
@@ -64,20 +51,10 @@ def inputs(oracle, name):
     return _INPUTS[name]
 
 
-def new_plan(M, name, variant=None, tall=False):
-    shape, T, dt, sw = KINDS[name]
-    M.set_variant(M.VARIANT_EXACT if variant is None else variant)
-    M.set_plan_layout(M.LAYOUT_REFERENCE if sw.get("ref") else M.LAYOUT_WAVEMAJOR)
-    M.set_tall_columns(int(tall))
-    M.set_f32_odd_ncrms(int(bool(sw.get("odd"))))
-    p = M.Plan(*shape, T, dtype=dt)
-    ref = bool(sw.get("ref")) or name.endswith("-odd-ref")
-    assert p.layout == (M.LAYOUT_REFERENCE if ref else M.LAYOUT_WAVEMAJOR), name
-    return p
-
-
-def upload(p, inp):
-    p.upload(inp["f"], inp["u"], inp["w"], inp["rho"], inp["rhow"], inp["adz"], inp["flux"])
+def new_plan(M, name, variant=None):
+    # (the layout from the name too: an odd fp32 plan without the opt-in lands in the reference layout; windows: not asserted)
+    ref = bool(KINDS[name][3].get("ref")) or name.endswith("-odd-ref")
+    return H.new_plan(M, KINDS[name], name, ref, None, variant)
 
 
 def model_of(oracle, name):
@@ -88,20 +65,11 @@ def model_of(oracle, name):
 
 
 def whole(M, p, name, what=("f", "flux")):
-    """the plan's whole export -> {name: Fortran array WITH a tracer axis}"""
-    import torch
-    shape, T, dt, _ = KINDS[name]
-    sh = M.shapes(*shape, T)
-    t = {k: torch.empty(sh[k], dtype=tdt(dt), device="cuda:0") for k in what}
-    p.export_device(**t)
-    p.sync()
-    return {k: to_host(v).reshape(to_host(v).shape + (() if T > 1 else (1,)), order="F") for k, v in t.items()}
+    return H.whole(M, p, KINDS[name], what)
 
 
 def same_as_model(M, p, name, m, what):
-    got, want = whole(M, p, name), m.export_device()
-    for k in ("f", "flux"):
-        assert_bitwise(got[k], want[k], f"{name} {what}: {k}")
+    H.same_as_model(M, p, KINDS[name], name, m, what)
 
 
 def coeffs(name, k, n=None, fluxes=True):

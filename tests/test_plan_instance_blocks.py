@@ -13,6 +13,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from plan_harness import upload
 from test_periodic_api import wrap
 from util import to_dev, to_host
 
@@ -116,10 +117,6 @@ def new_plan(M, case, **kw):
     if not kw:
         assert p.layout == want
     return p
-
-
-def upload(p, inp):
-    p.upload(inp["f"], inp["u"], inp["w"], inp["rho"], inp["rhow"], inp["adz"], inp["flux"])
 
 
 def whole_export(M, p, case):

@@ -17,26 +17,14 @@ import pytest
 
 import level_add_model as AM
 import level_stats_model as LM
+import plan_harness as H
 from oracle import plan_model as PM
-from test_plan_level_stats import BAND, BLOCKS, KINDS, _code, banded, new_plan, tdt, upload
+from plan_harness import BAND, _defaults, banded, upload
+from test_plan_level_stats import BLOCKS, KINDS, _code, new_plan
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 MODES = [(AM.ADD, "add"), (AM.CLIP, "clip")]
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 def dev_d(d):
@@ -58,14 +46,7 @@ def add(p, d, sl0=0, n=None, mode=AM.ADD, first=0):
 
 
 def whole(M, p, name, what=("f", "flux")):
-    """the plan's whole export -> {name: Fortran array WITH a tracer axis}"""
-    import torch
-    shape, T, dt, _ = LM.INPUTS[name]
-    sh = M.shapes(*shape, T)
-    t = {k: torch.empty(sh[k], dtype=tdt(dt), device="cuda:0") for k in what}
-    p.export_device(**t)
-    p.sync()
-    return {k: to_host(v).reshape(to_host(v).shape + (() if T > 1 else (1,)), order="F") for k, v in t.items()}
+    return H.whole(M, p, LM.INPUTS[name], what)
 
 
 def same_as_model(M, p, name, m, what, canon=False):

@@ -16,6 +16,7 @@ import pytest
 
 import level_add_model as AM
 from oracle import plan_model as PM
+from plan_harness import _defaults
 from test_plan_sequences import Player
 from util import assert_bitwise
 
@@ -23,20 +24,6 @@ pytestmark = pytest.mark.gpu
 
 SEQ_KINDS = ("wm32", "ref", "f32-odd-28", "tall-239", "tall-f32-odd-239")
 CASES = [(k, s) for k in SEQ_KINDS for s in PM.SEEDS[k]]
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 def with_adds(kind, seed, ops):

@@ -19,29 +19,10 @@ import numpy as np
 import pytest
 
 import level_stats_model as LM
+from plan_harness import BAND, _defaults, banded, tdt, upload
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
-BAND = 4096
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
-
-
-def tdt(dt):
-    import torch
-    return torch.float64 if np.dtype(dt) == np.float64 else torch.float32
 
 
 def chunk_kind(nz, dt=np.float64):
@@ -57,18 +38,6 @@ def new_plan(M, name, variant=None, ref=False, tall=False, odd=False, **kw):
     M.set_tall_columns(int(tall))
     M.set_f32_odd_ncrms(int(odd))
     return M.Plan(*shape, T, dtype=dt, **kw)
-
-
-def upload(p, inp):
-    p.upload(inp["f"], inp["u"], inp["w"], inp["rho"], inp["rhow"], inp["adz"], inp["flux"])
-
-
-def banded(shape, dt):
-    """(raw bytes, pristine copy, view of `shape` between two bands of BAND patterned bytes)"""
-    import torch
-    nb = int(np.prod(shape)) * np.dtype(dt).itemsize
-    raw = (torch.arange(nb + 2 * BAND, device="cuda:0") % 251).to(torch.uint8)
-    return raw, raw.clone(), raw[BAND:BAND + nb].view(tdt(dt)).view(tuple(shape))
 
 
 def stats(p, dt, nzm, sl0, n, first=0, ntr=None, which=("sum", "min", "max")):

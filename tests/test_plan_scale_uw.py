@@ -19,31 +19,19 @@ import pytest
 
 import courant_model as CM
 import level_stats_model as LM
+import plan_harness as H
 import scale_uw_model as SM
 from oracle import plan_model as PM
+from plan_harness import BAND, _defaults, banded, upload
 from test_plan_courant import cour
-from test_plan_level_add import same_as_model, whole
-from test_plan_level_stats import BAND, BLOCKS, KINDS, _code, banded, new_plan, tdt, upload
+from test_plan_level_add import same_as_model
+from test_plan_level_stats import BLOCKS, KINDS, _code, new_plan
 from test_plan_tall_columns import C_FAST, UNIT
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 BLOCK_INPUTS = [("f64-blocks", {}), ("f32-blocks", dict(odd=True)), ("f64-tall-blocks", dict(tall=True)),
                 ("f32-tall-blocks", dict(tall=True, odd=True))]
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 def dev_s(s):
@@ -79,7 +67,7 @@ def run_equals_oracle(M, oracle, p, name, inp, u, w, what):
     nzm = LM.INPUTS[name][0][2] - 1
     p.run()
     f2, fl2 = oracle.advect(dict(inp, u=u, w=w))
-    got = whole(M, p, name)
+    got = H.whole(M, p, LM.INPUTS[name])
     assert_bitwise(got["f"].reshape(f2.shape, order="F"), f2, f"{name} {what}: f")
     assert_bitwise(got["flux"].reshape(fl2.shape, order="F")[:, :nzm], fl2[:, :nzm], f"{name} {what}: flux")
     return f2
@@ -156,7 +144,7 @@ def test_every_plan_kind(mpdata, oracle, name, sw_, note):
     scale(p, su, sw)
     courant_equals_model(p, name, inp, u2, w2, "FAST upload, su and sw")
     p.run()
-    got = whole(M, p, name, ("f",))["f"].reshape(f_exact.shape, order="F")
+    got = H.whole(M, p, LM.INPUTS[name], ("f",))["f"].reshape(f_exact.shape, order="F")
     fin = inp["f"].reshape(got.shape, order="F")
     for t in range(T):
         sel = (Ellipsis, t) if T > 1 else Ellipsis

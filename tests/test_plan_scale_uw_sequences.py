@@ -18,6 +18,7 @@ import pytest
 
 import scale_uw_model as SM
 from oracle import plan_model as PM
+from plan_harness import _defaults
 from test_plan_level_add_sequences import AddPlayer, draw_d, with_adds
 from util import assert_bitwise
 
@@ -25,20 +26,6 @@ pytestmark = pytest.mark.gpu
 
 SEQ_KINDS = ("wm32", "ref", "ks-72", "f32-28", "f32-odd-28", "tall-239", "tall-f32-odd-239")   # one per kind family
 CASES = [(k, PM.SEEDS[k][0]) for k in SEQ_KINDS]
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 def with_scales(kind, seed, ops):

@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 from oracle import plan_model as PM
+from plan_harness import _defaults
 from test_plan_tall_columns import UNIT, C_FAST, w_of
 from util import assert_bitwise, to_dev, to_host
 
@@ -39,21 +40,6 @@ def M(mpdata):
     import torch
     assert torch.cuda.is_available(), "GPU tests need a device"
     return mpdata
-
-
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    """the library's defaults before and after; a case sets the switches of its kind itself"""
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
 
 
 def unwritten(shape, dt):

@@ -21,10 +21,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import plan_harness as H
 import subside_model as SM
 from oracle import plan_model as PM
+from plan_harness import BAND, _defaults, banded, upload
 from test_fortran_plan_calls import read_records, write_records
-from test_plan_level_stats import BAND, banded, tdt
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -48,20 +49,6 @@ REF = ("f32-nz12-odd-ref", "f64-nz12-ref", "f32-nz12-ref", "f64-nz250-ref")
 SEED = 100
 
 
-@pytest.fixture(autouse=True)
-def _defaults(mpdata):
-    def reset():
-        mpdata.set_tile(-1)
-        mpdata.set_wm_flags(0)
-        mpdata.set_plan_layout(mpdata.LAYOUT_WAVEMAJOR)
-        mpdata.set_variant(mpdata.VARIANT_EXACT)
-        mpdata.set_tall_columns(0)
-        mpdata.set_f32_odd_ncrms(0)
-    reset()
-    yield
-    reset()
-
-
 _INPUTS = {}
 
 
@@ -74,19 +61,7 @@ def inputs(oracle, name):
 
 
 def new_plan(M, name, variant=None):
-    shape, T, dt, sw = KINDS[name]
-    M.set_variant(M.VARIANT_EXACT if variant is None else variant)
-    M.set_plan_layout(M.LAYOUT_REFERENCE if sw.get("ref") else M.LAYOUT_WAVEMAJOR)
-    M.set_tall_columns(int(bool(sw.get("tall"))))
-    M.set_f32_odd_ncrms(int(bool(sw.get("odd"))))
-    p = M.Plan(*shape, T, dtype=dt)
-    assert p.layout == (M.LAYOUT_REFERENCE if name in REF else M.LAYOUT_WAVEMAJOR), name
-    assert (p.level_windows > 1) == bool(sw.get("tall")), name
-    return p
-
-
-def upload(p, inp):
-    p.upload(inp["f"], inp["u"], inp["w"], inp["rho"], inp["rhow"], inp["adz"], inp["flux"])
+    return H.new_plan(M, KINDS[name], name, name in REF, bool(KINDS[name][3].get("tall")), variant)
 
 
 def model_of(oracle, name):
@@ -97,20 +72,11 @@ def model_of(oracle, name):
 
 
 def whole(M, p, name, what=("f", "flux")):
-    """the plan's whole export -> {name: Fortran array WITH a tracer axis}"""
-    import torch
-    shape, T, dt, _ = KINDS[name]
-    sh = M.shapes(*shape, T)
-    t = {k: torch.empty(sh[k], dtype=tdt(dt), device="cuda:0") for k in what}
-    p.export_device(**t)
-    p.sync()
-    return {k: to_host(v).reshape(to_host(v).shape + (() if T > 1 else (1,)), order="F") for k, v in t.items()}
+    return H.whole(M, p, KINDS[name], what)
 
 
 def same_as_model(M, p, name, m, what):
-    got, want = whole(M, p, name), m.export_device()
-    for k in ("f", "flux"):
-        assert_bitwise(got[k], want[k], f"{name} {what}: {k}")
+    H.same_as_model(M, p, KINDS[name], name, m, what)
 
 
 def coeffs(name, k, n=None):

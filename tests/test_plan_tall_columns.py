@@ -14,6 +14,7 @@ on through the new entry point, so none of them can pass without it.
 import numpy as np
 import pytest
 
+from plan_harness import upload
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
@@ -120,10 +121,6 @@ def new_plan(M, inp, **kw):
         assert p.layout == M.LAYOUT_WAVEMAJOR
     assert p.level_windows == w_of(nz) >= 5
     return p
-
-
-def upload(p, inp):
-    p.upload(inp["f"], inp["u"], inp["w"], inp["rho"], inp["rhow"], inp["adz"], inp["flux"])
 
 
 def download(p, inp):

@@ -48,6 +48,12 @@ def max_abs(a, b):
     return float(np.max(np.abs(a - b)))
 
 
+def bits(a):
+    """the bit patterns of a: the unsigned integers of its item size"""
+    a = np.ascontiguousarray(a)
+    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
+
+
 def bit_mismatches(a, b):
     """Indices where a and b differ as bit patterns (so +0.0 != -0.0, and NaNs compare by payload)."""
     a, b = np.asarray(a), np.asarray(b)

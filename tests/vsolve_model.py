@@ -10,6 +10,7 @@ backward sweep x per (instance, column, tracer).  Every f on the right is the ol
 import numpy as np
 
 from oracle.plan_model import EINVAL, ESTATE, EUNSUPPORTED, PlanModel
+from util import bits
 
 
 def factor(lo, di, up):
@@ -86,11 +87,6 @@ def vsolve(f, lo, di, up):
     out[:, 3:nx + 3] = x
     assert out.dtype == dt
     return np.asfortranarray(out[..., 0] if one_tracer else out)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.uint64, 4: np.uint32}[a.dtype.itemsize])
 
 
 # ---- inputs.  lo, up uniform in [-0.4, 0), di = 1 - lo - up (formed in float64, then rounded to the dtype): strictly diagonally dominant by rows with
