@@ -5,8 +5,8 @@
 !
 !   ./plan_calls <input file> <dump file>          (plan_calls_sp: the -DMPDATA_SINGLE build, rp = c_float)
 !
-! Both files are streams of records: name (16 characters), element kind (int32: 1 int32, 2 int64, 3 real32, 4 real64), rank
-! (int32), dims (int64 each), data.  The input file is written by tests/test_fortran_plan_calls.py, which replays the same
+! Both files are streams of records (the format, and the helpers that read and write it, are in calls_common.F90: name,
+! element kind, rank, dims, data).  The input file is written by tests/test_fortran_plan_calls.py, which replays the same
 ! script on the numpy models and compares every record of the dump bit for bit, the return code of every call included: a
 ! code is recorded, never stopped on.  Outputs a call may leave alone are set to SENTINEL before the call.
 !
@@ -22,37 +22,15 @@
 !   3. export_device, download, last_kernel_ms, destroy
 !   4. the array forms on reference-layout device arrays of the same problem: level_stats, level_add (CLIP), diffuse on
 !      (sl0, n), column_path, courant, scale_uw, periodic_halo
-module plan_calls_hip
-  use iso_c_binding
-  implicit none
-  interface
-    ! the program's own copies to and from the device (codesign-kernels_amd/fortran/nested_hip.F90 is the precedent)
-    integer(c_int) function hipMemcpy(dst, src, bytes, kind) bind(C, name="hipMemcpy")
-      import :: c_int, c_ptr, c_size_t
-      type(c_ptr), value :: dst, src
-      integer(c_size_t), value :: bytes
-      integer(c_int), value :: kind      ! 1 host -> device, 2 device -> host
-    end function
-    integer(c_int) function hipDeviceSynchronize() bind(C, name="hipDeviceSynchronize")
-      import :: c_int
-    end function
-  end interface
-end module plan_calls_hip
-
 program plan_calls
   use iso_c_binding
   use mpdata_grid
   use mpdata_hip_mod
-  use plan_calls_hip
+  ! the shared helpers only: the frame of the single-call programs (their plan and arrays) stays out, this script has its own
+  use calls_common, only: SENTINEL, UIN, UOUT, note, put_r, put_i4, get_r, get_i8, dalloc, dfree, to_dev, to_host, &
+                          hipDeviceSynchronize
   implicit none
-#ifdef MPDATA_SINGLE
-  integer(c_int), parameter :: RKIND_CODE = 3
-#else
-  integer(c_int), parameter :: RKIND_CODE = 4
-#endif
-  real(rp), parameter :: SENTINEL = -777.0_rp, FACTOR = 0.75_rp
-  integer, parameter :: UIN = 21, UOUT = 22
-  integer(c_size_t), parameter :: EB = int(storage_size(1.0_rp) / 8, c_size_t)
+  real(rp), parameter :: FACTOR = 0.75_rp
 
   character(len=512) :: infile, outfile
   character(len=16) :: tag
@@ -305,106 +283,5 @@ program plan_calls
   tag = 'end'
   write(UOUT) tag, 1_c_int, 0_c_int
   close(UOUT)
-
-contains
-
-  !> the return code of a call, as a record of its own
-  subroutine note(code, what)
-    integer(c_int), intent(in) :: code
-    character(*), intent(in) :: what
-    call put_i4('rc:' // what, [code], [1])
-  end subroutine note
-
-  subroutine header(name, kind, dims)
-    character(*), intent(in) :: name
-    integer(c_int), intent(in) :: kind
-    integer, intent(in) :: dims(:)
-    character(len=16) :: nm
-    nm = name
-    if (len_trim(name) > 16) error stop 'record name longer than 16 characters'
-    write(UOUT) nm, kind, int(size(dims), c_int), int(dims, c_int64_t)
-  end subroutine header
-
-  subroutine put_r(name, a, dims)
-    character(*), intent(in) :: name
-    real(rp), intent(in) :: a(*)
-    integer, intent(in) :: dims(:)
-    call header(name, RKIND_CODE, dims)
-    write(UOUT) a(1:product(dims))
-  end subroutine put_r
-
-  subroutine put_i4(name, a, dims)
-    character(*), intent(in) :: name
-    integer(c_int), intent(in) :: a(*)
-    integer, intent(in) :: dims(:)
-    call header(name, 1_c_int, dims)
-    write(UOUT) a(1:product(dims))
-  end subroutine put_i4
-
-  !> the next record of the input file must be `name`, of kind `kind` and of exactly the shape `dims`
-  subroutine expect(name, kind, dims)
-    character(*), intent(in) :: name
-    integer(c_int), intent(in) :: kind
-    integer, intent(in) :: dims(:)
-    character(len=16) :: nm
-    integer(c_int) :: k, r
-    integer(c_int64_t) :: d(7)
-    read(UIN) nm, k, r
-    if (trim(nm) /= name .or. k /= kind .or. r /= size(dims)) then
-      write(*,*) 'input record ', trim(nm), k, r, ' where ', name, kind, size(dims), ' was expected'
-      error stop 2
-    end if
-    read(UIN) d(1:r)
-    if (any(d(1:r) /= dims)) then
-      write(*,*) 'input record ', name, ' has the shape ', d(1:r), ', the program declares ', dims
-      error stop 2
-    end if
-  end subroutine expect
-
-  subroutine get_r(name, a, dims)
-    character(*), intent(in) :: name
-    real(rp), intent(out) :: a(*)
-    integer, intent(in) :: dims(:)
-    call expect(name, RKIND_CODE, dims)
-    read(UIN) a(1:product(dims))
-  end subroutine get_r
-
-  subroutine get_i8(name, a, dims)
-    character(*), intent(in) :: name
-    integer(c_int64_t), intent(out) :: a(*)
-    integer, intent(in) :: dims(:)
-    call expect(name, 2_c_int, dims)
-    read(UIN) a(1:product(dims))
-  end subroutine get_i8
-
-  subroutine dalloc(p, nelem)
-    type(c_ptr), intent(out) :: p
-    integer, intent(in) :: nelem
-    p = c_null_ptr
-    call mpdata_check(mpdata_device_alloc_c(p, int(max(nelem, 1), c_int64_t) * int(EB, c_int64_t)), 'mpdata_device_alloc')
-  end subroutine dalloc
-
-  subroutine dfree(p)
-    type(c_ptr), intent(in) :: p
-    call mpdata_check(mpdata_device_free_c(p), 'mpdata_device_free')
-  end subroutine dfree
-
-  !> nelem reals host -> device; the device is idle when this returns
-  subroutine to_dev(p, a, nelem)
-    type(c_ptr), intent(in) :: p
-    real(rp), intent(in), target :: a(*)
-    integer, intent(in) :: nelem
-    if (nelem < 1) return
-    if (hipMemcpy(p, c_loc(a), int(nelem, c_size_t) * EB, 1_c_int) /= 0) error stop 'hipMemcpy to the device failed'
-    if (hipDeviceSynchronize() /= 0) error stop 'hipDeviceSynchronize failed'
-  end subroutine to_dev
-
-  subroutine to_host(a, p, nelem)
-    real(rp), intent(inout), target :: a(*)
-    type(c_ptr), intent(in) :: p
-    integer, intent(in) :: nelem
-    if (nelem < 1) return
-    if (hipMemcpy(c_loc(a), p, int(nelem, c_size_t) * EB, 2_c_int) /= 0) error stop 'hipMemcpy to the host failed'
-  end subroutine to_host
 
 end program plan_calls

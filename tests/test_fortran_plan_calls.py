@@ -18,10 +18,11 @@ tests of each call (tests/test_plan_level_add.py, test_plan_scale_uw.py, test_pl
 CPU tests: the module's text against the header -- every bind(C) interface in count, order AND kind of its dummy arguments, the
 symbol every per-precision macro names, what is public, the identifiers of INTEGRATION.md's Fortran snippets -- and the two
 programs build() leaves behind."""
+import functools
+import glob
 import os
 import re
 import shutil
-import struct
 import subprocess
 import time
 
@@ -31,6 +32,7 @@ import pytest
 import column_path_model as CP
 import courant_model as CM
 import diffuse_model as DM
+import fortran_records as FR
 import level_add_model as AM
 import level_stats_model as LM
 import scale_uw_model as SM
@@ -42,43 +44,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FDIR = os.path.join(ROOT, "codesign-kernels_amd", "fortran")
 MODULE = os.path.join(FDIR, "mpdata_hip_mod.F90")
 HEADER = os.path.join(ROOT, "include", "mpdata_hip.h")
-EXE = {np.float64: os.path.join(ROOT, "tests", "fortran", "plan_calls"), np.float32: os.path.join(ROOT, "tests", "fortran", "plan_calls_sp")}
-KIND = {1: np.int32, 2: np.int64, 3: np.float32, 4: np.float64}
-CODE = {np.dtype(v): k for k, v in KIND.items()}
+TDIR = os.path.join(ROOT, "tests", "fortran")
+EXE = {np.float64: "plan_calls", np.float32: "plan_calls_sp"}
+# every test program, by its source; the suffix of the executable per precision
+PROGRAMS = sorted(os.path.basename(p)[:-len(".F90")] for p in glob.glob(os.path.join(TDIR, "*_calls.F90")))
+SUFFIX = {np.float64: "", np.float32: "_sp"}
+COMMON = "calls_common"          # tests/fortran/calls_common.F90: what the programs share
 SENTINEL, FACTOR, S = -777.0, 0.75, 3
-
-
-# ------------------------------------------------------------------------------------------------ the record streams
-def write_records(path, records, end=False):
-    """records: (name, array) -- name (16 characters), kind, rank, dims, the data in Fortran order; end: the closing record
-    the program puts behind its dump"""
-    with open(path, "wb") as fh:
-        for name, a in records:
-            a = np.asarray(a)
-            assert len(name) <= 16 and name != "end"
-            fh.write(name.ljust(16).encode() + struct.pack("<ii", CODE[a.dtype], a.ndim) + struct.pack(f"<{a.ndim}q", *a.shape))
-            fh.write(a.tobytes(order="F"))
-        if end:
-            fh.write(b"end".ljust(16) + struct.pack("<ii", 1, 0))
-
-
-def read_records(path):
-    """-> [(name, array)], up to the program's closing record `end` (a dump without one is cut short)"""
-    raw, off, out = open(path, "rb").read(), 0, []
-    while True:
-        assert off + 24 <= len(raw), f"the dump ends after {len(out)} records without its closing record"
-        name = raw[off:off + 16].decode().rstrip()
-        kind, rank = struct.unpack_from("<ii", raw, off + 16)
-        off += 24
-        if name == "end":
-            assert off == len(raw)
-            return out
-        dims = struct.unpack_from(f"<{rank}q", raw, off)
-        off += 8 * rank
-        dt = np.dtype(KIND[kind])
-        cnt = int(np.prod(dims))
-        out.append((name, np.frombuffer(raw, dt, cnt, off).reshape(dims, order="F")))
-        off += cnt * dt.itemsize
 
 
 # ------------------------------------------------------------------------------------------------ the cases
@@ -361,12 +333,12 @@ def _built():
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_inputs_subcycle_and_the_stream_round_trips(scripts, tmp_path, name):
-    """(no GPU) the model alone: the condition on ncycle, and write_records / read_records are inverse"""
+    """(no GPU) the model alone: the condition on ncycle, and fortran_records.write_records / read_records are inverse"""
     inputs, want, plan_ncycle = scripts(name)
     check_subcycling(name, want, plan_ncycle)
     path = tmp_path / "records.bin"
-    write_records(path, want, end=True)
-    back = read_records(path)
+    FR.write_records(path, want, end=True)
+    back = FR.read_records(path)
     compare(back, want, name)
     if CASES[name]["tall"]:
         codes = {k: int(a[0]) for k, a in want if k.startswith("rc:diffuse")}
@@ -378,16 +350,10 @@ def test_inputs_subcycle_and_the_stream_round_trips(scripts, tmp_path, name):
 def test_program_matches_the_models(scripts, tmp_path, name):
     inputs, want, plan_ncycle = scripts(name)
     check_subcycling(name, want, plan_ncycle)
-    exe = EXE[CASES[name]["dt"]]
-    assert os.path.exists(exe), f"{exe} is not built (run __graft_entry__.build())"
-    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
-    write_records(fin, list(inputs.items()))
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MPDATA_")}
     t0 = time.perf_counter()
-    res = subprocess.run([exe, str(fin), str(fout)], capture_output=True, text=True, timeout=120, env=env)
+    got = FR.run_program(EXE[CASES[name]["dt"]], list(inputs.items()), tmp_path)
     print(f"{name}: the program ran {time.perf_counter() - t0:.2f} s")
-    assert res.returncode == 0, res.stdout + res.stderr
-    compare(read_records(fout), want, name)
+    compare(got, want, name)
 
 
 # ------------------------------------------------------------------------------------------------ the module's text
@@ -605,7 +571,8 @@ def test_integration_snippets_use_public_names():
 def test_the_programs_are_built_and_bind_the_module_only():
     _built()
     macros, _, _, _ = _module()
-    for dt, exe in EXE.items():
+    assert len(PROGRAMS) >= 7
+    for dt, exe in ((dt, os.path.join(TDIR, prog + sfx)) for prog in PROGRAMS for dt, sfx in SUFFIX.items()):
         assert os.path.exists(exe), f"{exe}: not built (run __graft_entry__.build())"
         syms = subprocess.run(["nm", "-D", "--undefined-only", exe], capture_output=True, text=True, check=True).stdout
         names = [line.split()[-1].split("@")[0] for line in syms.splitlines() if line.strip()]
@@ -614,11 +581,71 @@ def test_the_programs_are_built_and_bind_the_module_only():
         assert {"hipMemcpy", "hipDeviceSynchronize", "mpdata_device_alloc", "mpdata_plan_run", "mpdata_plan_import_device"} <= set(ours)
         single = dt == np.float32
         for sp, dp in macros.values():
-            assert (sp if single else dp) in ours, (exe, sp if single else dp)
+            if os.path.basename(exe) in EXE.values():      # plan_calls calls every interface; the others what their script needs
+                assert (sp if single else dp) in ours, (exe, sp if single else dp)
             assert (dp if single else sp) not in ours, (exe, dp if single else sp)
         # nothing of the library is reached past the module: every mpdata_ symbol is one the module binds
         _, interfaces, _, _ = _module()
         bound = set()
         for itf in interfaces.values():
             bound |= {itf["bind"].strip('"')} if itf["bind"].startswith('"') else set(macros[itf["bind"]])
+        # (_module reads the first interface block; the bindings with a real by value, 3p - 3r, stand in a second one)
+        bound |= set(re.findall(r'bind\(C, name="(mpdata_\w+)"\)', open(MODULE).read()))
         assert {s for s in ours if s.startswith("mpdata_")} <= bound
+
+
+# ------------------------------------------------------------------------------------------------ the build of the programs
+@functools.lru_cache(maxsize=None)
+def _dry_run(single):
+    """the commands `make hip=1 [single=1]` runs from a clean tree, as lists of words: a dry run, nothing is compiled"""
+    res = subprocess.run(["make", "-n", "-B", "hip=1"] + (["single=1"] if single else []), cwd=FDIR, capture_output=True, text=True,
+                         timeout=120)
+    assert res.returncode == 0, res.stdout + res.stderr
+    return [line.split() for line in res.stdout.replace("\\\n", " ").splitlines()]
+
+
+@pytest.fixture(scope="module")
+def ignored(tmp_path_factory):
+    """path relative to the root -> does git ignore it by the project's .gitignore?  Asked of an empty repository that holds
+    a copy of that file, so that the answer depends on the committed text alone and not on who owns the checkout"""
+    repo = tmp_path_factory.mktemp("ignore")
+    subprocess.run(["git", "init", "-q", str(repo)], check=True, capture_output=True)
+    shutil.copy(os.path.join(ROOT, ".gitignore"), repo / ".gitignore")
+
+    def ask(rel):
+        code = subprocess.run(["git", "-C", str(repo), "check-ignore", "-q", "--no-index", rel], capture_output=True).returncode
+        assert code in (0, 1), code
+        return code == 0
+    return ask
+
+
+@pytest.mark.parametrize("dt", list(SUFFIX), ids=["f64", "f32"])
+@pytest.mark.parametrize("prog", PROGRAMS)
+def test_make_links_every_program_and_git_ignores_it(ignored, prog, dt):
+    """every tests/fortran/*_calls.F90 has one link line that compiles it into its executable with the objects of
+    mpdata_hip_mod, mpdata_grid and the shared module, and git ignores that executable (and not its source)"""
+    single = dt == np.float32
+    lines, o = _dry_run(single), ".sp.o" if single else ".o"
+    exe = os.path.join(TDIR, prog + SUFFIX[dt])
+    link = [w for w in lines if "-o" in w and w[w.index("-o") + 1] == exe]
+    assert len(link) == 1, (exe, link)
+    words = link[0]
+    assert os.path.join(TDIR, prog + ".F90") in words and "-c" not in words, words
+    for obj in ("mpdata_hip_mod" + o, "mpdata_grid" + o, COMMON + o):
+        assert obj in words, (obj, words)
+    assert ("-DMPDATA_SINGLE" in words) == single
+    # the shared module is compiled once in this precision
+    assert len([w for w in lines if "-c" in w and os.path.join(TDIR, COMMON + ".F90") in w and COMMON + o in w]) == 1
+    assert ignored(f"tests/fortran/{prog}{SUFFIX[dt]}"), f"git does not ignore tests/fortran/{prog}{SUFFIX[dt]}"
+    assert not ignored(f"tests/fortran/{prog}.F90")
+
+
+def test_the_shared_text_of_the_programs_exists_once():
+    """the helpers and the two HIP runtime interfaces are in one file; no program binds a C name itself"""
+    texts = {p: open(p).read() for p in glob.glob(os.path.join(TDIR, "*.F90"))}
+    for needle in ("subroutine expect", 'name="hipMemcpy"'):
+        holders = [os.path.basename(p) for p, t in texts.items() if needle in t]
+        assert holders == [COMMON + ".F90"], (needle, holders)
+    assert len(PROGRAMS) >= 7
+    for prog in PROGRAMS:
+        assert "bind(C" not in texts[os.path.join(TDIR, prog + ".F90")], prog

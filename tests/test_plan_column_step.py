@@ -18,18 +18,15 @@ The kinds are those of tests/test_plan_cell_add.py without the tall ones: the sm
 wrong -- many slots per tile (nz = 8: a group of 32 units), nx no multiple of the column batch (nx = 11), three groups
 with a ragged last one, two and more slices per tile (nz = 65, 72, 140, 238: the group shrinks until a column fits the
 LDS), fp32 pairs, the phantom of an odd fp32 plan, and the reference layout in its four ways."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import cell_add_model as CM
 import column_step_model as QM
+import fortran_records as FR
 import plan_harness as H
 from oracle import plan_model as PM
 from plan_harness import BAND, _defaults, nan_banded, nan_out, upload
-from test_fortran_plan_calls import read_records, write_records
 from test_plan_cell_add import FAST as FAST_ALL
 from test_plan_cell_add import KINDS as KINDS_ALL
 from test_plan_cell_add import PERIODIC as PERIODIC_ALL
@@ -38,7 +35,6 @@ from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 F64, F32 = np.float64, np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = {k: v for k, v in KINDS_ALL.items() if not v[3].get("tall")}
 FAST = tuple(k for k in FAST_ALL if k in KINDS)
 PERIODIC = tuple(k for k in PERIODIC_ALL if k in KINDS) + ("f32-nz28-even",)
@@ -545,8 +541,6 @@ def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     """the program's factors: 0.75 clipped on the block, 0.1 (a double; the fp32 program's plan rounds it once) on the range"""
     dt, exe, shape, T, (sl0, n), (t1, tn) = FORTRAN[case]
     ncrms, nx, nz = shape
-    exe = os.path.join(ROOT, "tests", "fortran", exe)
-    assert os.path.exists(exe), f"{exe} is not built (run __graft_entry__.build())"
     inp = QM.make_plan_inputs(oracle, shape, T, dt, 103)
     arrs = {k: (inp[k].reshape(inp[k].shape + (1,), order="F") if T == 1 and k in ("f", "flux") else inp[k]) for k in PM.NAMES}
     ka = QM.make_args(n, nx, nz, T, dt, 700)
@@ -556,28 +550,13 @@ def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     records += [("lo_a", ka["lo"]), ("di_a", ka["di"]), ("up_a", ka["up"]), ("lo_b", kb["lo"]), ("di_b", kb["di"]), ("up_b", kb["up"])]
     # the replay on the model
     m = QM.PlanModelColumnStep(oracle, ncrms, nx, nz, T, dt)
-    want = []
-    rc = lambda what, code=None: want.append(("rc:" + what, np.array([0 if code is None else code], np.int32)))
-    rc("set_variant"); rc("create")
-    rc("set_boundary", m.set_boundary(PM.PERIODIC))
-    rc("import", m.import_device({k: np.array(inp[k], order="F") for k in PM.NAMES}))
+    want = FR.want_import(m, inp)
+    rc = lambda what, code=None: want.append(FR.rc(what, code))
     psfc = model_step(m, ka, 0.75, CLIP, sl0, n)
     rc("step_block"); rc("sync")
     want += [("psfc", psfc)]
     model_step(m, kb, 0.1, ADD, first=t1, ntr=tn)
     rc("step_range"); rc("sync")
     rc("step_none", m.column_step())
-    rc("run", m.run()); rc("sync")
-    e = m.export_device()
-    rc("export"); rc("sync")
-    want += [("f_e", e["f"]), ("flux_e", e["flux"])]
-    rc("destroy")
-    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
-    write_records(fin, records)
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MPDATA_")}
-    res = subprocess.run([exe, str(fin), str(fout)], capture_output=True, text=True, timeout=120, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    got = read_records(fout)
-    assert [k for k, _ in got] == [k for k, _ in want]
-    for (k, a), (_, b) in zip(got, want):
-        assert_bitwise(a, np.asfortranarray(b).reshape(a.shape, order="F"), f"{case}: record {k}")
+    want += FR.want_close(m)
+    FR.compare_dump(FR.run_program(exe, records, tmp_path), want, case)

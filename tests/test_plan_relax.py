@@ -32,22 +32,18 @@ in groups of 8: the shapes above are one short group, one whole group, two and t
   (3, 33, 28)      one above: the re-read form, five batches, the last of one column
   (3, 40, 28), (5, 43, 8)          the re-read form with five whole batches; six, the last short, with padding slots
   (7, 33, 28) fp32 odd, (2, 33, 239) tall   the re-read form with pairs, the phantom, split pairs and level windows"""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import fortran_records as FR
 import plan_harness as H
 import relax_model as RM
 from oracle import plan_model as PM
 from plan_harness import BAND, _defaults, nan_banded, nan_out, upload
-from test_fortran_plan_calls import read_records, write_records
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 F64, F32 = np.float64, np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # name -> (shape, tracers, dtype, switches)
 KINDS = {
@@ -575,8 +571,6 @@ def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     """the program's calls: to the horizontal mean on the block, all tracers; to a target on the whole plan, a tracer range"""
     dt, exe, shape, T, (sl0, n), (t1, tn) = FORTRAN[case]
     ncrms, nx, nz = shape
-    exe = os.path.join(ROOT, "tests", "fortran", exe)
-    assert os.path.exists(exe), f"{exe} is not built (run __graft_entry__.build())"
     inp = RM.make_plan_inputs(oracle, shape, T, dt, SEED + 3)
     arrs = {k: (inp[k].reshape(inp[k].shape + (1,), order="F") if T == 1 and k in ("f", "flux") else inp[k]) for k in PM.NAMES}
     c_a = RM.make_c(n, nz, dt, 700)
@@ -586,11 +580,8 @@ def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     records += [(k, arrs[k]) for k in PM.NAMES] + [("c_a", c_a), ("c_b", c_b), ("tgt_b", tgt_b)]
     # the replay on the model
     m = RM.PlanModelRelax(oracle, ncrms, nx, nz, T, dt)
-    want = []
-    rc = lambda what, code=None: want.append(("rc:" + what, np.array([0 if code is None else code], np.int32)))
-    rc("set_variant"); rc("create")
-    rc("set_boundary", m.set_boundary(PM.PERIODIC))
-    rc("import", m.import_device({k: np.array(inp[k], order="F") for k in PM.NAMES}))
+    want = FR.want_import(m, inp)
+    rc = lambda what, code=None: want.append(FR.rc(what, code))
     mean_a = model_relax(m, case, c_a, None, sl0, n)
     rc("relax_block"); rc("sync")
     want += [("mean_a", mean_a)]
@@ -598,17 +589,5 @@ def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     assert_bitwise(mean_b, tgt_b, "mean is the target")
     rc("relax_range"); rc("sync")
     want += [("mean_b", mean_b)]
-    rc("run", m.run()); rc("sync")
-    e = m.export_device()
-    rc("export"); rc("sync")
-    want += [("f_e", e["f"]), ("flux_e", e["flux"])]
-    rc("destroy")
-    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
-    write_records(fin, records)
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MPDATA_")}
-    res = subprocess.run([exe, str(fin), str(fout)], capture_output=True, text=True, timeout=120, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    got = read_records(fout)
-    assert [k for k, _ in got] == [k for k, _ in want]
-    for (k, a), (_, b) in zip(got, want):
-        assert_bitwise(a, np.asfortranarray(b).reshape(a.shape, order="F"), f"{case}: record {k}")
+    want += FR.want_close(m)
+    FR.compare_dump(FR.run_program(exe, records, tmp_path), want, case)

@@ -15,22 +15,18 @@ elements; (3, 2, 65), (3, 2, 72): element 63 | 64 across two waves; (2, 2, 140):
 four slices; (70, 3, 28) with 3 tracers: more than one workgroup.  fp32: pairs (even), the phantom (odd with the switch),
 the reference layout (odd without it).  Windowed plans (nz > 238 with set_tall_columns): 239 and 300 levels, fp32 with 15
 pseudo-instances (an inner phantom); 250 levels without the switch is a reference-layout plan."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import fortran_records as FR
 import plan_harness as H
 import subside_model as SM
 from oracle import plan_model as PM
 from plan_harness import BAND, _defaults, banded, upload
-from test_fortran_plan_calls import read_records, write_records
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 F64, F32 = np.float64, np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # name -> (shape, tracers, dtype, switches)
 KINDS = {
@@ -385,8 +381,6 @@ FORTRAN = {"f64": (F64, "subside_calls", (7, 5, 10), 3, (2, 3), (1, 2)), "f32": 
 def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     dt, exe, shape, T, (sl0, n), (t1, tn) = FORTRAN[case]
     ncrms, nx, nz = shape
-    exe = os.path.join(ROOT, "tests", "fortran", exe)
-    assert os.path.exists(exe), f"{exe} is not built (run __graft_entry__.build())"
     inp = SM.make_plan_inputs(oracle, shape, T, dt, SEED + 3)
     cb_a, cc_a = SM.make_coeffs(n, nz, dt, 700)
     cb_b, cc_b = SM.make_coeffs(ncrms, nz, dt, 701)
@@ -394,27 +388,12 @@ def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     records += [(k, inp[k]) for k in PM.NAMES] + [("cb_a", cb_a), ("cc_a", cc_a), ("cb_b", cb_b), ("cc_b", cc_b)]
     # the replay on the model
     m = SM.PlanModelSubside(oracle, ncrms, nx, nz, T, dt)
-    want = []
-    rc = lambda what, code=None: want.append(("rc:" + what, np.array([0 if code is None else code], np.int32)))
-    rc("set_variant"); rc("create")
-    rc("set_boundary", m.set_boundary(PM.PERIODIC))
-    rc("import", m.import_device({k: np.array(inp[k], order="F") for k in PM.NAMES}))
+    want = FR.want_import(m, inp)
+    rc = lambda what, code=None: want.append(FR.rc(what, code))
     dsum = m.subside(cb_a, cc_a, sl0=sl0, n=n)
     rc("subside_block"); rc("sync")
     want.append(("dsum", dsum))
     assert m.subside(cb_b, cc_b, first=t1, ntr=tn) is not None
     rc("subside_range"); rc("sync")
-    rc("run", m.run()); rc("sync")
-    e = m.export_device()
-    rc("export"); rc("sync")
-    want += [("f_e", e["f"]), ("flux_e", e["flux"])]
-    rc("destroy")
-    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
-    write_records(fin, records)
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MPDATA_")}
-    res = subprocess.run([exe, str(fin), str(fout)], capture_output=True, text=True, timeout=120, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    got = read_records(fout)
-    assert [k for k, _ in got] == [k for k, _ in want]
-    for (k, a), (_, b) in zip(got, want):
-        assert_bitwise(a, np.asfortranarray(b).reshape(a.shape, order="F"), f"{case}: record {k}")
+    want += FR.want_close(m)
+    FR.compare_dump(FR.run_program(exe, records, tmp_path), want, case)

@@ -17,22 +17,18 @@ than one; nx = 1 and 11; 1 and 3 tracers; nz = 2 (one level: the array forms onl
 66 (two slices), 72 (a tail wave), 130 (three slices), 238.  fp32: pairs (even, 37 pairs), the phantom (odd with the
 switch, 19 elements), the reference layout (odd without it).  Windowed plans (nz > 238 with set_tall_columns): 239 and 300
 levels fp64, 250 fp32, three groups of 239 levels, fp32 with an odd number of instances (an inner phantom)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import fortran_records as FR
 import plan_harness as H
 import vsolve_model as VM
 from oracle import plan_model as PM
 from plan_harness import _defaults, nan_banded, upload
-from test_fortran_plan_calls import read_records, write_records
 from util import assert_bitwise, to_dev, to_host
 
 pytestmark = pytest.mark.gpu
 F64, F32 = np.float64, np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = 16
 
 # name -> (shape, tracers, dtype, switches)
@@ -417,8 +413,6 @@ FORTRAN = {
 def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     dt, exe, shape, T, (sl0, n), (t1, tn) = FORTRAN[case]
     ncrms, nx, nz = shape
-    exe = os.path.join(ROOT, "tests", "fortran", exe)
-    assert os.path.exists(exe), f"{exe} is not built (run __graft_entry__.build())"
     inp = VM.make_plan_inputs(oracle, shape, T, dt, SEED + 3)
     arrs = {k: (inp[k].reshape(inp[k].shape + (1,), order="F") if T == 1 and k in ("f", "flux") else inp[k]) for k in PM.NAMES}
     ca, cb = VM.make_coeffs(n, nz, dt, 700), VM.make_coeffs(ncrms, nz, dt, 701)
@@ -427,27 +421,12 @@ def test_fortran_program_matches_the_model(oracle, tmp_path, case):
     records += [(k + "_a", a) for k, a in zip(("lo", "di", "up"), ca)] + [(k + "_b", a) for k, a in zip(("lo", "di", "up"), cb)]
     # the replay on the model
     m = VM.PlanModelVsolve(oracle, ncrms, nx, nz, T, dt)
-    want = []
-    rc = lambda what, code=None: want.append(("rc:" + what, np.array([0 if code is None else code], np.int32)))
-    rc("set_variant"); rc("create")
-    rc("set_boundary", m.set_boundary(PM.PERIODIC))
-    rc("import", m.import_device({k: np.array(inp[k], order="F") for k in PM.NAMES}))
+    want = FR.want_import(m, inp)
+    rc = lambda what, code=None: want.append(FR.rc(what, code))
     rc("vs_block", m.vsolve(*ca, sl0=sl0, n=n)); rc("sync")
     e = m.export_device()
     rc("export"); rc("sync")
     want += [("f_a", e["f"]), ("flux_a", e["flux"])]
     rc("vs_range", m.vsolve(*cb, first=t1, ntr=tn)); rc("sync")
-    rc("run", m.run()); rc("sync")
-    e = m.export_device()
-    rc("export"); rc("sync")
-    want += [("f_e", e["f"]), ("flux_e", e["flux"])]
-    rc("destroy")
-    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
-    write_records(fin, records)
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MPDATA_")}
-    res = subprocess.run([exe, str(fin), str(fout)], capture_output=True, text=True, timeout=120, env=env)
-    assert res.returncode == 0, res.stdout + res.stderr
-    got = read_records(fout)
-    assert [k for k, _ in got] == [k for k, _ in want]
-    for (k, a), (_, b) in zip(got, want):
-        assert_bitwise(a, np.asfortranarray(b).reshape(a.shape, order="F"), f"{case}: record {k}")
+    want += FR.want_close(m)
+    FR.compare_dump(FR.run_program(exe, records, tmp_path), want, case)
