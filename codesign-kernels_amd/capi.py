@@ -188,6 +188,14 @@ def lib():
         for name in ("mpdata_relax_device", "mpdata_relax_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 4 + [vp]
+        L.mpdata_plan_vdiffuse_device.restype = ci
+        L.mpdata_plan_vdiffuse_device.argtypes = [vp, i64, i64, vp, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_vdiffuse", "mpdata_plan_vdiffuse_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp, dp, dp]
+        for name in ("mpdata_vdiffuse_device", "mpdata_vdiffuse_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 7 + [vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -932,6 +940,28 @@ class Plan:
         ptrs = [None if a is None else self._block_host(a, name, (n, nzm)) for name, a in (("lo", lo), ("di", di), ("up", up))]
         _check(getattr(lib(), "mpdata_plan_vsolve" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def vdiffuse(self, tkh, cz, sb=None, st=None, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """Implicit vertical diffusion of f with a per-cell diffusivity, in place (include/mpdata_hip.h 3s) on the interior
+        columns of instances [sl0, sl0+n) (default: the rest of the plan from sl0): backward Euler of 3l's vertical part,
+        the tridiagonal matrix of every column formed from tkh and cz and solved without pivoting, on the plan's stream
+        (mpdata_plan_vdiffuse_device).  Reference-layout DEVICE tensors of the plan's precision, shapes vdiffuse_shapes(n,
+        nx, nz): tkh (nzm, nx+2, n), 3l's array as it is; cz (nzm, n); sb, st (nx, n) or None (zero flux).  The tracers are
+        first_tracer .. +ntr-1, ntr = ntracers (else 1).  Windowed plans: MpdataError (EUNSUPPORTED)."""
+        n = self._block_n(sl0, n)
+        ntr, _ = self._block_ntr(None, ntracers)
+        sh = vdiffuse_shapes(n, self.dims[1], self.dims[2])
+        ptrs = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("tkh", tkh), ("cz", cz), ("sb", sb), ("st", st))]
+        _check(lib().mpdata_plan_vdiffuse_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
+
+    def vdiffuse_host(self, tkh, cz, sb=None, st=None, sl0=0, n=None):
+        """The same for all tracers from HOST arrays (numpy, Fortran order): tkh (n, nx+2, nzm), cz (n, nzm), sb, st (n, nx)
+        or None, synchronous (mpdata_plan_vdiffuse[_f32])."""
+        n = self._block_n(sl0, n)
+        nx, nzm = self.dims[1], self.dims[2] - 1
+        ptrs = [None if a is None else self._block_host(a, name, want)
+                for name, a, want in (("tkh", tkh, (n, nx + 2, nzm)), ("cz", cz, (n, nzm)), ("sb", sb, (n, nx)), ("st", st, (n, nx)))]
+        _check(getattr(lib(), "mpdata_plan_vdiffuse" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def cell_add(self, s, c=1.0, mode=CELL_ADD, dsum=None, sl0=0, n=None, first_tracer=0, ntracers=None):
         """Per-cell sources of f in place (include/mpdata_hip.h 3p) on the interior columns of instances [sl0, sl0+n)
         (default: the rest of the plan from sl0): f += c * s, the product and the sum each rounded once; mode CELL_ADD
@@ -1317,6 +1347,35 @@ def vsolve(f, lo, di, up, sl0=0, n=None, stream=None):
     ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("lo", lo), ("di", di), ("up", up))]
     fn = lib().mpdata_vsolve_device if f.dtype == torch.float64 else lib().mpdata_vsolve_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, *ptrs, _stream_handle(stream)))
+
+
+def vdiffuse_shapes(n, nx, nz):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a vdiffuse call on n instances: tkh (nzm,
+    nx+2, n), cz (nzm, n), sb, st (nx, n)."""
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {"tkh": (nz - 1, nx + 2, n), "cz": (nz - 1, n), "sb": (nx, n), "st": (nx, n)}
+
+
+def vdiffuse(f, rho, adz, tkh, cz, sb=None, st=None, sl0=0, n=None, stream=None):
+    """Implicit vertical diffusion with a per-cell diffusivity (include/mpdata_hip.h 3s) of instances [sl0, sl0+n) (default:
+    the rest from sl0) of a reference-layout DEVICE tensor f ([ntr,] nzm, nx+6, ncrms) with rho, adz (nzm, ncrms), float64 or
+    float32, in place; tkh, cz, sb, st of the same dtype with the shapes of vdiffuse_shapes(n, nx, nz) (sb, st may be None).
+    Enqueued on `stream`; returns when the work is done (mpdata_vdiffuse_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"vdiffuse: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    pr = _dev_ptr(rho, (nzm, ncrms), "rho", f.dtype)
+    pa = _dev_ptr(adz, (nzm, ncrms), "adz", f.dtype)
+    sh = vdiffuse_shapes(n, nxp6 - 6, nzm + 1)
+    ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("tkh", tkh), ("cz", cz), ("sb", sb), ("st", st))]
+    fn = lib().mpdata_vdiffuse_device if f.dtype == torch.float64 else lib().mpdata_vdiffuse_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, *ptrs, _stream_handle(stream)))
 
 
 def subside_device(f, cb, cc, dsum=None, stream=None):

@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3r).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_relax.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3s).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_vdiffuse.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -16,6 +16,7 @@
 #include "mpdata_sediment.h"
 #include "mpdata_stats.h"
 #include "mpdata_subside.h"
+#include "mpdata_vdiffuse.h"
 #include "mpdata_vsolve.h"
 
 using namespace mpd;
@@ -1127,6 +1128,96 @@ int mpdata_relax_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0
 int mpdata_relax_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* c,
                             const float* target, float* mean, void* stream) {
   return relax_array(ncrms, nx, nz, ntracers, sl0, n, f, c, target, mean, stream, 4);
+}
+
+// ---- 3s: implicit vertical diffusion of f with a per-cell diffusivity, in place.  Reads tkh, cz, sb, st and the plan's rho
+// and adz, rewrites the INTERIOR columns of f of the block's instances and the tracer range; flux, u, w, rho, rhow, adz and
+// the boundary mode are not touched and no event is recorded.
+//   halo marks  halo columns are neither read nor written, so no wrap is launched in front; afterwards a periodic plan's
+//               halos are copies of the OLD interior: the marks of the range are cleared and the next run or read-back
+//               wraps again;
+//   windowed    refused in the check: the backward sweep needs g of every cell of the windows below, which a second pass
+//               would have to park in device memory;
+//   phantom     follows the plan's last slot inside the kernel (mpdata_vdiffuse.h).
+// Wave-major plans: tkh is read where it lies; a small kernel in front writes 1 / (rho * adz) (n nzm reals) into the plan's
+// diffusion buffer.  Reference-layout plans: the buffer takes g of every cell of the block (n nx nzm reals).
+static int plan_vdiffuse(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cz, const void* sb, const void* st,
+                         int first, int count) {
+  const int nzm = p->nz - 1;
+  const bool wm = plan_walked(p);
+  const int rc = plan_dbuf(p, (size_t)n * nzm * p->eb * (wm ? 1 : p->nx));
+  if (rc) return rc;
+  if (wm) {
+    MpdataVdiffuseJob b;
+    b.j = wm_job(p, 0, nullptr, first, count);
+    kc_rho_adz(p, b);
+    b.sel = block_sel(p, sl0, n);
+    b.ir = p->dbuf;
+    b.tkh = tkh; b.cz = cz; b.sb = sb; b.st = st;
+    HIP_TRY(mpdata_vdiffuse_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_vdiffuse_ref(ref_f(p, first), p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, nzm, count, tkh, cz, sb, st, p->dbuf,
+                                p->stream));
+  }
+  return plan_rewrote(p, sl0, n, first, count, HALOS);
+}
+static int plan_vdiffuse_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cz, int first,
+                               int count, int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  if (rc) return rc;
+  if (!tkh || !cz) return set_err(MPDATA_EINVAL, "%s: null %s", what, !tkh ? "tkh" : "cz");
+  if (p->inner)
+    return set_err(MPDATA_EUNSUPPORTED, "%s on a windowed plan (nz = %d > 238): the backward sweep needs g of every cell of the "
+                                        "windows below, a second pass would have to park it; not built yet", what, p->nz);
+  return plan_state(what, p, eb);
+}
+int mpdata_plan_vdiffuse_device(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cz, const void* sb, const void* st,
+                                int first_tracer, int ntracers) {
+  const int rc = plan_vdiffuse_check("mpdata_plan_vdiffuse_device", p, sl0, n, tkh, cz, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_vdiffuse(p, sl0, n, tkh, cz, sb, st, first_tracer, ntracers);
+}
+static int plan_vdiffuse_host(mpdata_plan* p, int64_t sl0, int64_t n, const void* tkh, const void* cz, const void* sb, const void* st,
+                              int eb) {
+  int rc = plan_vdiffuse_check("mpdata_plan_vdiffuse", p, sl0, n, tkh, cz, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb, xb = (size_t)n * p->nx * eb;
+  HostArr a[4] = {{tkh, kb * (p->nx + 2), false}, {cz, kb, false}, {sb, xb, false}, {st, xb, false}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_vdiffuse(p, sl0, n, a[0].dev, a[1].dev, a[2].dev, a[3].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_vdiffuse(mpdata_plan* p, int64_t sl0, int64_t n, const double* tkh, const double* cz, const double* sb,
+                         const double* st) {
+  return plan_vdiffuse_host(p, sl0, n, tkh, cz, sb, st, 8);
+}
+int mpdata_plan_vdiffuse_f32(mpdata_plan* p, int64_t sl0, int64_t n, const float* tkh, const float* cz, const float* sb, const float* st) {
+  return plan_vdiffuse_host(p, sl0, n, tkh, cz, sb, st, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call).  g of every cell of the block
+// goes through a scratch array of the call's own, which is freed when the work is done: the call returns after it.
+static int vdiffuse_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, const void* rho, const void* adz,
+                          const void* tkh, const void* cz, const void* sb, const void* st, void* stream, int eb) {
+  int rc = array_sizes("mpdata_vdiffuse_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block("mpdata_vdiffuse_device", ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "mpdata_vdiffuse_device: null %s", !f ? "f" : !rho ? "rho" : "adz");
+  if (!tkh || !cz) return set_err(MPDATA_EINVAL, "mpdata_vdiffuse_device: null %s", !tkh ? "tkh" : "cz");
+  void* scratch = nullptr;
+  HIP_TRY(hipMalloc(&scratch, (size_t)n * nx * (nz - 1) * eb));
+  return scratch_done(scratch, stream, mpdata_vdiffuse_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tkh, cz, sb, st, scratch,
+                                                           (hipStream_t)stream));
+}
+int mpdata_vdiffuse_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                           const double* adz, const double* tkh, const double* cz, const double* sb, const double* st, void* stream) {
+  return vdiffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cz, sb, st, stream, 8);
+}
+int mpdata_vdiffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                               const float* adz, const float* tkh, const float* cz, const float* sb, const float* st, void* stream) {
+  return vdiffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cz, sb, st, stream, 4);
 }
 
 }  // extern "C"

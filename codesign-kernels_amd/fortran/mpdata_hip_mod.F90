@@ -76,6 +76,10 @@ module mpdata_hip_mod
   ! only, one binding for both precisions -- it carries no reals of its own; it stands in the second interface block, next
   ! to 3p's and 3q's; mpdata_plan_relax[_f32] and mpdata_relax[_f32]_device have no Fortran interface yet
   public :: mpdata_plan_relax_device_c
+  ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
+  ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
+  ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
+  public :: mpdata_plan_vdiffuse_device_c
   ! the C entry points that carry reals exist per precision (include/mpdata_hip.h sections 1-3
   ! and 6); `make single=1` (-DMPDATA_SINGLE) binds the fp32 ones, rp = c_float
 #ifdef MPDATA_SINGLE
@@ -502,6 +506,17 @@ module mpdata_hip_mod
       type(c_ptr), value :: plan
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: lo, di, up
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! ---- implicit vertical diffusion of f with a per-cell diffusivity in place (include/mpdata_hip.h section 3s):
+    ! tkh(n, 0:nx+1, nzm) and cz(n, nzm) as 3l takes them, sb, st(n, nx) (c_null_ptr: zero flux); device arrays of the
+    ! plan's precision, asynchronous on the plan's stream; windowed plans are refused
+    integer(c_int) function mpdata_plan_vdiffuse_device_c(plan, sl0, n, tkh, cz, sb, st, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_vdiffuse_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: tkh, cz, sb, st
       integer(c_int), value :: first_tracer, ntracers
     end function
   end interface

@@ -1058,6 +1058,106 @@ int mpdata_relax_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0
 int mpdata_relax_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* c,
                             const float* target, float* mean, void* stream);
 
+/* ---- 3s. Implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (the implicit half
+ * of 3l: SAM's eddy diffusivity tkh differs in every cell, large in clouds and near zero beside them, so 3o, whose matrix is
+ * one per instance, cannot take it, and 3l, which can, is explicit and bound by cz * tkh <= 1/2 on thin layers).  The call
+ * takes the SAME tkh array 3l takes and the same cz, forms the tridiagonal matrix of every column from them and solves it
+ * where f lies: mpdata_plan_diffuse_device with cz = 0 followed by this call is an x-explicit, z-implicit diffusion step
+ * without f leaving the plan.  This section is the specification; the reference tree has no such routine.  For instance sl
+ * in [sl0, sl0 + n), tracer t in [first_tracer, first_tracer + ntracers), interior column i = 1 .. nx, nzm = nz - 1, each
+ * statement one rounded operation in the plan's precision, nothing contracted, the divide IEEE, every f on the right-hand
+ * side the value BEFORE the call:
+ *   ir(k)   = 1 / (rho(sl,k) * adz(sl,k))                        (the plan's rho, adz; as 3l)
+ *   s       = tkh(sl,i,k) + tkh(sl,i,k+1);  e(i,k) = cz(sl,k) * s     k = 1 .. nzm-1     (the product inside 3l's Fz)
+ *   e(i,0)  = e(i,nzm) = +0
+ *   a(k)    = e(i,k-1) * ir(k);   c(k) = e(i,k) * ir(k);   t = 1 + a(k);   di(k) = t + c(k)
+ *   r(k)    = f(i,k),  except  r(1) = f(i,1) + sb(sl,i) * ir(1)   and   r(nzm) = f(i,nzm) - st(sl,i) * ir(nzm)
+ *             (a NULL sb / st skips its statement; nzm = 1: first the sb statement, then st on its result)
+ *   forward:  p = 1 / di(1);  g(1) = c(1) * p;  y(1) = r(1) * p
+ *             k = 2 .. nzm:  m = a(k) * g(k-1);  d = di(k) - m;  p = 1 / d;  g(k) = c(k) * p
+ *                            q = a(k) * y(k-1);  v = r(k) + q;   y(k) = v * p
+ *   backward: x(nzm) = y(nzm);   k = nzm-1 .. 1:  m = g(k) * x(k+1);  x(k) = y(k) + m
+ *   f(i,k) = x(k)
+ * This is backward Euler of 3l's vertical part, x - f = -(Fz(k) - Fz(k-1)) * ir(k) with Fz taken from x, solved by the
+ * Thomas recurrence without PIVOTING.  The matrix is diagonally dominant for every cz, tkh >= 0 (row sums 1, non-positive
+ * off-diagonals: the discrete maximum principle holds in exact arithmetic).  The library looks at no sign.
+ * All arrays are of the plan's precision, reference layout, instance index fastest, leading dimension n (the block's first
+ * instance at index 0), tightly packed:
+ *   tkh   (n, 0:nx+1, nzm)     3l's array as it is, shared by the tracers; columns 0 and nx+1 are never read
+ *   cz    (n, nzm)             3l's meaning and SAM folding, 0.5 dtn grdf_z(k) / dz^2 * rhow(k+1) / adzw(k+1), the 0.5 that
+ *                              of the mean (tkh(k) + tkh(k+1)) / 2 and dtn the FULL step of the implicit solve: a caller
+ *                              that sub-cycles 3l (dtn / ncycle, to keep cz * tkh <= 1/2) does not apply the factor of
+ *                              its explicit sub-step here; cz(:, nzm) is never read
+ *   sb,st (n, nx)              the scaled surface and top fluxes, 3l's sign convention; either may be NULL
+ * Relation to 3o: where tkh does not depend on i the result is, bit for bit, mpdata_plan_vsolve_device with lo = -a, di,
+ * up = -c -- negation is exact, and the statements above are 3o's with the signs folded (m = lo * g(k-1) = a * g there as here,
+ * r = f - lo * y = f + a * y, x = y - g3o * x = y + g * x).
+ * Identity: tkh = 0 (or cz = 0) with NULL sb, st keeps every bit of f, except that a -0.0 may come back as +0.0: a = c = +0,
+ * di = 1, p = 1, g = +0, so q = +0 * y(k-1) and m = +0 * x(k+1) are zeros whose sign is that of the neighbour, and
+ * -0.0 + +0.0 = +0.0.  (sb or st given as arrays of +0 do the same to level 1 and nzm: f + +0.0.)
+ * Contract: NaN, infinities and a zero pivot are outside the contract.  EXACT and FAST plans give the same bits.
+ * Towards the rest of a plan:
+ *   halo marks   only interior columns are read or written.  No wrap is launched before the call, because nothing couples
+ *     in x.  GIVEN plans: halos keep every bit.  PERIODIC plans: the halo marks of the range are cleared afterwards, so the
+ *     next run or read-back hands out wrapped halos of the new field.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 whenever the block holds it.
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded; padding slots, neighbours in a group,
+ *     instances and tracers outside the ranges, flux, u, w, rho, rhow, adz, the held-velocity flags, the boundary mode and
+ *     the timing pair keep every bit.  The call is outside the run's event pair; the plan need not hold velocities.
+ *   windowed plans (3e, nz > 238): MPDATA_EUNSUPPORTED.  The backward sweep needs g of every cell of the windows below,
+ *     so a second pass would have to park g in device memory; 3l, the other half of the pair, refuses such plans too.
+ *     The named follow-up, not built yet.
+ * No zflux output: take the tendency from mpdata_plan_level_stats_device before and after, as 3o says.
+ * Kernels of their own on every kind of plan (mpdata_vdiffuse.hip), not fused into the run.  A small kernel in front forms
+ * ir once per call (n nzm reals in the plan's diffusion buffer of 3l).  Wave-major plans: the geometry of 3o -- a
+ * workgroup stages the column slots of 16 adjacent 8-byte elements of the instance axis (fewer where the levels would not
+ * fit) and a batch of columns through LDS, and beside them the rows of tkh of those instances and columns, read where they
+ * lie as 3n reads wp, and cz and ir per (element, level); a lane per (instance element, column) sweeps up and down in LDS in
+ * place, g(k) overwriting tkh(k) once e(k) is formed, so a cell takes two LDS elements and a batch is 4 columns at 27
+ * levels where 3o's is 8; the waves store LDS back to f as the same linear streams.  Every global load precedes a barrier
+ * and every global store follows the sweeps' barrier; workgroups own disjoint elements: the in-place update is race-free
+ * by construction.  The tracers of a call are workgroups of one launch, each forming the factors again (the form that
+ * keeps them in LDS across the tracers was not built: docs/EXPERIMENTS.md AC).  Reference-layout plans and the array forms:
+ * one thread per instance and column sweeps its column in place, tracer after tracer, g in a scratch array (n nx nzm reals:
+ * the plan's diffusion buffer; an allocation of the call's own in the array forms).
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range, a null tkh or cz; in the array forms bad
+ * sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null f, rho or adz, then a null tkh or cz.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3r (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0); a
+ * windowed plan.  MPDATA_ESTATE: a host form of the other precision; a plan never filled.  mpdata_last_error names the
+ * argument.
+ * Time on the MI355X (docs/EXPERIMENTS.md AC, tools/vdiffuse_bench.py, profiles/vdiffuse_bench.json), 65536 x 32 x 28, one tracer,
+ * cold: 0.515 ms fp64, 0.297 ms fp32 (the ir kernel included) -- 2.6 / 2.3 TB/s of the algorithmic bytes (the interior of f read
+ * once and written once, the interior of tkh read once: 3 nx nzm ncrms reals, 1.36 GB fp64); three batches differ by 2.1 % at
+ * most.  Against the parent's calls in the same run: 1.22 x / 1.27 x mpdata_plan_export_device + mpdata_plan_import_device of
+ * f alone (the old route without the caller's kernel), 1.97 x / 1.79 x mpdata_plan_vsolve_device (the same sweep, no per-cell
+ * field, no divide in the hot kernel), 1.65 x / 1.83 x mpdata_plan_sediment_device (the same algorithmic bytes), 1.03 x /
+ * 1.17 x mpdata_plan_diffuse_device (the full 3l).  25 tracers: 11.73 / 6.50 ms, 1.14 x / 1.25 x the export + import.  A block of
+ * 64 instances: 0.016 ms.  4096 x 32 x 238: 1.51 / 1.01 ms, 4.8 x / 6.2 x the export + import (4 of 256 lanes sweep there).
+ * Said plainly: the call does NOT beat the export + import of f at any shape measured.  It is bound by the sweep -- one wave
+ * of four carries a dependent chain with an IEEE divide per level, 64 of 256 lanes at work -- not by its bytes, which
+ * sediment moves in 0.61 of the time.  What it saves is the caller's tridiagonal kernel behind that export, the sub-cycling
+ * of 3l on thin layers and the host-side bookkeeping.  A 48 KiB and a 64 KiB LDS budget of the kernel's own
+ * were timed against the 40 KiB kept: 8 % slower at 28 levels. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_vdiffuse_device(mpdata_plan* plan, int64_t sl0, int64_t n, const void* tkh, const void* cz, const void* sb,
+                                const void* st, int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3r host forms) */
+int mpdata_plan_vdiffuse(mpdata_plan* plan, int64_t sl0, int64_t n, const double* tkh, const double* cz, const double* sb,
+                         const double* st);
+int mpdata_plan_vdiffuse_f32(mpdata_plan* plan, int64_t sl0, int64_t n, const float* tkh, const float* cz, const float* sb,
+                             const float* st);
+/* the same on instances [sl0, sl0+n) of reference-layout DEVICE arrays f(ncrms,-2:nx+3,1,nzm[,ntracers]), rho(ncrms,nzm),
+ * adz(ncrms,nzm) (leading dimension ncrms); tkh, cz, sb, st as above (leading dimension n).  Enqueued on `stream`; the call
+ * allocates its scratch array and returns when the work is done and the scratch is freed. */
+int mpdata_vdiffuse_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, const double* rho,
+                           const double* adz, const double* tkh, const double* cz, const double* sb, const double* st,
+                           void* stream);
+int mpdata_vdiffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
+                               const float* adz, const float* tkh, const float* cz, const float* sb, const float* st,
+                               void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
