@@ -26,6 +26,7 @@ LAYOUT_REFERENCE, LAYOUT_WAVEMAJOR = 0, 1
 BOUNDARY_GIVEN, BOUNDARY_PERIODIC = 0, 1   # MPDATA_BOUNDARY_* (include/mpdata_hip.h section 3a)
 LEVEL_ADD, LEVEL_ADD_CLIP = 0, 1           # MPDATA_LEVEL_ADD* (include/mpdata_hip.h section 3i)
 CELL_ADD, CELL_ADD_CLIP = 0, 1             # MPDATA_CELL_ADD* (include/mpdata_hip.h section 3p)
+CONVERT_LIMIT = 1                          # MPDATA_CONVERT_LIMIT (include/mpdata_hip.h section 3t)
 
 _lib = None
 
@@ -196,6 +197,14 @@ def lib():
         for name in ("mpdata_vdiffuse_device", "mpdata_vdiffuse_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64] + [dp] * 7 + [vp]
+        L.mpdata_plan_convert_device.restype = ci
+        L.mpdata_plan_convert_device.argtypes = [vp, i64, i64, ci, ci, vp, vp, vp, ci, vp]
+        for name in ("mpdata_plan_convert", "mpdata_plan_convert_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, ci, dp, dp, dp, ci, dp]
+        for name in ("mpdata_convert_device", "mpdata_convert_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, dp, dp, dp, ci, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1049,6 +1058,29 @@ class Plan:
                 for name, a, tr, out in (("c", c, False, False), ("target", target, True, False), ("mean", mean, True, True))]
         _check(getattr(lib(), "mpdata_plan_relax" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def convert(self, src, dst, r, q0=None, y=None, mode=0, dsum=None, sl0=0, n=None):
+        """First-order conversion from tracer src to tracer dst in place (include/mpdata_hip.h 3t) on the interior columns
+        of instances [sl0, sl0+n) (default: the rest of the plan from sl0): d = r * max(f_src - q0, 0), with mode
+        CONVERT_LIMIT capped from above by max(f_src, 0); f_src -= d, f_dst += y * d; levels with r == 0 keep every bit
+        of both tracers; on the plan's stream (mpdata_plan_convert_device).  Reference-layout DEVICE tensors of the plan's
+        precision, shapes convert_shapes(n, nx, nz): r (nzm, n); q0, y (nzm, n) or None (no threshold, yield 1); dsum
+        (nzm, n) or None (skipped), d summed over the interior columns.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        sh = convert_shapes(n, self.dims[1], self.dims[2])
+        ptrs = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("r", r), ("q0", q0), ("y", y), ("dsum", dsum))}
+        _check(lib().mpdata_plan_convert_device(self._p, int(sl0), n, int(src), int(dst), ptrs["r"], ptrs["q0"], ptrs["y"], int(mode),
+                                                ptrs["dsum"]))
+
+    def convert_host(self, src, dst, r, q0=None, y=None, mode=0, dsum=None, sl0=0, n=None):
+        """The same from HOST arrays (numpy, Fortran order): r (n, nzm), q0, y (n, nzm) or None, dsum (n, nzm) or None
+        (written), synchronous (mpdata_plan_convert[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        ptrs = {name: None if a is None else self._block_host(a, name, (n, nzm), False, out)
+                for name, a, out in (("r", r, False), ("q0", q0, False), ("y", y, False), ("dsum", dsum, True))}
+        _check(getattr(lib(), "mpdata_plan_convert" + self._sfx)(self._p, int(sl0), n, int(src), int(dst), ptrs["r"], ptrs["q0"],
+                                                                 ptrs["y"], int(mode), ptrs["dsum"]))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1321,6 +1353,34 @@ def relax(f, c, target=None, mean=None, sl0=0, n=None, stream=None):
     ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("c", c), ("target", target), ("mean", mean))]
     fn = lib().mpdata_relax_device if f.dtype == torch.float64 else lib().mpdata_relax_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, *ptrs, _stream_handle(stream)))
+
+
+def convert_shapes(n, nx, nz):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a convert call on n instances: r, q0, y,
+    dsum (nzm, n).  (nx is taken as the other shape functions take it; no array of the call has a column axis.)"""
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {k: (nz - 1, n) for k in ("r", "q0", "y", "dsum")}
+
+
+def convert(f, src, dst, r, q0=None, y=None, mode=0, dsum=None, sl0=0, n=None, stream=None):
+    """First-order conversion from tracer src to tracer dst (include/mpdata_hip.h 3t) of instances [sl0, sl0+n) (default:
+    the rest from sl0) of a reference-layout DEVICE tensor f (ntr, nzm, nx+6, ncrms), float64 or float32, in place: d = r *
+    max(f_src - q0, 0), with mode CONVERT_LIMIT capped by max(f_src, 0); f_src -= d, f_dst += y * d on the interior columns;
+    r, q0, y, dsum of the same dtype with the shapes of convert_shapes(n, nx, nz) (q0, y, dsum may be None).  Asynchronous
+    on `stream` (mpdata_convert_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"convert: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() != 4 or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis")
+    nt, nzm, nxp6, ncrms = f.shape
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = convert_shapes(n, nxp6 - 6, nzm + 1)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("r", r), ("q0", q0), ("y", y), ("dsum", dsum))}
+    fn = lib().mpdata_convert_device if f.dtype == torch.float64 else lib().mpdata_convert_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(src), int(dst), P["r"], P["q0"], P["y"], int(mode), P["dsum"],
+              _stream_handle(stream)))
 
 
 def vsolve_shapes(n, nz):

@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3s).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_vdiffuse.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3t).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_convert.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -7,6 +7,7 @@
 #include "mpdata_cell_add.h"
 #include "mpdata_column_path.h"
 #include "mpdata_column_step.h"
+#include "mpdata_convert.h"
 #include "mpdata_courant.h"
 #include "mpdata_diffuse.h"
 #include "mpdata_level_add.h"
@@ -1218,6 +1219,101 @@ int mpdata_vdiffuse_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t 
 int mpdata_vdiffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, const float* rho,
                                const float* adz, const float* tkh, const float* cz, const float* sb, const float* st, void* stream) {
   return vdiffuse_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tkh, cz, sb, st, stream, 4);
+}
+
+// ---- 3t: first-order conversion between two tracers of f, in place: d = r * max(a - q0, 0), capped by max(a, 0) on
+// request, taken from tracer src and given (times y) to tracer dst.  Reads r, q0 and y, writes dsum, rewrites the INTERIOR
+// columns of tracers src and dst of the block's instances; every other tracer, flux, u, w, rho, rhow, adz and the boundary
+// mode are not touched and no event is recorded.
+//   halo marks  halo columns are neither read nor written, so no wrap is launched in front; afterwards a periodic plan's
+//               halos of BOTH tracers are copies of the OLD interior: their marks are cleared and the next run or
+//               read-back wraps again;
+//   seam marks  the operator is pointwise in (i, k): the call reads and writes OWNED levels only, which are right whatever
+//               the seams hold: no refresh in front; afterwards the other copies of both tracers are stale: their marks are
+//               cleared and the next run refreshes them;
+//   phantom     follows the plan's last slot inside the kernel, in both tracers (mpdata_convert.h); on a windowed plan the
+//               refresh of the inner plan follows as after a seam refresh.
+// Every kind of plan: r, q0 and y are read where they lie and f is updated in place; the diffusion buffer is not used.
+static int plan_convert(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const void* r, const void* q0, const void* y, int mode,
+                        void* dsum) {
+  const int limit = (mode & MPDATA_CONVERT_LIMIT) != 0;
+  if (plan_walked(p)) {
+    MpdataConvertJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, 0, p->ntracers);
+    b.sel = block_sel(p, sl0, n);
+    b.src = src; b.dst = dst;
+    b.r = r; b.q0 = q0; b.y = y; b.limit = limit; b.dsum = dsum;
+    HIP_TRY(mpdata_convert_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_convert_ref(p->f, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, src, dst, r, q0, y, limit, dsum, p->stream));
+  }
+  const int rc = plan_rewrote(p, sl0, n, src, 1, SEAMS | HALOS);
+  return rc ? rc : plan_rewrote(p, sl0, n, dst, 1, SEAMS | HALOS);
+}
+// the pair, r and the mode of a call, for the plan forms (ntracers of the plan) and the array forms alike
+static int convert_args(const char* what, int ntracers, int src, int dst, const void* r, int mode) {
+  if (src < 0 || src >= ntracers || dst < 0 || dst >= ntracers)
+    return set_err(MPDATA_EINVAL, "%s: tracer pair (src %d, dst %d) outside the %d tracers", what, src, dst, ntracers);
+  if (src == dst) return set_err(MPDATA_EINVAL, "%s: src == dst (%d)", what, src);
+  if (!r) return set_err(MPDATA_EINVAL, "%s: null r", what);
+  if (mode & ~MPDATA_CONVERT_LIMIT) return set_err(MPDATA_EINVAL, "%s: unknown mode bits %d", what, mode);
+  return 0;
+}
+static int plan_convert_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const void* r, int mode,
+                              int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = convert_args(what, p->ntracers, src, dst, r, mode);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_convert_device(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const void* r, const void* q0, const void* y,
+                               int mode, void* dsum) {
+  const int rc = plan_convert_check("mpdata_plan_convert_device", p, sl0, n, src, dst, r, mode, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_convert(p, sl0, n, src, dst, r, q0, y, mode, dsum);
+}
+static int plan_convert_host(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const void* r, const void* q0, const void* y,
+                             int mode, void* dsum, int eb) {
+  int rc = plan_convert_check("mpdata_plan_convert", p, sl0, n, src, dst, r, mode, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb;
+  HostArr a[4] = {{r, kb, false}, {q0, kb, false}, {y, kb, false}, {dsum, kb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_convert(p, sl0, n, src, dst, a[0].dev, a[1].dev, a[2].dev, mode, a[3].dev);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_convert(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const double* r, const double* q0, const double* y,
+                        int mode, double* dsum) {
+  return plan_convert_host(p, sl0, n, src, dst, r, q0, y, mode, dsum, 8);
+}
+int mpdata_plan_convert_f32(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const float* r, const float* q0, const float* y,
+                            int mode, float* dsum) {
+  return plan_convert_host(p, sl0, n, src, dst, r, q0, y, mode, dsum, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): in place, asynchronous
+static int convert_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, int src, int dst, const void* r,
+                         const void* q0, const void* y, int mode, void* dsum, void* stream, int eb) {
+  const char* const what = "mpdata_convert_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  rc = convert_args(what, ntracers, src, dst, r, mode);
+  if (rc) return rc;
+  HIP_TRY(mpdata_convert_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, src, dst, r, q0, y, (mode & MPDATA_CONVERT_LIMIT) != 0, dsum,
+                             (hipStream_t)stream));
+  return 0;
+}
+int mpdata_convert_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, int src, int dst,
+                          const double* r, const double* q0, const double* y, int mode, double* dsum, void* stream) {
+  return convert_array(ncrms, nx, nz, ntracers, sl0, n, f, src, dst, r, q0, y, mode, dsum, stream, 8);
+}
+int mpdata_convert_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int src, int dst,
+                              const float* r, const float* q0, const float* y, int mode, float* dsum, void* stream) {
+  return convert_array(ncrms, nx, nz, ntracers, sl0, n, f, src, dst, r, q0, y, mode, dsum, stream, 4);
 }
 
 }  // extern "C"

@@ -76,6 +76,11 @@ module mpdata_hip_mod
   ! only, one binding for both precisions -- it carries no reals of its own; it stands in the second interface block, next
   ! to 3p's and 3q's; mpdata_plan_relax[_f32] and mpdata_relax[_f32]_device have no Fortran interface yet
   public :: mpdata_plan_relax_device_c
+  ! first-order conversion between two tracers of a resident plan, in place (include/mpdata_hip.h section 3t): the device
+  ! form only, one binding for both precisions -- it carries no reals of its own; it stands in the second interface block,
+  ! behind 3r's; mpdata_plan_convert[_f32] and mpdata_convert[_f32]_device have no Fortran interface yet
+  public :: mpdata_plan_convert_device_c
+  integer(c_int), parameter, public :: MPDATA_CONVERT_LIMIT = 1
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
   ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
   ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
@@ -564,6 +569,20 @@ module mpdata_hip_mod
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: c, target, mean
       integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! ---- first-order conversion from tracer src to tracer dst in place (include/mpdata_hip.h section 3t; tracers counted
+    ! from 0): d = r * max(f_src - q0, 0), with mode MPDATA_CONVERT_LIMIT capped by max(f_src, 0); f_src = f_src - d,
+    ! f_dst = f_dst + y * d; r, q0, y, dsum(n, nzm) (q0, y, dsum c_null_ptr: absent / skipped); device arrays of the plan's
+    ! precision, asynchronous on the plan's stream; windowed plans are supported
+    integer(c_int) function mpdata_plan_convert_device_c(plan, sl0, n, src, dst, r, q0, y, mode, dsum) &
+        bind(C, name="mpdata_plan_convert_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: src, dst
+      type(c_ptr), value :: r, q0, y
+      integer(c_int), value :: mode
+      type(c_ptr), value :: dsum
     end function
   end interface
 

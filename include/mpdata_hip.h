@@ -1158,6 +1158,84 @@ int mpdata_vdiffuse_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int6
                                const float* adz, const float* tkh, const float* cz, const float* sb, const float* st,
                                void* stream);
 
+/* ---- 3t. First-order conversion between two tracers of a resident plan, in place (the one piece of a cloud model's scalar
+ * step that couples two species of the same cell: autoconversion of cloud water into rain, d = r * max(qc - qc0, 0), taken
+ * from one species and given to the other; ageing and decay chains of passive tracers; a first-order chemical loss with a
+ * yield; a phase change with its latent-heat increment on a temperature-like tracer.  Every call of 3g - 3s works on one
+ * tracer at a time; this one sees two).  This section is the specification; the reference tree has no such routine.  For one
+ * ordered pair of tracers (src, dst), every instance sl in [sl0, sl0 + n) with b = sl - sl0, every level k = 1 .. nzm,
+ * nzm = nz - 1, and every INTERIOR column i = 1 .. nx, with a = f_old(i,k,src) and c = f_old(i,k,dst), every statement
+ * below is rounded once in the plan's precision, in this association, with no contraction; comparisons are plain
+ * compare-and-select, never fmax / fmin:
+ *   r(b,k) == 0            : the level keeps every bit in BOTH tracers and is not stored; dsum(b,k) = +0
+ *   e = q0 ? a - q0(b,k) : a
+ *   e = (e > 0) ? e : +0                       (so NaN and -0 give +0)
+ *   d = r(b,k) * e
+ *   mode & MPDATA_CONVERT_LIMIT:  m = (a > 0) ? a : +0 ;  d = (d > m) ? m : d
+ *   f(i,k,src) = a - d
+ *   g = y ? y(b,k) * d : d
+ *   f(i,k,dst) = c + g
+ *   dsum(b,k): s = +0; do i = 1, nx: s = s + d(i)        (NULL: skipped)
+ * r (required), q0, y (optional inputs, NULL: absent) and dsum (optional output) are (n, nzm) arrays of the plan's
+ * precision, reference layout, instance index fastest, leading dimension n (the block's first instance at index 0), as c of
+ * 3r.  r may have either sign; LIMIT caps d from above only (with r in [0, 1] and a >= q0 >= 0 it never bites; it is for
+ * r * dt > 1, where src would go negative); a reverse conversion swaps src and dst.  Halo columns are neither read nor
+ * written.  A tracer that is neither src nor dst keeps every bit.  EXACT and FAST plans give the same bits.  With y == NULL
+ * the amount added to dst is the amount taken from src, so src + dst is conserved up to the two roundings of a - d and
+ * c + d.  No byte outside the arrays is read or written.  Afterwards the plan behaves exactly as if the interior of the two
+ * tracers had been exported, changed as above and imported again.
+ * Towards the rest of a plan:
+ *   halo marks   only interior columns are read and written.  GIVEN plans: halos keep every bit.  PERIODIC plans: no wrap
+ *     is launched; the halo marks of BOTH tracers are cleared afterwards, so the next run or read-back hands out wrapped
+ *     halos of the new fields.
+ *   windowed plans (3e, nz > 238) are supported, as in 3r: the operator is pointwise, the call reads and writes OWNED levels
+ *     only, each with r, q0 and y of the tall level it stands for, needs no seam refresh in front and clears the seam marks
+ *     of both tracers afterwards; dsum of a level is written by that level's owner.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 in both tracers whenever the block holds it and its r
+ *     is not zero on that level (on a windowed plan the phantom of the inner plan is restored behind the call, as in 3r).
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded: a -0.0 there stays; padding slots,
+ *     neighbours in a tile, instances outside the block, every other tracer, flux, u, w, rho, rhow, adz, the held-velocity
+ *     flags, the boundary mode and the timing pair keep every bit.  The call is outside the run's event pair; the plan need
+ *     not hold velocities.
+ * A kernel of its own on every kind of plan (mpdata_convert.hip), not fused into the run.  Wave-major and windowed plans: a
+ * lane owns one (instance, level) element and walks its interior column slots as TWO linear streams (the walk of 3g and 3i),
+ * 8 columns in flight on each: the src tracer and, at a signed 64-bit offset from it, the dst tracer.  r, q0 and y are in
+ * registers, dsum is lane-local in column order: no LDS, no barrier, no cross-lane traffic, and no ordering to argue -- a
+ * lane touches the columns of its own element only, in two tracers.  A wave whose elements all have r == 0 loads nothing.
+ * Reference-layout plans and the array forms: one thread per instance and level row, one loop over i, in place.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), src or dst outside [0, ntracers), src == dst, a null r, a
+ * mode bit other than MPDATA_CONVERT_LIMIT; in the array forms bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block
+ * outside the arrays, a null f, then the pair, r and the mode as above.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3s (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md AD, tools/convert_bench.py, profiles/convert_bench.json), 65536 x 32 x 28, cold: with
+ * r alone 0.417 ms fp64, 0.210 ms fp32; with q0, y and dsum 0.438 / 0.220 ms -- 4.35 and 4.14 TB/s of the algorithmic bytes (the
+ * interior of two tracers read once and written once: 4 nx nzm ncrms reals, 1.81 GB fp64).  Against existing calls in the
+ * same run, r alone / with everything: (a) 0.48 x / 0.51 x fp64 and 0.46 x / 0.49 x fp32 mpdata_plan_export_device +
+ * mpdata_plan_import_device of both tracers (the old route without the caller's kernel); (b) 0.90 x / 0.94 x and 0.89 x / 0.93 x
+ * two mpdata_plan_level_add_device calls; (c) 0.98 x / 1.02 x and 0.96 x / 1.00 x two mpdata_plan_relax_device calls to a target,
+ * which move the same bytes.  LIMIT and a negative offset (dst < src) cost nothing.  A block of 64 instances: 0.007 ms.  Tall
+ * plans, 4096 x 32 x 300 (6 windows): 0.299 / 0.318 ms fp64, 0.157 / 0.174 ms fp32, 0.41 x / 0.44 x (a) in fp64.  Said plainly: per
+ * byte the call does not reach level_add's rate (4.35 against 4.62 TB/s) and sits at relax's, whose interior-only walk it
+ * shares.  NB = 4 on both streams (8 waves per SIMD where NB = 8 has 5) was timed against it: 1.3 % to 1.6 % slower. */
+#define MPDATA_CONVERT_LIMIT 1 /* mode bit: cap d from above by max(a, 0), so that src does not change sign */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_convert_device(mpdata_plan* plan, int64_t sl0, int64_t n, int src, int dst, const void* r, const void* q0,
+                               const void* y, int mode, void* dsum);
+/* host arrays, synchronous (the plan's block staging buffer, as the 3g - 3s host forms) */
+int mpdata_plan_convert(mpdata_plan* plan, int64_t sl0, int64_t n, int src, int dst, const double* r, const double* q0,
+                        const double* y, int mode, double* dsum);
+int mpdata_plan_convert_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int src, int dst, const float* r, const float* q0,
+                            const float* y, int mode, float* dsum);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm,ntracers) (leading
+ * dimension ncrms); r, q0, y, dsum as above (leading dimension n).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_convert_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, int src, int dst,
+                          const double* r, const double* q0, const double* y, int mode, double* dsum, void* stream);
+int mpdata_convert_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int src, int dst,
+                              const float* r, const float* q0, const float* y, int mode, float* dsum, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
