@@ -27,6 +27,7 @@ BOUNDARY_GIVEN, BOUNDARY_PERIODIC = 0, 1   # MPDATA_BOUNDARY_* (include/mpdata_h
 LEVEL_ADD, LEVEL_ADD_CLIP = 0, 1           # MPDATA_LEVEL_ADD* (include/mpdata_hip.h section 3i)
 CELL_ADD, CELL_ADD_CLIP = 0, 1             # MPDATA_CELL_ADD* (include/mpdata_hip.h section 3p)
 CONVERT_LIMIT = 1                          # MPDATA_CONVERT_LIMIT (include/mpdata_hip.h section 3t)
+LEVEL_COV_RAW = 1                          # MPDATA_LEVEL_COV_RAW (include/mpdata_hip.h section 3u)
 
 _lib = None
 
@@ -205,6 +206,14 @@ def lib():
         for name in ("mpdata_convert_device", "mpdata_convert_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, dp, dp, dp, ci, dp, vp]
+        L.mpdata_plan_level_cov_device.restype = ci
+        L.mpdata_plan_level_cov_device.argtypes = [vp, i64, i64, ci, ci, vp, vp, ci, vp, vp, vp]
+        for name in ("mpdata_plan_level_cov", "mpdata_plan_level_cov_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, ci, dp, dp, ci, dp, dp, dp]
+        for name in ("mpdata_level_cov_device", "mpdata_level_cov_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, dp, dp, ci, dp, dp, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1081,6 +1090,32 @@ class Plan:
         _check(getattr(lib(), "mpdata_plan_convert" + self._sfx)(self._p, int(sl0), n, int(src), int(dst), ptrs["r"], ptrs["q0"],
                                                                  ptrs["y"], int(mode), ptrs["dsum"]))
 
+    def level_cov(self, ta, tb, cov, ma=None, mb=None, mode=0, mean_a=None, mean_b=None, sl0=0, n=None):
+        """Per-level covariance of tracers ta and tb (include/mpdata_hip.h 3u; ta == tb: the variance) over the interior
+        columns of instances [sl0, sl0+n) (default: the rest of the plan from sl0): cov = the SUM over i of (a_i - m_a) *
+        (b_i - m_b), with m the given profile ma / mb or, without one, the horizontal mean of the row (the sum of
+        level_stats over nx, one rounded divide); mode LEVEL_COV_RAW: the sum of a_i * b_i (ma, mb, mean_a, mean_b must be
+        None); on the plan's stream (mpdata_plan_level_cov_device).  Reference-layout DEVICE tensors of the plan's precision,
+        shapes level_cov_shapes(n, nx, nz), all (nzm, n): cov (written); ma, mb or None; mean_a, mean_b or None (skipped),
+        written with the means used.  Changes nothing of the plan.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        sh = level_cov_shapes(n, self.dims[1], self.dims[2])
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt())
+             for k, t in (("ma", ma), ("mb", mb), ("cov", cov), ("mean_a", mean_a), ("mean_b", mean_b))}
+        _check(lib().mpdata_plan_level_cov_device(self._p, int(sl0), n, int(ta), int(tb), P["ma"], P["mb"], int(mode), P["cov"],
+                                                  P["mean_a"], P["mean_b"]))
+
+    def level_cov_host(self, ta, tb, cov, ma=None, mb=None, mode=0, mean_a=None, mean_b=None, sl0=0, n=None):
+        """The same with HOST arrays (numpy, Fortran order), all (n, nzm): cov (written), ma, mb or None, mean_a, mean_b or
+        None (written), synchronous (mpdata_plan_level_cov[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        P = {name: None if a is None else self._block_host(a, name, (n, nzm), False, out)
+             for name, a, out in (("ma", ma, False), ("mb", mb, False), ("cov", cov, True), ("mean_a", mean_a, True),
+                                  ("mean_b", mean_b, True))}
+        _check(getattr(lib(), "mpdata_plan_level_cov" + self._sfx)(self._p, int(sl0), n, int(ta), int(tb), P["ma"], P["mb"], int(mode),
+                                                                   P["cov"], P["mean_a"], P["mean_b"]))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1381,6 +1416,36 @@ def convert(f, src, dst, r, q0=None, y=None, mode=0, dsum=None, sl0=0, n=None, s
     fn = lib().mpdata_convert_device if f.dtype == torch.float64 else lib().mpdata_convert_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(src), int(dst), P["r"], P["q0"], P["y"], int(mode), P["dsum"],
               _stream_handle(stream)))
+
+
+def level_cov_shapes(n, nx, nz):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a level_cov call on n instances: ma, mb,
+    cov, mean_a, mean_b (nzm, n).  (nx is taken as the other shape functions take it; no array of the call has a column
+    axis.)"""
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {k: (nz - 1, n) for k in ("ma", "mb", "cov", "mean_a", "mean_b")}
+
+
+def level_cov(f, ta, tb, cov, ma=None, mb=None, mode=0, mean_a=None, mean_b=None, sl0=0, n=None, stream=None):
+    """Per-level covariance of tracers ta and tb (include/mpdata_hip.h 3u) of instances [sl0, sl0+n) (default: the rest
+    from sl0) of a reference-layout DEVICE tensor f (ntr, nzm, nx+6, ncrms), float64 or float32, which is only read: cov =
+    the sum over the interior columns of (a_i - m_a) * (b_i - m_b), m = ma / mb or the horizontal mean of the row; mode
+    LEVEL_COV_RAW: the sum of a_i * b_i.  cov, ma, mb, mean_a, mean_b of the same dtype with the shapes of
+    level_cov_shapes(n, nx, nz) (all but cov may be None).  Asynchronous on `stream` (mpdata_level_cov_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"level_cov: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() != 4 or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis")
+    nt, nzm, nxp6, ncrms = f.shape
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = level_cov_shapes(n, nxp6 - 6, nzm + 1)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype)
+         for k, t in (("ma", ma), ("mb", mb), ("cov", cov), ("mean_a", mean_a), ("mean_b", mean_b))}
+    fn = lib().mpdata_level_cov_device if f.dtype == torch.float64 else lib().mpdata_level_cov_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(ta), int(tb), P["ma"], P["mb"], int(mode), P["cov"], P["mean_a"],
+              P["mean_b"], _stream_handle(stream)))
 
 
 def vsolve_shapes(n, nz):

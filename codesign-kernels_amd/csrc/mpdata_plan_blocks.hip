@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3t).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_convert.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3u).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_level_cov.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -11,6 +11,7 @@
 #include "mpdata_courant.h"
 #include "mpdata_diffuse.h"
 #include "mpdata_level_add.h"
+#include "mpdata_level_cov.h"
 #include "mpdata_plan_priv.h"
 #include "mpdata_relax.h"
 #include "mpdata_scale_uw.h"
@@ -1314,6 +1315,95 @@ int mpdata_convert_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t s
 int mpdata_convert_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int src, int dst,
                               const float* r, const float* q0, const float* y, int mode, float* dsum, void* stream) {
   return convert_array(ncrms, nx, nz, ntracers, sl0, n, f, src, dst, r, q0, y, mode, dsum, stream, 4);
+}
+
+// ---- 3u: per-level covariance of two tracers of f: the sum over the interior columns of (a - m_a) * (b - m_b), m the given
+// profile or the horizontal mean of the row, or of a * b (RAW).  Reads f, ma and mb, writes cov, mean_a and mean_b: as 3g,
+// no flag of the plan is touched (the halo and seam marks stay -- halo columns are not read, owned levels are right
+// whatever the seams hold), no event is recorded, and a windowed plan's inner plan is read where it lies.
+static int plan_level_cov(mpdata_plan* p, int64_t sl0, int64_t n, int ta, int tb, const void* ma, const void* mb, int mode, void* cov,
+                          void* mean_a, void* mean_b) {
+  const int raw = (mode & MPDATA_LEVEL_COV_RAW) != 0;
+  if (plan_walked(p)) {
+    MpdataLevelCovJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, 0, p->ntracers);
+    b.sel = block_sel(p, sl0, n);
+    b.ta = ta; b.tb = tb;
+    b.ma = ma; b.mb = mb; b.raw = raw; b.cov = cov; b.mean_a = mean_a; b.mean_b = mean_b;
+    HIP_TRY(mpdata_level_cov_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_level_cov_ref(p->f, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, ta, tb, ma, mb, raw, cov, mean_a, mean_b,
+                                 p->stream));
+  }
+  return 0;
+}
+// the pair, the mode and the arrays of a call, for the plan forms (ntracers of the plan) and the array forms alike
+static int level_cov_args(const char* what, int ntracers, int ta, int tb, const void* ma, const void* mb, int mode, const void* cov,
+                          const void* mean_a, const void* mean_b) {
+  if (ta < 0 || ta >= ntracers || tb < 0 || tb >= ntracers)
+    return set_err(MPDATA_EINVAL, "%s: tracer pair (ta %d, tb %d) outside the %d tracers", what, ta, tb, ntracers);
+  if (mode & ~MPDATA_LEVEL_COV_RAW) return set_err(MPDATA_EINVAL, "%s: unknown mode bits %d", what, mode);
+  if ((mode & MPDATA_LEVEL_COV_RAW) && (ma || mb || mean_a || mean_b))
+    return set_err(MPDATA_EINVAL, "%s: MPDATA_LEVEL_COV_RAW with a non-null %s (RAW subtracts no mean)", what,
+                   ma ? "ma" : mb ? "mb" : mean_a ? "mean_a" : "mean_b");
+  if (!cov) return set_err(MPDATA_EINVAL, "%s: null cov", what);
+  return 0;
+}
+static int plan_level_cov_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int ta, int tb, const void* ma,
+                                const void* mb, int mode, const void* cov, const void* mean_a, const void* mean_b, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = level_cov_args(what, p->ntracers, ta, tb, ma, mb, mode, cov, mean_a, mean_b);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_level_cov_device(mpdata_plan* p, int64_t sl0, int64_t n, int ta, int tb, const void* ma, const void* mb, int mode,
+                                 void* cov, void* mean_a, void* mean_b) {
+  const int rc = plan_level_cov_check("mpdata_plan_level_cov_device", p, sl0, n, ta, tb, ma, mb, mode, cov, mean_a, mean_b, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_level_cov(p, sl0, n, ta, tb, ma, mb, mode, cov, mean_a, mean_b);
+}
+static int plan_level_cov_host(mpdata_plan* p, int64_t sl0, int64_t n, int ta, int tb, const void* ma, const void* mb, int mode,
+                               void* cov, void* mean_a, void* mean_b, int eb) {
+  int rc = plan_level_cov_check("mpdata_plan_level_cov", p, sl0, n, ta, tb, ma, mb, mode, cov, mean_a, mean_b, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb;
+  HostArr a[5] = {{ma, kb, false}, {mb, kb, false}, {cov, kb, true}, {mean_a, kb, true}, {mean_b, kb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_level_cov(p, sl0, n, ta, tb, a[0].dev, a[1].dev, mode, a[2].dev, a[3].dev, a[4].dev);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_level_cov(mpdata_plan* p, int64_t sl0, int64_t n, int ta, int tb, const double* ma, const double* mb, int mode,
+                          double* cov, double* mean_a, double* mean_b) {
+  return plan_level_cov_host(p, sl0, n, ta, tb, ma, mb, mode, cov, mean_a, mean_b, 8);
+}
+int mpdata_plan_level_cov_f32(mpdata_plan* p, int64_t sl0, int64_t n, int ta, int tb, const float* ma, const float* mb, int mode,
+                              float* cov, float* mean_a, float* mean_b) {
+  return plan_level_cov_host(p, sl0, n, ta, tb, ma, mb, mode, cov, mean_a, mean_b, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): asynchronous
+static int level_cov_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const void* f, int ta, int tb,
+                           const void* ma, const void* mb, int mode, void* cov, void* mean_a, void* mean_b, void* stream, int eb) {
+  const char* const what = "mpdata_level_cov_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  rc = level_cov_args(what, ntracers, ta, tb, ma, mb, mode, cov, mean_a, mean_b);
+  if (rc) return rc;
+  HIP_TRY(mpdata_level_cov_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, ta, tb, ma, mb, (mode & MPDATA_LEVEL_COV_RAW) != 0, cov, mean_a,
+                               mean_b, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_level_cov_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, int ta, int tb,
+                            const double* ma, const double* mb, int mode, double* cov, double* mean_a, double* mean_b, void* stream) {
+  return level_cov_array(ncrms, nx, nz, ntracers, sl0, n, f, ta, tb, ma, mb, mode, cov, mean_a, mean_b, stream, 8);
+}
+int mpdata_level_cov_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int ta, int tb,
+                                const float* ma, const float* mb, int mode, float* cov, float* mean_a, float* mean_b, void* stream) {
+  return level_cov_array(ncrms, nx, nz, ntracers, sl0, n, f, ta, tb, ma, mb, mode, cov, mean_a, mean_b, stream, 4);
 }
 
 }  // extern "C"

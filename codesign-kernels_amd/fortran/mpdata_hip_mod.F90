@@ -81,6 +81,11 @@ module mpdata_hip_mod
   ! behind 3r's; mpdata_plan_convert[_f32] and mpdata_convert[_f32]_device have no Fortran interface yet
   public :: mpdata_plan_convert_device_c
   integer(c_int), parameter, public :: MPDATA_CONVERT_LIMIT = 1
+  ! per-level covariance of two tracers of a resident plan (include/mpdata_hip.h section 3u): the device form only, one
+  ! binding for both precisions -- it carries no reals of its own; it stands in the second interface block, behind 3t's;
+  ! mpdata_plan_level_cov[_f32] and mpdata_level_cov[_f32]_device have no Fortran interface yet
+  public :: mpdata_plan_level_cov_device_c
+  integer(c_int), parameter, public :: MPDATA_LEVEL_COV_RAW = 1
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
   ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
   ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
@@ -583,6 +588,21 @@ module mpdata_hip_mod
       type(c_ptr), value :: r, q0, y
       integer(c_int), value :: mode
       type(c_ptr), value :: dsum
+    end function
+    ! ---- per-level covariance of tracers ta and tb (include/mpdata_hip.h section 3u; tracers counted from 0; ta == tb: the
+    ! variance): cov(n, nzm) = the SUM over the interior columns of (a - m_a) * (b - m_b), m = ma / mb(n, nzm) or
+    ! (c_null_ptr) the horizontal mean of the row; mode MPDATA_LEVEL_COV_RAW: the sum of a * b, and ma, mb, mean_a, mean_b
+    ! must be c_null_ptr; mean_a, mean_b(n, nzm) (c_null_ptr: skipped) take the means used; device arrays of the plan's
+    ! precision, asynchronous on the plan's stream; nothing of the plan changes; windowed plans are supported
+    integer(c_int) function mpdata_plan_level_cov_device_c(plan, sl0, n, ta, tb, ma, mb, mode, cov, mean_a, mean_b) &
+        bind(C, name="mpdata_plan_level_cov_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: ta, tb
+      type(c_ptr), value :: ma, mb
+      integer(c_int), value :: mode
+      type(c_ptr), value :: cov, mean_a, mean_b
     end function
   end interface
 

@@ -1236,6 +1236,88 @@ int mpdata_convert_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t s
 int mpdata_convert_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int src, int dst,
                               const float* r, const float* q0, const float* y, int mode, float* dsum, void* stream);
 
+/* ---- 3u. Per-level covariance of two tracers of a resident plan (the read side of a cloud model's second moments: the
+ * horizontal variance of a tracer per level, the covariance of two, the amplitude that variance transport in a multiscale
+ * modelling framework hands to the global model, SAM-style statistics such as QT2 and TL2.  3g gives first moments and
+ * extrema, 3k column integrals; everything that needs a product of deviations forced f out of the plan.  The feedback of
+ * variance transport -- scaling each cell's deviation from the level mean -- is mpdata_plan_relax_device (3r) in mean mode
+ * with c = 1 - factor: only the diagnosis was missing).  This section is the specification; the reference tree has no such
+ * routine.  For one pair of tracers (ta, tb) -- ta == tb is allowed and gives the variance --, every instance sl in
+ * [sl0, sl0 + n) with b = sl - sl0, every level k = 1 .. nzm, nzm = nz - 1, over the INTERIOR columns i = 1 .. nx, with
+ * a_i = f(sl,i,k,ta) and b_i = f(sl,i,k,tb), every statement below is rounded ONCE in the plan's precision, in this
+ * association, with nothing contracted, so EXACT and FAST plans give the same bits:
+ *   mode & MPDATA_LEVEL_COV_RAW :  da_i = a_i ;  db_i = b_i                  (no subtraction at all)
+ *   otherwise:
+ *       m_a = ma ? ma(b,k) : ( s = +0; do i = 1, nx: s = s + a_i ;  s / nx )   (the sum of 3g, ONE IEEE divide, as 3r)
+ *       m_b = mb ? mb(b,k) : the same from b_i
+ *       mean_a(b,k) = m_a ;  mean_b(b,k) = m_b                               (NULL: skipped; written in both cases)
+ *       da_i = a_i - m_a ;  db_i = b_i - m_b
+ *   c = +0;  do i = 1, nx:  p = da_i * db_i ;  c = c + p
+ *   cov(b,k) = c
+ * cov is the SUM over the columns, not divided by nx and not by nx - 1: the caller normalises, as with sum of 3g, so no
+ * rounding is hidden.  The two-pass form is the definition; the one-pass form  sum(a b) - sum(a) sum(b) / nx  is not, and
+ * differs from it in bits in most outputs.  The divide is the correctly rounded IEEE one in both precisions, not a product
+ * with a rounded reciprocal (on random fields more than a fifth, a tenth and a thirtieth of the outputs differ at nx = 3,
+ * 11 and 17).  NaN and infinities are outside the contract.  ma, mb (optional inputs), cov (required output), mean_a, mean_b (optional outputs)
+ * are (n, nzm) arrays of the plan's precision, reference layout, instance index fastest, leading dimension n (the block's
+ * first instance at index 0), as c of 3r.  With ta == tb, ma and mb may still differ; the definition above covers it.
+ * Towards the rest of a plan, exactly as 3g: halo columns are never read, so a PERIODIC plan needs no wrap; nothing of the
+ * plan's state changes -- filled, have_u, have_w, the halo marks, the seam marks, the timing pair and last_kernel_ms --;
+ * the call is outside the run's event pair; the plan need not hold velocities.
+ *   windowed plans (3e, nz > 238) are supported: only OWNED levels are read, each is written to the tall level it stands
+ *     for and uses ma / mb of that tall level, and no seam refresh is launched in front.
+ *   no output is reached by the phantom half of an odd fp32 plan (3f), the partner of a split fp32 pair or a padding slot,
+ *     and no byte outside the five arrays is touched.
+ * A kernel of its own on every kind of plan (mpdata_level_cov.hip), not fused into the run.  Wave-major and windowed plans:
+ * a lane owns one (instance, level) element and walks its interior column slots as two read-only linear streams (the walk
+ * of 3t), 8 columns in flight on each: tracer ta and, at a signed 64-bit offset from it, tracer tb; with ta == tb ONE
+ * stream.  No LDS, no barrier, no cross-lane traffic.  Three forms with the same bits: ONE-PASS (RAW, or both profiles
+ * given), KEPT (a mean is formed and nx <= 32: the columns stay in registers between the two passes, so f is read once) and
+ * RE-READ (a mean is formed, nx > 32: the summing walk of 3g, the divides, then the accumulating walk).  A wave none of
+ * whose elements is in the block, or owned in a window, loads nothing.  Reference-layout plans and the array forms: one
+ * thread per instance and level row, loops over i, 64-bit offsets.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), ta or tb outside [0, ntracers), a mode bit other than
+ * MPDATA_LEVEL_COV_RAW, RAW together with a non-null ma, mb, mean_a or mean_b, a null cov; in the array forms bad sizes
+ * (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null f, then the same list as above.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3t (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md AE, tools/level_cov_bench.py, profiles/level_cov_bench.json), 65536 x 32 x 28,
+ * cold, ta != tb, fp64 / fp32: both means formed (the kept form) 0.174 / 0.092 ms -- 5.2 / 5.0 TB/s of the algorithmic bytes
+ * (the interior of two tracers read once: 2 nx nzm ncrms reals, 0.91 GB fp64; one tracer for ta == tb) --, with mean_a and
+ * mean_b written 0.200 / 0.108, RAW 0.180 / 0.089, both profiles given 0.187 / 0.098; ta == tb: 0.093 / 0.047 formed, 0.096 /
+ * 0.051 RAW.  Against existing calls in the same run, means formed: (a) 0.42 x / 0.42 x mpdata_plan_export_device of the two
+ * tracers (0.418 / 0.219 ms: the old route without the caller's kernel); (b) 0.91 x / 0.91 x two mpdata_plan_level_stats_device
+ * calls (0.190 / 0.100 ms), which read the same bytes once without the products.  A negative offset (tb < ta) costs nothing.
+ * A block of 64 instances: 0.006 ms.  Tall plans, 4096 x 32 x 300 (6 windows): 0.139 / 0.080 ms formed, 0.42 x / 0.28 x (a),
+ * 0.93 x / 0.86 x (b).  The kept form against the re-read form at nx = 32 (the same library with the kept limits at 0, same
+ * session): two tracers 0.174 against 0.255 ms fp64 and 0.092 against 0.137 fp32 (146 and 206 VGPRs, 3 and 2 waves per SIMD,
+ * no scratch, no spill), one tracer 0.093 against 0.128 and 0.047 against 0.070 (82 VGPRs): kept wins by 27 % to 33 %, far
+ * beyond the 3 % run-to-run spread of 3r, at 28 and at 300 levels, so both kept forms stay at nx <= 32.  Said plainly: above
+ * nx = 32 the re-read form is what runs, and it LOSES to two level_stats calls (1.33 x fp64, 1.38 x fp32; still 0.63 x / 0.65 x
+ * the export): its second read costs a third of a first read, so the caches serve part of it, not all.  Writing the two
+ * means costs 15 % -- the outputs of a wave lie a leading dimension apart, as those of 3g -- and the given-profile call is
+ * 7 % to 10 % slower than forming the means in the kept form, which has all its loads in flight at once. */
+#define MPDATA_LEVEL_COV_RAW 1 /* mode bit: the sum of a_i * b_i, no mean subtracted; ma, mb, mean_a, mean_b must be NULL */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_level_cov_device(mpdata_plan* plan, int64_t sl0, int64_t n, int ta, int tb, const void* ma, const void* mb,
+                                 int mode, void* cov, void* mean_a, void* mean_b);
+/* host arrays, synchronous (the plan's block staging buffer, as the 3g - 3t host forms) */
+int mpdata_plan_level_cov(mpdata_plan* plan, int64_t sl0, int64_t n, int ta, int tb, const double* ma, const double* mb,
+                          int mode, double* cov, double* mean_a, double* mean_b);
+int mpdata_plan_level_cov_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int ta, int tb, const float* ma, const float* mb,
+                              int mode, float* cov, float* mean_a, float* mean_b);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm,ntracers) (leading
+ * dimension ncrms), which is only read; ma, mb, cov, mean_a, mean_b as above (leading dimension n).  Asynchronous on
+ * `stream`; 64-bit offsets. */
+int mpdata_level_cov_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, int ta, int tb,
+                            const double* ma, const double* mb, int mode, double* cov, double* mean_a, double* mean_b,
+                            void* stream);
+int mpdata_level_cov_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int ta,
+                                int tb, const float* ma, const float* mb, int mode, float* cov, float* mean_a, float* mean_b,
+                                void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
