@@ -214,6 +214,14 @@ def lib():
         for name in ("mpdata_level_cov_device", "mpdata_level_cov_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, dp, dp, ci, dp, dp, dp, vp]
+        L.mpdata_plan_level_cond_device.restype = ci
+        L.mpdata_plan_level_cond_device.argtypes = [vp, i64, i64, ci, vp, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_level_cond", "mpdata_plan_level_cond_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, dp, dp, dp, dp]
+        for name in ("mpdata_level_cond_device", "mpdata_level_cond_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, dp, dp, dp, dp, ci, ci, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1116,6 +1124,31 @@ class Plan:
         _check(getattr(lib(), "mpdata_plan_level_cov" + self._sfx)(self._p, int(sl0), n, int(ta), int(tb), P["ma"], P["mb"], int(mode),
                                                                    P["cov"], P["mean_a"], P["mean_b"]))
 
+    def level_cond(self, tc, lo=None, hi=None, cnt=None, csum=None, first_tracer=0, sl0=0, n=None):
+        """Per-level conditional counts and sums (include/mpdata_hip.h 3v) over the interior columns of instances [sl0, sl0+n)
+        (default: the rest of the plan from sl0): a column is IN where lo < f(tc) <= hi (a bound that is None does not
+        bind; one of the two is needed); cnt = the number of columns that are in, csum[j] = the SUM of tracer first_tracer
+        + j over exactly those columns (the caller divides); on the plan's stream (mpdata_plan_level_cond_device).
+        Reference-layout DEVICE tensors of the plan's precision, shapes level_cond_shapes(n, nx, nz, ntr): lo, hi, cnt
+        (nzm, n), csum (ntr, nzm, n) with ntr its leading axis; cnt or csum may be None (skipped), not both.  Changes
+        nothing of the plan.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        ntr = 0 if csum is None or csum.dim() != 3 else int(csum.shape[0])
+        sh = level_cond_shapes(n, self.dims[1], self.dims[2], ntr)
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("lo", lo), ("hi", hi), ("cnt", cnt), ("csum", csum))}
+        _check(lib().mpdata_plan_level_cond_device(self._p, int(sl0), n, int(tc), P["lo"], P["hi"], P["cnt"], P["csum"], int(first_tracer),
+                                                   ntr))
+
+    def level_cond_host(self, tc, lo=None, hi=None, cnt=None, csum=None, sl0=0, n=None):
+        """The same for all tracers with HOST arrays (numpy, Fortran order): lo, hi or None, cnt (written) (n, nzm), csum
+        (written) (n, nzm, ntracers); cnt or csum may be None; synchronous (mpdata_plan_level_cond[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        P = {name: None if a is None else self._block_host(a, name, (n, nzm), tr, out)
+             for name, a, tr, out in (("lo", lo, False, False), ("hi", hi, False, False), ("cnt", cnt, False, True),
+                                      ("csum", csum, True, True))}
+        _check(getattr(lib(), "mpdata_plan_level_cond" + self._sfx)(self._p, int(sl0), n, int(tc), P["lo"], P["hi"], P["cnt"], P["csum"]))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1446,6 +1479,36 @@ def level_cov(f, ta, tb, cov, ma=None, mb=None, mode=0, mean_a=None, mean_b=None
     fn = lib().mpdata_level_cov_device if f.dtype == torch.float64 else lib().mpdata_level_cov_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(ta), int(tb), P["ma"], P["mb"], int(mode), P["cov"], P["mean_a"],
               P["mean_b"], _stream_handle(stream)))
+
+
+def level_cond_shapes(n, nx, nz, ntr=1):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a level_cond call on n instances and ntr
+    value tracers: lo, hi, cnt (nzm, n), csum (ntr, nzm, n).  (nx is taken as the other shape functions take it; no array
+    of the call has a column axis.)"""
+    n, nx, nz, ntr = int(n), int(nx), int(nz), int(ntr)
+    return {"lo": (nz - 1, n), "hi": (nz - 1, n), "cnt": (nz - 1, n), "csum": (ntr, nz - 1, n)}
+
+
+def level_cond(f, tc, lo=None, hi=None, cnt=None, csum=None, first_tracer=0, sl0=0, n=None, stream=None):
+    """Per-level conditional counts and sums (include/mpdata_hip.h 3v) of instances [sl0, sl0+n) (default: the rest from
+    sl0) of a reference-layout DEVICE tensor f (ntr, nzm, nx+6, ncrms), float64 or float32, which is only read: a column is
+    in where lo < f[tc] <= hi; cnt = the number of interior columns that are in, csum[j] = the sum of tracer first_tracer +
+    j over them.  lo, hi, cnt, csum of the same dtype with the shapes of level_cond_shapes(n, nx, nz, ntr), ntr the leading
+    axis of csum (lo or hi, and cnt or csum, may be None).  Asynchronous on `stream` (mpdata_level_cond_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"level_cond: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() != 4 or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis")
+    nt, nzm, nxp6, ncrms = f.shape
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    ntr = 0 if csum is None or csum.dim() != 3 else int(csum.shape[0])
+    sh = level_cond_shapes(n, nxp6 - 6, nzm + 1, ntr)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("lo", lo), ("hi", hi), ("cnt", cnt), ("csum", csum))}
+    fn = lib().mpdata_level_cond_device if f.dtype == torch.float64 else lib().mpdata_level_cond_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(tc), P["lo"], P["hi"], P["cnt"], P["csum"], int(first_tracer), ntr,
+              _stream_handle(stream)))
 
 
 def vsolve_shapes(n, nz):

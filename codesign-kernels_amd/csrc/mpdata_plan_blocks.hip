@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3u).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_level_cov.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3v).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_level_cond.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -11,6 +11,7 @@
 #include "mpdata_courant.h"
 #include "mpdata_diffuse.h"
 #include "mpdata_level_add.h"
+#include "mpdata_level_cond.h"
 #include "mpdata_level_cov.h"
 #include "mpdata_plan_priv.h"
 #include "mpdata_relax.h"
@@ -1404,6 +1405,90 @@ int mpdata_level_cov_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t
 int mpdata_level_cov_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int ta, int tb,
                                 const float* ma, const float* mb, int mode, float* cov, float* mean_a, float* mean_b, void* stream) {
   return level_cov_array(ncrms, nx, nz, ntracers, sl0, n, f, ta, tb, ma, mb, mode, cov, mean_a, mean_b, stream, 4);
+}
+
+// ---- 3v: per-level conditional counts and sums of f: how many interior columns have tracer tc inside (lo, hi], and the
+// sum of every value tracer over exactly those columns.  Reads f, lo and hi, writes cnt and csum: as 3g and 3u, no flag of
+// the plan is touched (the halo and seam marks stay -- halo columns are not read, owned levels are right whatever the
+// seams hold), no event is recorded, and a windowed plan's inner plan is read where it lies.
+static int plan_level_cond(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, void* cnt, void* csum,
+                           int first, int count) {
+  if (plan_walked(p)) {
+    MpdataLevelCondJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, 0, p->ntracers);
+    b.sel = block_sel(p, sl0, n);
+    b.tc = tc; b.first = first; b.ntr = count;
+    b.lo = lo; b.hi = hi; b.cnt = cnt; b.csum = csum;
+    HIP_TRY(mpdata_level_cond_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_level_cond_ref(p->f, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, tc, lo, hi, cnt, csum, first, count,
+                                  p->stream));
+  }
+  return 0;
+}
+// the condition, the bounds, the outputs and the value tracers of a call, for the plan forms (ntracers of the plan) and
+// the array forms alike; without csum the range is not looked at
+static int level_cond_args(const char* what, int ntracers, int tc, const void* lo, const void* hi, const void* cnt, const void* csum,
+                           int first, int count) {
+  if (tc < 0 || tc >= ntracers) return set_err(MPDATA_EINVAL, "%s: condition tracer tc %d outside the %d tracers", what, tc, ntracers);
+  if (!lo && !hi) return set_err(MPDATA_EINVAL, "%s: lo and hi are both NULL", what);
+  if (!cnt && !csum) return set_err(MPDATA_EINVAL, "%s: cnt and csum are both NULL", what);
+  if (csum && (first < 0 || count < 1 || first > ntracers - count))
+    return set_err(MPDATA_EINVAL, "%s: tracer range [%d, %lld) outside the %d tracers", what, first, (long long)first + count, ntracers);
+  return 0;
+}
+static int plan_level_cond_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi,
+                                 const void* cnt, const void* csum, int first, int count, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = level_cond_args(what, p->ntracers, tc, lo, hi, cnt, csum, first, count);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_level_cond_device(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, void* cnt, void* csum,
+                                  int first_tracer, int ntracers) {
+  const int rc = plan_level_cond_check("mpdata_plan_level_cond_device", p, sl0, n, tc, lo, hi, cnt, csum, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_level_cond(p, sl0, n, tc, lo, hi, cnt, csum, first_tracer, ntracers);
+}
+static int plan_level_cond_host(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, void* cnt, void* csum,
+                                int eb) {
+  int rc = plan_level_cond_check("mpdata_plan_level_cond", p, sl0, n, tc, lo, hi, cnt, csum, 0, p ? p->ntracers : 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb;
+  HostArr a[4] = {{lo, kb, false}, {hi, kb, false}, {cnt, kb, true}, {csum, kb * p->ntracers, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_level_cond(p, sl0, n, tc, a[0].dev, a[1].dev, a[2].dev, a[3].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_level_cond(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const double* lo, const double* hi, double* cnt, double* csum) {
+  return plan_level_cond_host(p, sl0, n, tc, lo, hi, cnt, csum, 8);
+}
+int mpdata_plan_level_cond_f32(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const float* lo, const float* hi, float* cnt, float* csum) {
+  return plan_level_cond_host(p, sl0, n, tc, lo, hi, cnt, csum, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): asynchronous
+static int level_cond_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const void* f, int tc, const void* lo,
+                            const void* hi, void* cnt, void* csum, int first, int count, void* stream, int eb) {
+  const char* const what = "mpdata_level_cond_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  rc = level_cond_args(what, ntracers, tc, lo, hi, cnt, csum, first, count);
+  if (rc) return rc;
+  HIP_TRY(mpdata_level_cond_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tc, lo, hi, cnt, csum, first, count, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_level_cond_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, int tc,
+                             const double* lo, const double* hi, double* cnt, double* csum, int first_tracer, int ntr, void* stream) {
+  return level_cond_array(ncrms, nx, nz, ntracers, sl0, n, f, tc, lo, hi, cnt, csum, first_tracer, ntr, stream, 8);
+}
+int mpdata_level_cond_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int tc,
+                                 const float* lo, const float* hi, float* cnt, float* csum, int first_tracer, int ntr, void* stream) {
+  return level_cond_array(ncrms, nx, nz, ntracers, sl0, n, f, tc, lo, hi, cnt, csum, first_tracer, ntr, stream, 4);
 }
 
 }  // extern "C"

@@ -86,6 +86,10 @@ module mpdata_hip_mod
   ! mpdata_plan_level_cov[_f32] and mpdata_level_cov[_f32]_device have no Fortran interface yet
   public :: mpdata_plan_level_cov_device_c
   integer(c_int), parameter, public :: MPDATA_LEVEL_COV_RAW = 1
+  ! per-level conditional counts and sums of a resident plan's tracers (include/mpdata_hip.h section 3v): the device form
+  ! only, one binding for both precisions -- it carries no reals of its own; it stands in the second interface block,
+  ! behind 3u's; mpdata_plan_level_cond[_f32] and mpdata_level_cond[_f32]_device have no Fortran interface yet
+  public :: mpdata_plan_level_cond_device_c
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
   ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
   ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
@@ -603,6 +607,20 @@ module mpdata_hip_mod
       type(c_ptr), value :: ma, mb
       integer(c_int), value :: mode
       type(c_ptr), value :: cov, mean_a, mean_b
+    end function
+    ! ---- per-level conditional counts and sums (include/mpdata_hip.h section 3v; tracers counted from 0): a column is in
+    ! where lo(n, nzm) < f(tc) <= hi(n, nzm) (c_null_ptr: that bound does not bind; one of the two is needed); cnt(n, nzm) =
+    ! the number of interior columns that are in, csum(n, nzm, ntracers) = the SUM of tracers first_tracer .. first_tracer +
+    ! ntracers - 1 over exactly those columns (c_null_ptr: skipped; one of the two is needed); device arrays of the plan's
+    ! precision, asynchronous on the plan's stream; nothing of the plan changes; windowed plans are supported
+    integer(c_int) function mpdata_plan_level_cond_device_c(plan, sl0, n, tc, lo, hi, cnt, csum, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_level_cond_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi, cnt, csum
+      integer(c_int), value :: first_tracer, ntracers
     end function
   end interface
 

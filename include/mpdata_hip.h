@@ -1318,6 +1318,94 @@ int mpdata_level_cov_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int
                                 int tb, const float* ma, const float* mb, int mode, float* cov, float* mean_a, float* mean_b,
                                 void* stream);
 
+/* ---- 3v. Per-level conditional counts and sums of a resident plan's tracers (the third kind of horizontal statistic a
+ * host model takes from its CRM instances every step, next to the first moments and extrema of 3g and the second moments
+ * of 3u: the share of the columns of a level in which a tracer exceeds a threshold, and the sum of other tracers over
+ * exactly those columns -- the cloud fraction profile handed to the radiation of the global model, in-cloud means of the
+ * water species, "core" and "environment" averages, a histogram of a tracer per level taken bin by bin.  The minimum and
+ * maximum of 3g only say whether ANY column is in; everything else forced the condition tracer and every sampled tracer
+ * out of the plan).  This section is the specification; the reference tree has no such routine.  For one condition
+ * tracer tc, a range of value tracers [first_tracer, first_tracer + ntracers) -- tc may lie inside it --, every instance
+ * sl in [sl0, sl0 + n) with b = sl - sl0, every level k = 1 .. nzm, nzm = nz - 1, over the INTERIOR columns i = 1 .. nx,
+ * with c_i = f(sl,i,k,tc) and v_i = f(sl,i,k,t), every statement below is rounded ONCE in the plan's precision, in this
+ * association, with nothing contracted, and the comparisons are plain compare-and-select, so EXACT and FAST plans give
+ * the same bits:
+ *   in_i = (lo ? c_i >  lo(b,k) : true)  and  (hi ? c_i <= hi(b,k) : true)     (half-open: bins (lo, hi] tile the line)
+ *   cnt(b,k)    :  q = +0;  do i = 1, nx:  if in_i:  q = q + 1                 (a real of the plan's precision; NULL: skipped)
+ *   csum(b,k,j) :  s = +0;  do i = 1, nx:  if in_i:  s = s + v_i               (j = t - first_tracer; NULL: skipped)
+ * The interval is half-open, (lo, hi]: a column with c_i == lo is out, one with c_i == hi is in, so the bins of a
+ * histogram whose edges are each the hi of one bin and the lo of the next count every column exactly once.  Selection
+ * means selection: a column that is not in contributes NOTHING, whatever its bits -- an excluded cell of a VALUE tracer
+ * may hold an infinity or a NaN and it does not reach csum; multiplying v_i by a 0 / 1 mask is therefore wrong (0 * inf
+ * is a NaN).  Adding a selected +0 in place of v_i IS allowed: in round-to-nearest a sum is -0 only when both
+ * terms are -0 (an exact zero from terms of opposite sign is +0, and +0 + (-0) = +0), s starts at +0, so by induction s can
+ * never be -0, and s + (+0) keeps every bit of every other s.  (cnt likewise: q + (+0) = q.)  NaN in c_i, lo or hi is outside the
+ * contract.  lo, hi (optional inputs, at least one required), cnt and csum (optional outputs, at least one required): lo,
+ * hi and cnt are (n, nzm) arrays, csum is (n, nzm, ntracers), all of the plan's precision, reference layout, instance
+ * index fastest, leading dimension n (the block's first instance at index 0), as sum of 3g.  A level with lo >= hi is
+ * empty: cnt = +0, csum = +0.  Sums are SUMS, and cnt is a count: the caller divides (cnt / nx: the fraction; csum / cnt:
+ * the conditional mean, where cnt > 0), so no rounding is hidden.  cnt is exact: nx < 2^24.
+ * Towards the rest of a plan, exactly as 3g and 3u: halo columns are never read, so a PERIODIC plan needs no wrap; nothing
+ * of the plan's state changes -- filled, have_u, have_w, the halo marks, the seam marks, the timing pair and
+ * last_kernel_ms --; the call is outside the run's event pair; the plan need not hold velocities.
+ *   windowed plans (3e, nz > 238) are supported: only OWNED levels are read, each with lo / hi of the tall level it stands
+ *     for, each is written to that tall level, and no seam refresh is launched in front.
+ *   no output is reached by the phantom half of an odd fp32 plan (3f), the partner of a split fp32 pair or a padding slot,
+ *     and no byte outside cnt and csum is touched.
+ * A kernel of its own on every kind of plan (mpdata_level_cond.hip), not fused into the run.  Wave-major and windowed plans:
+ * a lane owns one (instance, level) element and walks its interior column slots as read-only linear streams (the walk of
+ * 3g / 3u), 8 columns in flight; the value tracers lie at signed 64-bit offsets from the tc stream and are a loop inside
+ * the kernel (no tracer axis on the grid); lo and hi sit in registers, every accumulator is lane-local in column order.  No
+ * LDS, no barrier, no cross-lane traffic.  Two forms with the same bits: MASK (nx <= 64 and two value tracers or more: one walk over the tc stream forms
+ * cnt, the sum of tc under its own condition and a 64-bit in-mask per lane, then one walk per value tracer adds under the
+ * mask -- the condition is read ONCE for all tracers, and the walk of t == tc is the first one, kept) and RE-READ (every other call:
+ * per value tracer the tc stream and the t stream are walked together, one stream for t == tc, and compared again).  A wave
+ * none of whose elements is in the block, or owned in a window, loads nothing.  Reference-layout plans and the array
+ * forms: one thread per instance and level row, loops over i, 64-bit offsets.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), tc outside [0, ntracers), lo and hi both NULL, cnt and csum
+ * both NULL, with a non-null csum a tracer range that is empty or outside the plan (with csum == NULL the range is not
+ * looked at); in the array forms bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null f,
+ * then the same list as above.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3u (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md AF, tools/level_cond_bench.py, profiles/level_cond_bench.json), 65536 x 32 x 28,
+ * cold, plans of nine tracers, lo and hi given, 40 % of the columns in, fp64 / fp32: cnt alone 0.103 / 0.060 ms (4.4 / 3.8 TB/s of
+ * the algorithmic bytes, the interior of the T + 1 tracers read once: (T + 1) nx nzm ncrms reals); cnt and csum of T = 1, 2, 3,
+ * 8 value tracers 0.195 / 0.112, 0.296 / 0.158, 0.378 / 0.225, 0.826 / 0.457 ms -- 4.7 / 4.1, 4.6 / 4.3, 4.8 / 4.0, 4.9 / 4.5 TB/s.  lo alone
+ * is 2 % faster.  Against existing calls in the same run: (a) mpdata_plan_export_device of the T + 1 tracers (the old route
+ * without the caller's kernel): 0.49 x / 0.51 x for cnt alone, 0.48 x / 0.50 x, 0.49 x / 0.49 x, 0.47 x / 0.53 x, 0.46 x / 0.49 x for T = 1, 2, 3,
+ * 8; (b) T + 1 mpdata_plan_level_stats_device calls, which read the same bytes once: 1.12 x / 1.16 x for cnt alone, 1.05 x / 1.10 x,
+ * 1.08 x / 1.04 x, 1.04 x / 1.11 x, 1.00 x / 1.01 x.  Said plainly: the call halves the export it replaces and LOSES to the level_stats
+ * calls on the same bytes, by 12 % to 16 % for cnt alone and by less the more tracers share the condition -- a compare, a
+ * select and, for cnt, a second accumulator per column against one add.  A block of 64 instances: 0.013 / 0.015 ms.  Tall plans,
+ * 4096 x 32 x 300 (6 windows), T = 3: 0.325 / 0.192 ms, 0.51 x / 0.34 x (a), 1.07 x / 1.00 x (b).  MASK against RE-READ (the same library
+ * with the MASK limit at 0, same session), nx = 32, T = 2, 3, 8: 0.296 against 0.319, 0.378 against 0.448, 0.826 against 1.093 ms fp64
+ * (-7 %, -16 %, -24 %), 0.158 / 0.177, 0.225 / 0.252, 0.457 / 0.594 fp32 (-11 %, -11 %, -23 %); nx = 64 (32768 instances): -14 %, -19 %,
+ * -27 % fp64 and -15 %, -21 %, -20 % fp32: beyond the 3 % spread of 3r, so MASK runs there.  For cnt alone and for T = 1 both forms
+ * read the same bytes and MASK was 6 % SLOWER (cnt alone) or within 4 % either way (T = 1): RE-READ runs for those.  The
+ * tracer loop inside the kernel against one call per tracer, which is the traffic of a tracer axis on the grid: 0.378 against
+ * 0.557 ms fp64, 0.225 / 0.328 fp32 at T = 3 -- the loop stays. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_level_cond_device(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, void* cnt,
+                                  void* csum, int first_tracer, int ntracers);
+/* host arrays, all tracers (csum (n, nzm, ntracers of the plan)), synchronous (the plan's block staging buffer, as the
+ * 3g - 3u host forms) */
+int mpdata_plan_level_cond(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const double* lo, const double* hi, double* cnt,
+                           double* csum);
+int mpdata_plan_level_cond_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const float* lo, const float* hi, float* cnt,
+                               float* csum);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm,ntracers) (leading
+ * dimension ncrms), which is only read; lo, hi, cnt, csum as above (leading dimension n; csum (n, nzm, ntr)).  Asynchronous
+ * on `stream`; 64-bit offsets. */
+int mpdata_level_cond_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, int tc,
+                             const double* lo, const double* hi, double* cnt, double* csum, int first_tracer, int ntr,
+                             void* stream);
+int mpdata_level_cond_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int tc,
+                                 const float* lo, const float* hi, float* cnt, float* csum, int first_tracer, int ntr,
+                                 void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
