@@ -222,6 +222,14 @@ def lib():
         for name in ("mpdata_level_cond_device", "mpdata_level_cond_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, dp, dp, dp, dp, ci, ci, vp]
+        L.mpdata_plan_column_cond_device.restype = ci
+        L.mpdata_plan_column_cond_device.argtypes = [vp, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_column_cond", "mpdata_plan_column_cond_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, dp, dp, dp, dp, dp, dp, dp, dp]
+        for name in ("mpdata_column_cond_device", "mpdata_column_cond_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, dp, ci, dp, dp, dp, dp, dp, dp, dp, dp, ci, ci, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1149,6 +1157,41 @@ class Plan:
                                       ("csum", csum, True, True))}
         _check(getattr(lib(), "mpdata_plan_level_cond" + self._sfx)(self._p, int(sl0), n, int(tc), P["lo"], P["hi"], P["cnt"], P["csum"]))
 
+    def column_cond(self, tc, lo=None, hi=None, kcnt=None, kbot=None, ktop=None, cpath=None, cover=None, mass=None, first_tracer=0,
+                    sl0=0, n=None):
+        """Per-column conditional level counts, tops and paths (include/mpdata_hip.h 3w) of the interior columns of
+        instances [sl0, sl0+n) (default: the rest of the plan from sl0): a level is IN where lo < f(tc) <= hi (a bound that
+        is None does not bind; one of the two is needed; lo = +inf shuts a level out: a band of levels); kcnt = the number
+        of levels of a column that are in, kbot / ktop = the lowest / highest of them (0: none), cpath[j] = the sum of rho *
+        adz * tracer first_tracer + j over exactly those levels, cover = the number of columns with kcnt > 0 (needs kcnt),
+        mass[j] = the sum of cpath[j] over the columns (needs cpath); on the plan's stream
+        (mpdata_plan_column_cond_device).  Reference-layout DEVICE tensors of the plan's precision, shapes
+        column_cond_shapes(n, nx, nz, ntr): lo, hi (nzm, n); kcnt, kbot, ktop (nx, n); cpath (ntr, nx, n) with ntr its
+        leading axis; cover (n,); mass (ntr, n); any output may be None (skipped), not all.  Changes nothing of the plan.
+        Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        ntr = 0 if cpath is None or cpath.dim() != 3 else int(cpath.shape[0])
+        sh = column_cond_shapes(n, self.dims[1], self.dims[2], ntr)
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt())
+             for k, t in (("lo", lo), ("hi", hi), ("kcnt", kcnt), ("kbot", kbot), ("ktop", ktop), ("cpath", cpath), ("cover", cover),
+                          ("mass", mass))}
+        _check(lib().mpdata_plan_column_cond_device(self._p, int(sl0), n, int(tc), P["lo"], P["hi"], P["kcnt"], P["kbot"], P["ktop"],
+                                                    P["cpath"], P["cover"], P["mass"], int(first_tracer), ntr))
+
+    def column_cond_host(self, tc, lo=None, hi=None, kcnt=None, kbot=None, ktop=None, cpath=None, cover=None, mass=None, sl0=0, n=None):
+        """The same for all tracers with HOST arrays (numpy, Fortran order): lo, hi (n, nzm) or None; written: kcnt, kbot,
+        ktop (n, nx), cpath (n, nx, ntracers), cover (n,), mass (n, ntracers), each or None; synchronous
+        (mpdata_plan_column_cond[_f32])."""
+        n = self._block_n(sl0, n)
+        nx, nzm = self.dims[1], self.dims[2] - 1
+        P = {name: None if a is None else self._block_host(a, name, shape, tr, out)
+             for name, a, shape, tr, out in (("lo", lo, (n, nzm), False, False), ("hi", hi, (n, nzm), False, False),
+                                             ("kcnt", kcnt, (n, nx), False, True), ("kbot", kbot, (n, nx), False, True),
+                                             ("ktop", ktop, (n, nx), False, True), ("cpath", cpath, (n, nx), True, True),
+                                             ("cover", cover, (n,), False, True), ("mass", mass, (n,), True, True))}
+        _check(getattr(lib(), "mpdata_plan_column_cond" + self._sfx)(self._p, int(sl0), n, int(tc), P["lo"], P["hi"], P["kcnt"], P["kbot"],
+                                                                    P["ktop"], P["cpath"], P["cover"], P["mass"]))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1509,6 +1552,43 @@ def level_cond(f, tc, lo=None, hi=None, cnt=None, csum=None, first_tracer=0, sl0
     fn = lib().mpdata_level_cond_device if f.dtype == torch.float64 else lib().mpdata_level_cond_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(tc), P["lo"], P["hi"], P["cnt"], P["csum"], int(first_tracer), ntr,
               _stream_handle(stream)))
+
+
+def column_cond_shapes(n, nx, nz, ntr=1):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a column_cond call on n instances and
+    ntr value tracers: lo, hi (nzm, n); kcnt, kbot, ktop (nx, n); cpath (ntr, nx, n); cover (n,); mass (ntr, n)."""
+    n, nx, nz, ntr = int(n), int(nx), int(nz), int(ntr)
+    return {"lo": (nz - 1, n), "hi": (nz - 1, n), "kcnt": (nx, n), "kbot": (nx, n), "ktop": (nx, n), "cpath": (ntr, nx, n),
+            "cover": (n,), "mass": (ntr, n)}
+
+
+def column_cond(f, rho, adz, tc, lo=None, hi=None, kcnt=None, kbot=None, ktop=None, cpath=None, cover=None, mass=None, first_tracer=0,
+                sl0=0, n=None, stream=None):
+    """Per-column conditional level counts, tops and paths (include/mpdata_hip.h 3w) of instances [sl0, sl0+n) (default: the
+    rest from sl0) of reference-layout DEVICE tensors f (ntr, nzm, nx+6, ncrms), rho, adz (nzm, ncrms), float64 or float32,
+    which are only read: a level is in where lo < f[tc] <= hi; kcnt = the levels of a column that are in, kbot / ktop = the
+    lowest / highest of them, cpath[j] = the sum of rho * adz * tracer first_tracer + j over them, cover = the columns with
+    kcnt > 0, mass[j] = the sum of cpath[j] over the columns.  lo, hi and the outputs of the same dtype with the shapes of
+    column_cond_shapes(n, nx, nz, ntr), ntr the leading axis of cpath (lo or hi, and all outputs but one, may be None).
+    Asynchronous on `stream` (mpdata_column_cond_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"column_cond: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() != 4 or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis")
+    nt, nzm, nxp6, ncrms = f.shape
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    pr = _dev_ptr(rho, (nzm, ncrms), "rho", f.dtype)
+    pa = _dev_ptr(adz, (nzm, ncrms), "adz", f.dtype)
+    ntr = 0 if cpath is None or cpath.dim() != 3 else int(cpath.shape[0])
+    sh = column_cond_shapes(n, nxp6 - 6, nzm + 1, ntr)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype)
+         for k, t in (("lo", lo), ("hi", hi), ("kcnt", kcnt), ("kbot", kbot), ("ktop", ktop), ("cpath", cpath), ("cover", cover),
+                      ("mass", mass))}
+    fn = lib().mpdata_column_cond_device if f.dtype == torch.float64 else lib().mpdata_column_cond_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, pr, pa, int(tc), P["lo"], P["hi"], P["kcnt"], P["kbot"], P["ktop"],
+              P["cpath"], P["cover"], P["mass"], int(first_tracer), ntr, _stream_handle(stream)))
 
 
 def vsolve_shapes(n, nz):

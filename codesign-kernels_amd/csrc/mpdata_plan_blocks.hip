@@ -1,5 +1,5 @@
 // mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3v).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_level_cond.hip.  A call is its kernel file, a dispatch on the
+// code only: the kernels are in mpdata_stats.hip .. mpdata_column_cond.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -12,6 +12,7 @@
 #include "mpdata_diffuse.h"
 #include "mpdata_level_add.h"
 #include "mpdata_level_cond.h"
+#include "mpdata_column_cond.h"
 #include "mpdata_level_cov.h"
 #include "mpdata_plan_priv.h"
 #include "mpdata_relax.h"
@@ -1489,6 +1490,114 @@ int mpdata_level_cond_device(int64_t ncrms, int nx, int nz, int ntracers, int64_
 int mpdata_level_cond_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int tc,
                                  const float* lo, const float* hi, float* cnt, float* csum, int first_tracer, int ntr, void* stream) {
   return level_cond_array(ncrms, nx, nz, ntracers, sl0, n, f, tc, lo, hi, cnt, csum, first_tracer, ntr, stream, 4);
+}
+
+// ---- 3w: per-column conditional level counts, bottoms, tops and paths of f: along the levels of every interior column,
+// how many have tracer tc inside (lo, hi], the first and the last of them, and the mass-weighted integral of every value
+// tracer over exactly those levels; cover and mass are their reductions over the columns.  Reads f, rho, adz, lo and hi,
+// writes the outputs: as 3k and 3v, no flag of the plan is touched (the halo and seam marks stay -- halo columns are not
+// read, owned levels are right whatever the seams hold), no event is recorded, a windowed plan's inner plan is read where
+// it lies, and the velocities are not looked at.
+struct ColumnCondOut {
+  void *kcnt, *kbot, *ktop, *cpath, *cover, *mass;
+};
+static int plan_column_cond(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, const ColumnCondOut& o,
+                            int first, int count) {
+  if (!o.cpath) first = count = 0;
+  if (plan_walked(p)) {
+    const mpdata_plan* q = wm_plan(p);
+    MpdataColumnCondJob b;
+    b.j = wm_job(q, 0, nullptr, 0, p->ntracers);
+    kc_rho_adz(q, b);
+    b.sel = block_sel(p, sl0, n);
+    b.tc = tc; b.first = first; b.ntr = count;
+    b.lo = lo; b.hi = hi;
+    b.kcnt = o.kcnt; b.kbot = o.kbot; b.ktop = o.ktop; b.cpath = o.cpath; b.cover = o.cover; b.mass = o.mass;
+    HIP_TRY(mpdata_column_cond_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_column_cond_ref(p->f, p->rho, p->adz, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, tc, lo, hi, o.kcnt, o.kbot,
+                                   o.ktop, o.cpath, o.cover, o.mass, first, count, p->stream));
+  }
+  return 0;
+}
+// the condition, the bounds, the outputs and the value tracers of a call, for the plan forms (ntracers of the plan) and
+// the array forms alike; without cpath the range is not looked at
+static int column_cond_args(const char* what, int ntracers, int tc, const void* lo, const void* hi, const ColumnCondOut& o, int first,
+                            int count) {
+  if (tc < 0 || tc >= ntracers) return set_err(MPDATA_EINVAL, "%s: condition tracer tc %d outside the %d tracers", what, tc, ntracers);
+  if (!lo && !hi) return set_err(MPDATA_EINVAL, "%s: lo and hi are both NULL", what);
+  if (!o.kcnt && !o.kbot && !o.ktop && !o.cpath && !o.cover && !o.mass) return set_err(MPDATA_EINVAL, "%s: every output is NULL", what);
+  if (o.cover && !o.kcnt) return set_err(MPDATA_EINVAL, "%s: cover without kcnt", what);
+  if (o.mass && !o.cpath) return set_err(MPDATA_EINVAL, "%s: mass without cpath", what);
+  if (o.cpath && (first < 0 || count < 1 || first > ntracers - count))
+    return set_err(MPDATA_EINVAL, "%s: tracer range [%d, %lld) outside the %d tracers", what, first, (long long)first + count, ntracers);
+  return 0;
+}
+static int plan_column_cond_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi,
+                                  const ColumnCondOut& o, int first, int count, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = column_cond_args(what, p->ntracers, tc, lo, hi, o, first, count);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_column_cond_device(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, void* kcnt, void* kbot,
+                                   void* ktop, void* cpath, void* cover, void* mass, int first_tracer, int ntracers) {
+  const ColumnCondOut o = {kcnt, kbot, ktop, cpath, cover, mass};
+  const int rc = plan_column_cond_check("mpdata_plan_column_cond_device", p, sl0, n, tc, lo, hi, o, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_column_cond(p, sl0, n, tc, lo, hi, o, first_tracer, ntracers);
+}
+static int plan_column_cond_host(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, void* kcnt, void* kbot,
+                                 void* ktop, void* cpath, void* cover, void* mass, int eb) {
+  const ColumnCondOut o = {kcnt, kbot, ktop, cpath, cover, mass};
+  int rc = plan_column_cond_check("mpdata_plan_column_cond", p, sl0, n, tc, lo, hi, o, 0, p ? p->ntracers : 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb, xb = (size_t)n * p->nx * eb;
+  HostArr a[8] = {{lo, kb, false}, {hi, kb, false}, {kcnt, xb, true}, {kbot, xb, true}, {ktop, xb, true}, {cpath, xb * p->ntracers, true},
+                  {cover, (size_t)n * eb, true}, {mass, (size_t)n * p->ntracers * eb, true}};
+  rc = stage_in(p, a);
+  const ColumnCondOut d = {a[2].dev, a[3].dev, a[4].dev, a[5].dev, a[6].dev, a[7].dev};
+  if (!rc) rc = plan_column_cond(p, sl0, n, tc, a[0].dev, a[1].dev, d, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_column_cond(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const double* lo, const double* hi, double* kcnt, double* kbot,
+                            double* ktop, double* cpath, double* cover, double* mass) {
+  return plan_column_cond_host(p, sl0, n, tc, lo, hi, kcnt, kbot, ktop, cpath, cover, mass, 8);
+}
+int mpdata_plan_column_cond_f32(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const float* lo, const float* hi, float* kcnt, float* kbot,
+                                float* ktop, float* cpath, float* cover, float* mass) {
+  return plan_column_cond_host(p, sl0, n, tc, lo, hi, kcnt, kbot, ktop, cpath, cover, mass, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): asynchronous
+static int column_cond_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const void* f, const void* rho,
+                             const void* adz, int tc, const void* lo, const void* hi, const ColumnCondOut& o, int first, int count,
+                             void* stream, int eb) {
+  const char* const what = "mpdata_column_cond_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f || !rho || !adz) return set_err(MPDATA_EINVAL, "%s: null %s", what, !f ? "f" : !rho ? "rho" : "adz");
+  rc = column_cond_args(what, ntracers, tc, lo, hi, o, first, count);
+  if (rc) return rc;
+  if (!o.cpath) first = count = 0;
+  HIP_TRY(mpdata_column_cond_ref(f, rho, adz, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tc, lo, hi, o.kcnt, o.kbot, o.ktop, o.cpath, o.cover,
+                                 o.mass, first, count, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_column_cond_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, const double* rho,
+                              const double* adz, int tc, const double* lo, const double* hi, double* kcnt, double* kbot, double* ktop,
+                              double* cpath, double* cover, double* mass, int first_tracer, int ntr, void* stream) {
+  const ColumnCondOut o = {kcnt, kbot, ktop, cpath, cover, mass};
+  return column_cond_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tc, lo, hi, o, first_tracer, ntr, stream, 8);
+}
+int mpdata_column_cond_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, const float* rho,
+                                  const float* adz, int tc, const float* lo, const float* hi, float* kcnt, float* kbot, float* ktop,
+                                  float* cpath, float* cover, float* mass, int first_tracer, int ntr, void* stream) {
+  const ColumnCondOut o = {kcnt, kbot, ktop, cpath, cover, mass};
+  return column_cond_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tc, lo, hi, o, first_tracer, ntr, stream, 4);
 }
 
 }  // extern "C"

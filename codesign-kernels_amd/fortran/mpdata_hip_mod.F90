@@ -90,6 +90,12 @@ module mpdata_hip_mod
   ! only, one binding for both precisions -- it carries no reals of its own; it stands in the second interface block,
   ! behind 3u's; mpdata_plan_level_cond[_f32] and mpdata_level_cond[_f32]_device have no Fortran interface yet
   public :: mpdata_plan_level_cond_device_c
+  ! per-column conditional level counts, tops and paths of a resident plan's tracers (include/mpdata_hip.h section 3w): all
+  ! five entry points, each bound by its literal name -- the arrays are c_ptr, so the fp64 and the fp32 form of the host
+  ! and of the array call are two interfaces each and a caller picks by its precision (tests/fortran/column_cond_calls.F90);
+  ! they stand in the second interface block, behind 3v's
+  public :: mpdata_plan_column_cond_device_c, mpdata_plan_column_cond_c, mpdata_plan_column_cond_f32_c
+  public :: mpdata_column_cond_device_c, mpdata_column_cond_f32_device_c
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
   ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
   ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
@@ -621,6 +627,69 @@ module mpdata_hip_mod
       integer(c_int), value :: tc
       type(c_ptr), value :: lo, hi, cnt, csum
       integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! ---- per-column conditional level counts, tops and paths (include/mpdata_hip.h section 3w; tracers counted from 0): a
+    ! level is in where lo(n, nzm) < f(tc) <= hi(n, nzm) (c_null_ptr: that bound does not bind; one of the two is needed;
+    ! lo = +inf shuts a level out); kcnt(n, nx) = the levels of a column that are in, kbot, ktop(n, nx) = the lowest and the
+    ! highest of them (0: none), cpath(n, nx, ntracers) = the sum of rho * adz * f of tracers first_tracer .. first_tracer +
+    ! ntracers - 1 over exactly those levels, cover(n) = the columns with kcnt > 0 (needs kcnt), mass(n, ntracers) = the sum
+    ! of cpath over the columns (needs cpath); c_null_ptr: skipped, one output is needed; device arrays of the plan's
+    ! precision, asynchronous on the plan's stream; nothing of the plan changes; windowed plans are supported
+    integer(c_int) function mpdata_plan_column_cond_device_c(plan, sl0, n, tc, lo, hi, kcnt, kbot, ktop, cpath, cover, mass, &
+                                                             first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_column_cond_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi, kcnt, kbot, ktop, cpath, cover, mass
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! host arrays, all tracers (c_loc of real(c_double) arrays, or c_null_ptr), synchronous
+    integer(c_int) function mpdata_plan_column_cond_c(plan, sl0, n, tc, lo, hi, kcnt, kbot, ktop, cpath, cover, mass) &
+        bind(C, name="mpdata_plan_column_cond")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi, kcnt, kbot, ktop, cpath, cover, mass
+    end function
+    ! ... of real(c_float) arrays, for fp32 plans
+    integer(c_int) function mpdata_plan_column_cond_f32_c(plan, sl0, n, tc, lo, hi, kcnt, kbot, ktop, cpath, cover, mass) &
+        bind(C, name="mpdata_plan_column_cond_f32")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi, kcnt, kbot, ktop, cpath, cover, mass
+    end function
+    ! the same on instances [sl0, sl0 + n) of reference-layout device arrays f, rho(ncrms,nzm), adz(ncrms,nzm) of real(c_double)
+    integer(c_int) function mpdata_column_cond_device_c(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tc, lo, hi, kcnt, kbot, ktop, &
+                                                        cpath, cover, mass, first_tracer, ntr, stream) &
+        bind(C, name="mpdata_column_cond_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f, rho, adz
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi, kcnt, kbot, ktop, cpath, cover, mass
+      integer(c_int), value :: first_tracer, ntr
+      type(c_ptr), value :: stream
+    end function
+    ! ... of real(c_float)
+    integer(c_int) function mpdata_column_cond_f32_device_c(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tc, lo, hi, kcnt, kbot, ktop, &
+                                                        cpath, cover, mass, first_tracer, ntr, stream) &
+        bind(C, name="mpdata_column_cond_f32_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f, rho, adz
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi, kcnt, kbot, ktop, cpath, cover, mass
+      integer(c_int), value :: first_tracer, ntr
+      type(c_ptr), value :: stream
     end function
   end interface
 

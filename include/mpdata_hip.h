@@ -1406,6 +1406,99 @@ int mpdata_level_cond_f32_device(int64_t ncrms, int nx, int nz, int ntracers, in
                                  const float* lo, const float* hi, float* cnt, float* csum, int first_tracer, int ntr,
                                  void* stream);
 
+/* ---- 3w. Per-column conditional level counts, tops and paths of a resident plan's tracers (the column diagnostics a host
+ * model takes from its CRM instances every step: shaded cloud cover -- the share of the columns that hold ANY cloudy
+ * level, as a whole and in a low, a middle and a high band of levels --, the cloud-base and cloud-top level of every
+ * column, and in-cloud water paths, the mass-weighted integral of other tracers over exactly the cloudy levels of a
+ * column.  3v answers "how many columns of this level are in"; it cannot answer "is this column in anywhere", which needs
+ * the same condition reduced along k per column: this call is the transposed twin of 3v, as 3k is of 3g.  Everything
+ * here forced T + 1 tracers out of the plan before).  This section is the specification; the reference tree has no such
+ * routine.  For one condition tracer tc, a range of value tracers [first_tracer, first_tracer + ntracers) -- tc may lie
+ * inside it --, every instance sl in [sl0, sl0 + n) with b = sl - sl0 and every INTERIOR column i = 1 .. nx, with c_k =
+ * f(sl,i,k,tc), v_k = f(sl,i,k,t) and j = t - first_tracer, every statement below is rounded ONCE in the plan's
+ * precision, in this association, with nothing contracted, and the comparisons are plain compare-and-select, so EXACT
+ * and FAST plans give the same bits:
+ *   wgt(sl,k)    = rho(sl,k) * adz(sl,k)                                          (one rounded multiply: 3k's weight)
+ *   in_k         = (lo ? c_k >  lo(b,k) : true)  and  (hi ? c_k <= hi(b,k) : true)     (half-open (lo, hi], as 3v)
+ *   kcnt(b,i)    :  q = +0;  do k = 1, nzm:  if in_k:  q = q + 1
+ *   kbot(b,i)    :  the smallest k in 1 .. nzm with in_k, as a real;  +0 if there is none
+ *   ktop(b,i)    :  the largest  k in 1 .. nzm with in_k, as a real;  +0 if there is none
+ *   cpath(b,i,j) :  s = +0;  do k = 1, nzm:  if in_k:  s = s + wgt(sl,k) * v_k     (the product rounded, then the add; no fma)
+ *   cover(b)     :  q = +0;  do i = 1, nx:   if kcnt(b,i) > 0:  q = q + 1
+ *   mass(b,j)    :  s = +0;  do i = 1, nx:   s = s + cpath(b,i,j)                  (3k's mass)
+ * lo and hi follow 3v: both optional, at least one required, each an (n, nzm) array of the plan's precision in the
+ * reference layout, instance fastest, leading dimension n.  A level with lo >= hi is out in every column, and so is a
+ * level with lo = +inf: that is how a caller restricts a call to a BAND of levels per instance (lo = +inf outside the
+ * band); three bands -- low, middle, high cloud cover -- are three calls.  Selection means selection: a level that is not in contributes NOTHING,
+ * whatever bits an excluded cell of a VALUE tracer holds, an infinity or a NaN included; multiplying by a 0 / 1 mask is
+ * therefore wrong (0 * inf is a NaN).  Adding a selected +0 is allowed, by the argument in 3v (s starts at +0 and can
+ * never become -0).  NaN in c_k, lo or hi is outside the contract.
+ * The six outputs are all optional, at least one is required: kcnt, kbot and ktop are (n, nx) arrays, cpath is (n, nx,
+ * ntracers), cover is (n), mass is (n, ntracers); all reals of the plan's precision -- the counts and level indices are
+ * exact because nzm, nx < 2^24 --, all in the reference layout with the instance fastest and the tracer slowest, tightly
+ * packed, interior columns only.  cover needs kcnt and mass needs cpath (MPDATA_EINVAL otherwise): as in 3k, a second
+ * small kernel on the same stream forms them from those arrays.  Without cpath the tracer range is not looked at.
+ * Two identities (both tested):  with every level in -- hi = +inf alone, say -- cpath has the bits of 3k's path and mass
+ * the bits of its mass;  and sum_i kcnt(b,i) == sum_k cnt(b,k) of 3v for the same tc, lo and hi, both sides exact.
+ * Towards the rest of a plan, exactly as 3k and 3v: halo columns are never read, so a PERIODIC plan needs no wrap; nothing
+ * of the plan's state changes -- filled, have_u, have_w, the halo marks, the seam marks, the timing pair and
+ * last_kernel_ms --; the call is outside the run's event pair; the plan need not hold velocities.
+ *   windowed plans (3e, nz > 238) are supported: only OWNED levels are read, each with lo, hi and the weight of the tall
+ *     level it stands for, in rising order of the tall level; k in kbot and ktop is the TALL level; the running values
+ *     stay in registers across the windows; no seam refresh is launched.
+ *   no output is reached by the phantom half of an odd fp32 plan (3f), the partner of a split fp32 pair, padding slots or
+ *     instances outside the block, and no byte outside the outputs is written.
+ * A kernel of its own on every kind of plan (mpdata_column_cond.hip), not fused into the run.  Wave-major and windowed
+ * plans: the staging of 3k -- a workgroup copies the column slots of a group of adjacent instances and a batch of columns
+ * through LDS as linear streams, with the rows wgt, lo and hi of those instances; a lane per (instance element, column)
+ * walks its levels from LDS in rising order.  The condition tracer is staged ONCE per workgroup and batch: the lane keeps
+ * the in-bits of its levels in registers (eight 32-bit words per half, all at compile-time positions), forms kcnt, kbot
+ * and ktop from them with integer bit operations (exact), and the value tracers follow through the same columns of LDS
+ * in a loop inside the kernel, each summed under the bits.  (Windowed plans carry the running sums of up to eight value
+ * tracers across the windows in registers; a ninth tracer stages the condition a second time.)  With cpath == NULL only
+ * tc is staged.  No reduction across lanes; a store of an (n, nx) row of a full group is a whole 128-byte line.
+ * Reference-layout plans and the array forms: one thread per (instance, column), coalesced along the instances, the
+ * loops over k and the tracers inside, 64-bit offsets.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), tc outside [0, ntracers), lo and hi both NULL, every output
+ * NULL, cover without kcnt or mass without cpath, with a non-null cpath a tracer range that is empty or outside the plan;
+ * in the array forms bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null f, rho or
+ * adz, then the same list as above.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3v (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md AG, tools/column_cond_bench.py, profiles/column_cond_bench.json), 65536 x 32 x 28,
+ * cold, plans of nine tracers, lo and hi given, 40 % of the levels in, fp64 / fp32: kcnt + cover 0.182 / 0.126 ms; cpath of T = 1,
+ * 3, 8 value tracers 0.270 / 0.183, 0.462 / 0.306, 0.908 / 0.622 ms -- 3.4 / 2.5, 3.9 / 3.0, 4.5 / 3.3 TB/s of the algorithmic bytes, the
+ * interior of the T + 1 tracers read once.  Against existing calls in the same run on the same plans: (a)
+ * mpdata_plan_export_device of the T + 1 tracers (the old route without the caller's kernel): 0.87 x / 1.09 x for kcnt + cover,
+ * 0.66 x / 0.83 x, 0.58 x / 0.72 x, 0.51 x / 0.66 x for T = 1, 3, 8; (b) mpdata_plan_column_path_device of T + 1 tracers, the same bytes
+ * through the same staging: 1.43 x / 1.66 x, 1.09 x / 1.30 x, 0.96 x / 1.13 x, 0.85 x / 1.04 x.  Said plainly: the count alone beats the
+ * export by little in fp64 and LOSES to it in fp32; the call loses to column_path until three (fp64) or more than eight (fp32)
+ * value tracers share the condition.  Tall plans, 4096 x 32 x 300 (6 windows): 0.539 / 0.388, 0.809 / 0.580, 1.367 / 0.976, 2.771 / 1.962
+ * ms -- it LOSES to the export everywhere there (3.2 x / 2.7 x for the count, 1.9 x / 1.6 x at T = 8) and to column_path by 1.5 x to 2.2 x:
+ * two columns fit next to the three rows at 55 levels.  A block of 64 instances: 0.020 / 0.029 ms. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_column_cond_device(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, void* kcnt,
+                                   void* kbot, void* ktop, void* cpath, void* cover, void* mass, int first_tracer, int ntracers);
+/* host arrays, all tracers (cpath (n, nx, ntracers of the plan), mass (n, ntracers of the plan)), synchronous (the
+ * plan's block staging buffer, as the 3g - 3v host forms) */
+int mpdata_plan_column_cond(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const double* lo, const double* hi, double* kcnt,
+                            double* kbot, double* ktop, double* cpath, double* cover, double* mass);
+int mpdata_plan_column_cond_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const float* lo, const float* hi, float* kcnt,
+                                float* kbot, float* ktop, float* cpath, float* cover, float* mass);
+/* the same on instances [sl0, sl0+n) of reference-layout DEVICE arrays f(ncrms,-2:nx+3,1,nzm,ntracers), rho(ncrms,nzm),
+ * adz(ncrms,nzm) (leading dimension ncrms), which are only read; lo, hi and the outputs as above (leading dimension n;
+ * cpath (n, nx, ntr), mass (n, ntr)).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_column_cond_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f,
+                              const double* rho, const double* adz, int tc, const double* lo, const double* hi, double* kcnt,
+                              double* kbot, double* ktop, double* cpath, double* cover, double* mass, int first_tracer, int ntr,
+                              void* stream);
+int mpdata_column_cond_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f,
+                                  const float* rho, const float* adz, int tc, const float* lo, const float* hi, float* kcnt,
+                                  float* kbot, float* ktop, float* cpath, float* cover, float* mass, int first_tracer, int ntr,
+                                  void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
