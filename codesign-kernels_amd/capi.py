@@ -230,6 +230,14 @@ def lib():
         for name in ("mpdata_column_cond_device", "mpdata_column_cond_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, dp, ci, dp, dp, dp, dp, dp, dp, dp, dp, ci, ci, vp]
+        L.mpdata_plan_nonneg_device.restype = ci
+        L.mpdata_plan_nonneg_device.argtypes = [vp, i64, i64, vp, vp, ci, ci]
+        for name in ("mpdata_plan_nonneg", "mpdata_plan_nonneg_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, dp, dp]
+        for name in ("mpdata_nonneg_device", "mpdata_nonneg_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1083,6 +1091,35 @@ class Plan:
                 for name, a, tr, out in (("c", c, False, False), ("target", target, True, False), ("mean", mean, True, True))]
         _check(getattr(lib(), "mpdata_plan_relax" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def nonneg(self, sum=None, nneg=None, sl0=0, n=None, first_tracer=0, ntracers=None):
+        """The conservative per-level non-negativity fixer of f in place (include/mpdata_hip.h 3x) on the interior columns
+        of instances [sl0, sl0+n) (default: the rest of the plan from sl0): in every row (instance, level, tracer) with a
+        negative cell the negative cells become +0 and the others are scaled by s / p, the row's sum over the sum of its
+        positive cells (one rounded divide), so that the row keeps its total; a row whose sum is not positive becomes +0
+        throughout; a row without a negative cell keeps every bit and is not stored; on the plan's stream
+        (mpdata_plan_nonneg_device).  Reference-layout DEVICE tensors of the plan's precision, shapes nonneg_shapes(n,
+        nx, nz, ntr): sum ([ntr,] nzm, n) or None, the row sums of the OLD field (the sum of level_stats); nneg ([ntr,] nzm,
+        n) or None, the number of negative cells of each row as a real.  The tracers are first_tracer .. +ntr-1, ntr =
+        ntracers, or the leading axis of a 3-d sum or nneg (else 1); both carry that axis together; with neither output and
+        no ntracers: every tracer from first_tracer on -- Plan.nonneg() fixes the whole plan.  Windowed plans are
+        supported."""
+        n = self._block_n(sl0, n)
+        nx, nz = self.dims[1], self.dims[2]
+        if sum is None and nneg is None and ntracers is None:
+            ntracers = self.dims[3] - int(first_tracer)
+        ntr, axis = self._block_ntr(sum if sum is not None else nneg, ntracers)
+        sh = nonneg_shapes(n, nx, nz, ntr if axis else None)
+        ptrs = [None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("sum", sum), ("nneg", nneg))]
+        _check(lib().mpdata_plan_nonneg_device(self._p, int(sl0), n, *ptrs, int(first_tracer), ntr))
+
+    def nonneg_host(self, sum=None, nneg=None, sl0=0, n=None):
+        """The same for all tracers into HOST arrays (numpy, Fortran order): sum, nneg (n, nzm[, ntracers]) or None
+        (written), synchronous (mpdata_plan_nonneg[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        ptrs = [None if a is None else self._block_host(a, name, (n, nzm), True, True) for name, a in (("sum", sum), ("nneg", nneg))]
+        _check(getattr(lib(), "mpdata_plan_nonneg" + self._sfx)(self._p, int(sl0), n, *ptrs))
+
     def convert(self, src, dst, r, q0=None, y=None, mode=0, dsum=None, sl0=0, n=None):
         """First-order conversion from tracer src to tracer dst in place (include/mpdata_hip.h 3t) on the interior columns
         of instances [sl0, sl0+n) (default: the rest of the plan from sl0): d = r * max(f_src - q0, 0), with mode
@@ -1463,6 +1500,36 @@ def relax(f, c, target=None, mean=None, sl0=0, n=None, stream=None):
     sh = relax_shapes(n, nxp6 - 6, nzm + 1, nt if f.dim() == 4 else None)
     ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("c", c), ("target", target), ("mean", mean))]
     fn = lib().mpdata_relax_device if f.dtype == torch.float64 else lib().mpdata_relax_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, *ptrs, _stream_handle(stream)))
+
+
+def nonneg_shapes(n, nx, nz, ntracers=None):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a nonneg call on n instances: sum and
+    nneg ([ntracers,] nzm, n); ntracers None: one tracer without the leading axis.  (nx is taken as the other shape
+    functions take it; no array of the call has a column axis.)"""
+    lead = () if ntracers is None else (int(ntracers),)
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {"sum": lead + (nz - 1, n), "nneg": lead + (nz - 1, n)}
+
+
+def nonneg(f, sum=None, nneg=None, sl0=0, n=None, stream=None):
+    """The conservative per-level non-negativity fixer (include/mpdata_hip.h 3x) of instances [sl0, sl0+n) (default: the
+    rest from sl0) of a reference-layout DEVICE tensor f ([ntr,] nzm, nx+6, ncrms), float64 or float32, in place: rows of
+    the interior columns with a negative cell get their negative cells zeroed and the others scaled so that the row keeps
+    its sum (all +0 where the sum is not positive); sum, nneg of the same dtype with the shapes of nonneg_shapes(n, nx,
+    nz, ntr), each may be None.  Asynchronous on `stream` (mpdata_nonneg_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"nonneg: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() not in (3, 4) or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f")
+    nt = f.shape[0] if f.dim() == 4 else 1
+    nzm, nxp6, ncrms = f.shape[-3:]
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = nonneg_shapes(n, nxp6 - 6, nzm + 1, nt if f.dim() == 4 else None)
+    ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("sum", sum), ("nneg", nneg))]
+    fn = lib().mpdata_nonneg_device if f.dtype == torch.float64 else lib().mpdata_nonneg_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, *ptrs, _stream_handle(stream)))
 
 

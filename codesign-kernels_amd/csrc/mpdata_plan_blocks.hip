@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3v).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_column_cond.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3x).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_nonneg.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -14,6 +14,7 @@
 #include "mpdata_level_cond.h"
 #include "mpdata_column_cond.h"
 #include "mpdata_level_cov.h"
+#include "mpdata_nonneg.h"
 #include "mpdata_plan_priv.h"
 #include "mpdata_relax.h"
 #include "mpdata_scale_uw.h"
@@ -1598,6 +1599,70 @@ int mpdata_column_cond_f32_device(int64_t ncrms, int nx, int nz, int ntracers, i
                                   float* cpath, float* cover, float* mass, int first_tracer, int ntr, void* stream) {
   const ColumnCondOut o = {kcnt, kbot, ktop, cpath, cover, mass};
   return column_cond_array(ncrms, nx, nz, ntracers, sl0, n, f, rho, adz, tc, lo, hi, o, first_tracer, ntr, stream, 4);
+}
+
+// ---- 3x: conservative per-level non-negativity fixer of f, in place: the negative cells of an interior row become +0 and
+// the others are scaled so that the row keeps its sum; a row without a negative cell is read and not stored.  Writes sum
+// and nneg, rewrites the INTERIOR columns of f of the block's instances and the tracer range; flux, u, w, rho, rhow, adz and
+// the boundary mode are not touched and no event is recorded.  Halo marks, seam marks and the phantom: word for word as
+// 3r's (plan_relax) -- the sums are over the owned level's own interior columns; the marks of the range are cleared
+// whether a row was rewritten or not, since the host does not know.
+static int plan_nonneg(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* nneg, int first, int count) {
+  if (plan_walked(p)) {
+    MpdataNonnegJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, first, count);
+    b.sel = block_sel(p, sl0, n);
+    b.sum = sum; b.nneg = nneg;
+    HIP_TRY(mpdata_nonneg_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_nonneg_ref(ref_f(p, first), p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, count, sum, nneg, p->stream));
+  }
+  return plan_rewrote(p, sl0, n, first, count, SEAMS | HALOS);
+}
+static int plan_nonneg_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int first, int count, int eb) {
+  const int rc = block_ranges(what, p, sl0, n, first, count, eb);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_nonneg_device(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* nneg, int first_tracer, int ntracers) {
+  const int rc = plan_nonneg_check("mpdata_plan_nonneg_device", p, sl0, n, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_nonneg(p, sl0, n, sum, nneg, first_tracer, ntracers);
+}
+static int plan_nonneg_host(mpdata_plan* p, int64_t sl0, int64_t n, void* sum, void* nneg, int eb) {
+  int rc = plan_nonneg_check("mpdata_plan_nonneg", p, sl0, n, 0, 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb * p->ntracers;
+  HostArr a[2] = {{sum, kb, true}, {nneg, kb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_nonneg(p, sl0, n, a[0].dev, a[1].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_nonneg(mpdata_plan* p, int64_t sl0, int64_t n, double* sum, double* nneg) {
+  return plan_nonneg_host(p, sl0, n, sum, nneg, 8);
+}
+int mpdata_plan_nonneg_f32(mpdata_plan* p, int64_t sl0, int64_t n, float* sum, float* nneg) {
+  return plan_nonneg_host(p, sl0, n, sum, nneg, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): in place, asynchronous
+static int nonneg_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, void* sum, void* nneg, void* stream,
+                        int eb) {
+  int rc = array_sizes("mpdata_nonneg_device", ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block("mpdata_nonneg_device", ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "mpdata_nonneg_device: null f");
+  HIP_TRY(mpdata_nonneg_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, sum, nneg, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_nonneg_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, double* sum, double* nneg,
+                         void* stream) {
+  return nonneg_array(ncrms, nx, nz, ntracers, sl0, n, f, sum, nneg, stream, 8);
+}
+int mpdata_nonneg_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, float* sum, float* nneg,
+                             void* stream) {
+  return nonneg_array(ncrms, nx, nz, ntracers, sl0, n, f, sum, nneg, stream, 4);
 }
 
 }  // extern "C"

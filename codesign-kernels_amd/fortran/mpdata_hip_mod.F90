@@ -96,6 +96,11 @@ module mpdata_hip_mod
   ! they stand in the second interface block, behind 3v's
   public :: mpdata_plan_column_cond_device_c, mpdata_plan_column_cond_c, mpdata_plan_column_cond_f32_c
   public :: mpdata_column_cond_device_c, mpdata_column_cond_f32_device_c
+  ! conservative per-level non-negativity fixer of a resident plan's tracers, in place (include/mpdata_hip.h section 3x): all
+  ! five entry points, each bound by its literal name as 3w's are (tests/fortran/nonneg_calls.F90); they stand in the second
+  ! interface block, behind 3w's
+  public :: mpdata_plan_nonneg_device_c, mpdata_plan_nonneg_c, mpdata_plan_nonneg_f32_c
+  public :: mpdata_nonneg_device_c, mpdata_nonneg_f32_device_c
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
   ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
   ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
@@ -689,6 +694,56 @@ module mpdata_hip_mod
       integer(c_int), value :: tc
       type(c_ptr), value :: lo, hi, kcnt, kbot, ktop, cpath, cover, mass
       integer(c_int), value :: first_tracer, ntr
+      type(c_ptr), value :: stream
+    end function
+    ! ---- conservative per-level non-negativity fixer of f in place (include/mpdata_hip.h section 3x; tracers counted from
+    ! 0): in every row (instance, level, tracer) with a negative interior cell the negative cells become +0 and the others
+    ! are scaled by the row's sum over the sum of its positive cells, so that the row keeps its total (all +0 where the sum
+    ! is not positive); a row without a negative cell keeps every bit; sum, nneg(n, nzm, ntracers) = the row sums of the old
+    ! field and the negative cells of each row, written (c_null_ptr: skipped; both may be); device arrays of the plan's
+    ! precision, asynchronous on the plan's stream; halo columns are neither read nor written; windowed plans are supported
+    integer(c_int) function mpdata_plan_nonneg_device_c(plan, sl0, n, sum, nneg, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_nonneg_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: sum, nneg
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! host arrays, all tracers (c_loc of real(c_double) arrays, or c_null_ptr), synchronous
+    integer(c_int) function mpdata_plan_nonneg_c(plan, sl0, n, sum, nneg) &
+        bind(C, name="mpdata_plan_nonneg")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: sum, nneg
+    end function
+    ! ... of real(c_float) arrays, for fp32 plans
+    integer(c_int) function mpdata_plan_nonneg_f32_c(plan, sl0, n, sum, nneg) &
+        bind(C, name="mpdata_plan_nonneg_f32")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: sum, nneg
+    end function
+    ! the same on instances [sl0, sl0 + n) of a reference-layout device array f of real(c_double), in place
+    integer(c_int) function mpdata_nonneg_device_c(ncrms, nx, nz, ntracers, sl0, n, f, sum, nneg, stream) &
+        bind(C, name="mpdata_nonneg_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f, sum, nneg
+      type(c_ptr), value :: stream
+    end function
+    ! ... of real(c_float)
+    integer(c_int) function mpdata_nonneg_f32_device_c(ncrms, nx, nz, ntracers, sl0, n, f, sum, nneg, stream) &
+        bind(C, name="mpdata_nonneg_f32_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f, sum, nneg
       type(c_ptr), value :: stream
     end function
   end interface

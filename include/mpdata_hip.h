@@ -1499,6 +1499,90 @@ int mpdata_column_cond_f32_device(int64_t ncrms, int nx, int nz, int ntracers, i
                                   float* kbot, float* ktop, float* cpath, float* cover, float* mass, int first_tracer, int ntr,
                                   void* stream);
 
+/* ---- 3x. A conservative per-level non-negativity fixer of a resident plan's tracers, in place (what a SAM-type host
+ * model runs after a step that can drive a positive-definite tracer below zero -- 3i and 3p without CLIP, 3m with a
+ * Courant number above one, 3t without LIMIT, 3l near its stability limit, 3o with a caller's matrix: the negative cells
+ * of a level are set to zero and the level's other cells are scaled so that the level's total is what it was.  The CLIP
+ * modes of 3i and 3p clip and create mass; this call does not).  This section is the specification; the reference tree
+ * has no such routine.  For instance sl in [sl0, sl0 + n), tracer t in [first_tracer, first_tracer + ntracers), level
+ * k = 1 .. nzm, nzm = nz - 1, interior column i = 1 .. nx, with b = sl - sl0:
+ *   s = +0;  p = +0;  c = +0
+ *   do i = 1, nx:  x = f_old(sl,i,k,t)
+ *                  s = s + x                      (the sum of 3g, in its order: the same bits as level_stats)
+ *                  y = (x > 0) ? x : +0           (compare-and-select; -0.0 and negatives give +0)
+ *                  p = p + y
+ *                  c = c + ((x < 0) ? 1 : 0)
+ *   sum(b,k,t) = s;  nneg(b,k,t) = c              (each optional; c as a real of the plan's precision, as cnt of 3v)
+ *   c == 0       :  f(sl,:,k,t) keeps every bit -- the row is not rewritten; a -0.0 there stays
+ *   c > 0, s > 0 :  r = s / p (ONE IEEE divide, correctly rounded in both precisions);  f(sl,i,k,t) = y_i * r
+ *   c > 0, else  :  f(sl,i,k,t) = +0 for every i  (the row owes mass; sum tells the caller how much)
+ * Every operation is rounded ONCE in the plan's precision, in exactly this association; nothing is contracted, so EXACT
+ * and FAST plans give the same bits.  NaN and infinities are outside the contract.  r is whatever the divide gives: it
+ * is at most 1 up to rounding, it can be exactly 1 (a negative cell far below the row's unit roundoff), and it is not
+ * clamped.  A fixed row sums to s up to (2 nx + 4) u sum|f_old| (two sequential sums, the divide, the products), and a
+ * second call finds nneg == 0 everywhere and changes nothing.
+ * Both arrays are of the plan's precision, reference layout, instance index fastest, leading dimension n (the block's
+ * first instance at index 0), tightly packed, tracer slowest:
+ *   sum   (n, nzm [, ntracers])   only written; may be NULL
+ *   nneg  (n, nzm [, ntracers])   only written; may be NULL
+ * With both NULL the call is still valid.  No byte outside these arrays is read or written.  Afterwards the plan behaves
+ * exactly as if the interior of f had been exported, changed as above and imported again.
+ * Towards the rest of a plan (3r's rules, word for word):
+ *   halo marks   only interior columns are read and written; halo columns are neither.  GIVEN plans: halos keep every
+ *     bit.  PERIODIC plans: no wrap is launched, because the sums are taken over the interior alone; the halo marks of
+ *     the range are cleared afterwards, so the next run or read-back hands out wrapped halos of the new field.
+ *   windowed plans (3e, nz > 238) are supported: the call reads and writes OWNED levels only, needs no seam refresh in
+ *     front, and clears the seam marks of the range afterwards.  sum and nneg of a level are written by that level's
+ *     owner and are addressed by tall level directly in the caller's arrays: nothing is cut into windows.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 whenever the block holds it and its row is
+ *     rewritten (on a windowed plan the phantom of the inner plan is restored behind the call, as in 3m / 3n / 3p / 3r).
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded: a -0.0 or a negative value there
+ *     stays; padding slots, neighbours in a tile, instances and tracers outside the ranges, flux, u, w, rho, rhow, adz,
+ *     the held-velocity flags, the boundary mode and the timing pair keep every bit.  The call is outside the run's
+ *     event pair; the plan need not hold velocities.
+ * A kernel of its own on every kind of plan (mpdata_nonneg.hip), not fused into the run.  Wave-major and windowed plans: a
+ * lane owns one (instance, level) element and walks its interior column slots (the walk of 3g, 3i and 3r), so the three
+ * reductions are lane-local: no LDS, no barrier, no cross-lane traffic, and no ordering to argue.  Two forms (DESIGN.md
+ * 4.27): nx <= 32, the KEPT form -- the nx columns of the lane's element are loaded into registers once (fully unrolled,
+ * no scratch), reduced, and scaled and stored by the lanes whose row is in need; nx > 32, the RE-READ form -- a reducing
+ * walk, the outputs, and, unless no lane of the wave is in need, the updating walk over the same columns.  Both give the
+ * same bits.  A row without a negative cell is read and never stored: on a field that is already clean the call is a
+ * read.  Reference-layout plans and the array forms: one thread per instance and (level, tracer) row, two loops over i,
+ * in place, no scratch array.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), a bad tracer range; in the array forms bad sizes
+ * (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, then a null f.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3w (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Not offered (follow-ups): a floor other than zero; borrowing along the column (a vertical fixer in the staging of 3k);
+ * fusing the fixer into 3q.
+ * Time on the MI355X (docs/EXPERIMENTS.md AH, tools/nonneg_bench.py, profiles/nonneg_bench.json), 65536 x 32 x 28, one tracer,
+ * cold, fp64 / fp32: (a) a field without a negative cell 0.091 / 0.052 ms -- 0.84 x / 0.85 x mpdata_plan_level_stats_device
+ * (sum), which reads the same bytes (0.108 / 0.061 ms), 5.0 / 4.4 TB/s of the interior of f read once; (b) every row in need
+ * 0.216 / 0.113 ms -- 1.00 x / 1.05 x mpdata_plan_relax_device in mean mode, which moves the same bytes (0.216 / 0.108 ms), 4.2 /
+ * 4.0 TB/s of the interior read once and written once; with both outputs 0.236 / 0.121 ms; (c) the mix of the tests (71 % of
+ * the rows in need) 0.223 / 0.113 ms.  Against mpdata_plan_export_device + mpdata_plan_import_device of f alone, the old route
+ * without the caller's kernel (0.448 / 0.238 ms): (a) 0.20 x / 0.22 x, (b) 0.48 x / 0.47 x, (c) 0.50 x / 0.47 x.  With 25
+ * tracers: (a) 2.01 / 1.06 ms, (b) 5.38 / 2.78 ms (0.99 x / 1.02 x relax, 0.51 x / 0.53 x the round trip).  Tall plans, 4096 x 32
+ * x 300 (6 windows): (a) 0.065 / 0.036 ms (0.79 x / 0.73 x level_stats), (b) 0.151 / 0.083 ms (1.01 x / 1.09 x relax, 0.40 x /
+ * 0.27 x the round trip).  The KEPT form against the RE-READ form at nx = 32 on (b): 0.216 against 0.228 ms fp64, 0.113 / 0.125
+ * fp32, 0.151 / 0.170 and 0.083 / 0.094 tall -- 5 % to 12 % (10 % to 18 % on the mix), where five rounds of one form differ by
+ * 3 % (tall: 4 %) at most.  Said plainly: (b) does not beat relax -- in fp32 it is 5 % (tall: 9 %) slower, with three running sums per
+ * half where relax has one --, and the mix is no faster than (b) although it stores 71 % of the rows: a lane that returns
+ * early frees nothing while the other lanes of its wave store. */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_nonneg_device(mpdata_plan* plan, int64_t sl0, int64_t n, void* sum, void* nneg, int first_tracer, int ntracers);
+/* host arrays, all tracers, synchronous (the plan's block staging buffer, as the 3g - 3w host forms) */
+int mpdata_plan_nonneg(mpdata_plan* plan, int64_t sl0, int64_t n, double* sum, double* nneg);
+int mpdata_plan_nonneg_f32(mpdata_plan* plan, int64_t sl0, int64_t n, float* sum, float* nneg);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm[,ntracers]) (leading
+ * dimension ncrms); sum, nneg as above (leading dimension n).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_nonneg_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, double* sum, double* nneg,
+                         void* stream);
+int mpdata_nonneg_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, float* sum, float* nneg,
+                             void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
