@@ -27,6 +27,7 @@ BOUNDARY_GIVEN, BOUNDARY_PERIODIC = 0, 1   # MPDATA_BOUNDARY_* (include/mpdata_h
 LEVEL_ADD, LEVEL_ADD_CLIP = 0, 1           # MPDATA_LEVEL_ADD* (include/mpdata_hip.h section 3i)
 CELL_ADD, CELL_ADD_CLIP = 0, 1             # MPDATA_CELL_ADD* (include/mpdata_hip.h section 3p)
 CONVERT_LIMIT = 1                          # MPDATA_CONVERT_LIMIT (include/mpdata_hip.h section 3t)
+SATADJ_ICE = 1                             # MPDATA_SATADJ_ICE (include/mpdata_hip.h section 3y)
 LEVEL_COV_RAW = 1                          # MPDATA_LEVEL_COV_RAW (include/mpdata_hip.h section 3u)
 
 _lib = None
@@ -36,6 +37,28 @@ class MpdataError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libmpdata_hip error {code}: {msg}")
         self.code = code
+
+
+class SatadjParams(ctypes.Structure):
+    """struct mpdata_satadj_params (include/mpdata_hip.h section 3y): the caller's numbers of a saturation adjustment.
+    SatadjParams(esw=[...9], desw=[...9], esi=[...9], desi=[...9], t0=..., xmin=..., eps=..., lv=..., ls=..., tmin=...,
+    tmax=..., tol=..., maxit=...); what is not given is 0."""
+    _fields_ = [("esw", ctypes.c_double * 9), ("desw", ctypes.c_double * 9), ("esi", ctypes.c_double * 9),
+                ("desi", ctypes.c_double * 9), ("t0", ctypes.c_double), ("xmin", ctypes.c_double), ("eps", ctypes.c_double),
+                ("lv", ctypes.c_double), ("ls", ctypes.c_double), ("tmin", ctypes.c_double), ("tmax", ctypes.c_double),
+                ("tol", ctypes.c_double), ("maxit", ctypes.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        for k, v in kw.items():
+            if k in ("esw", "desw", "esi", "desi"):
+                v = [float(x) for x in v]
+                if len(v) != 9:
+                    raise MpdataError(-1, f"SatadjParams: {k} has {len(v)} coefficients, not 9")
+                v = (ctypes.c_double * 9)(*v)
+            elif k not in dict(self._fields_):
+                raise MpdataError(-1, f"SatadjParams: no field {k}")
+            setattr(self, k, v)
 
 
 def lib_path():
@@ -238,6 +261,15 @@ def lib():
         for name in ("mpdata_nonneg_device", "mpdata_nonneg_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, dp, vp]
+        pp = ctypes.POINTER(SatadjParams)
+        L.mpdata_plan_satadj_device.restype = ci
+        L.mpdata_plan_satadj_device.argtypes = [vp, i64, i64, ci, ci, ci, ci, vp, vp, pp, ci, vp, vp]
+        for name in ("mpdata_plan_satadj", "mpdata_plan_satadj_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, ci, ci, ci, dp, dp, pp, ci, dp, dp]
+        for name in ("mpdata_satadj_device", "mpdata_satadj_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, ci, ci, dp, dp, pp, ci, dp, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1120,6 +1152,31 @@ class Plan:
         ptrs = [None if a is None else self._block_host(a, name, (n, nzm), True, True) for name, a in (("sum", sum), ("nneg", nneg))]
         _check(getattr(lib(), "mpdata_plan_nonneg" + self._sfx)(self._p, int(sl0), n, *ptrs))
 
+    def satadj(self, th, tq, tn, pres, par, tt=-1, gz=None, mode=0, ncld=None, iters=None, sl0=0, n=None):
+        """Saturation adjustment in place (include/mpdata_hip.h 3y) on the interior columns of instances [sl0, sl0+n)
+        (default: the rest of the plan from sl0): the condensate (tracer tn, overwritten) and, with tt >= 0, the temperature
+        (tracer tt) from the temperature-like tracer th and total water tq, by a Newton iteration per cell on the curves of
+        par (a SatadjParams; None reaches the library as a null pointer); mode SATADJ_ICE adds the ice curve and the ramp
+        between tmin and tmax; rows with pres == 0 keep every bit of tn and tt; on the plan's stream
+        (mpdata_plan_satadj_device).  Reference-layout DEVICE tensors of the plan's precision, shapes satadj_shapes(n, nx,
+        nz): pres (nzm, n); gz (nzm, n) or None (T1 = h); ncld, iters (nzm, n) or None (skipped): the cells with
+        condensate and the most Newton steps of a row.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        sh = satadj_shapes(n, self.dims[1], self.dims[2])
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("pres", pres), ("gz", gz), ("ncld", ncld), ("iters", iters))}
+        _check(lib().mpdata_plan_satadj_device(self._p, int(sl0), n, int(th), int(tq), int(tn), int(tt), P["pres"], P["gz"],
+                                               _satadj_par(par), int(mode), P["ncld"], P["iters"]))
+
+    def satadj_host(self, th, tq, tn, pres, par, tt=-1, gz=None, mode=0, ncld=None, iters=None, sl0=0, n=None):
+        """The same from HOST arrays (numpy, Fortran order): pres (n, nzm), gz (n, nzm) or None, ncld, iters (n, nzm) or
+        None (written), synchronous (mpdata_plan_satadj[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        P = {name: None if a is None else self._block_host(a, name, (n, nzm), False, out)
+             for name, a, out in (("pres", pres, False), ("gz", gz, False), ("ncld", ncld, True), ("iters", iters, True))}
+        _check(getattr(lib(), "mpdata_plan_satadj" + self._sfx)(self._p, int(sl0), n, int(th), int(tq), int(tn), int(tt), P["pres"],
+                                                                P["gz"], _satadj_par(par), int(mode), P["ncld"], P["iters"]))
+
     def convert(self, src, dst, r, q0=None, y=None, mode=0, dsum=None, sl0=0, n=None):
         """First-order conversion from tracer src to tracer dst in place (include/mpdata_hip.h 3t) on the interior columns
         of instances [sl0, sl0+n) (default: the rest of the plan from sl0): d = r * max(f_src - q0, 0), with mode
@@ -1531,6 +1588,43 @@ def nonneg(f, sum=None, nneg=None, sl0=0, n=None, stream=None):
     ptrs = [None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("sum", sum), ("nneg", nneg))]
     fn = lib().mpdata_nonneg_device if f.dtype == torch.float64 else lib().mpdata_nonneg_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, *ptrs, _stream_handle(stream)))
+
+
+def _satadj_par(par):
+    """the par argument of a satadj call: a SatadjParams by reference, None as the null pointer"""
+    if par is None:
+        return None
+    if not isinstance(par, SatadjParams):
+        raise MpdataError(-1, f"par: {type(par).__name__} is no SatadjParams")
+    return ctypes.byref(par)
+
+
+def satadj_shapes(n, nx, nz):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a satadj call on n instances: pres, gz,
+    ncld, iters (nzm, n).  (nx is taken as the other shape functions take it; no array of the call has a column axis.)"""
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {k: (nz - 1, n) for k in ("pres", "gz", "ncld", "iters")}
+
+
+def satadj(f, th, tq, tn, pres, par, tt=-1, gz=None, mode=0, ncld=None, iters=None, sl0=0, n=None, stream=None):
+    """Saturation adjustment (include/mpdata_hip.h 3y) of instances [sl0, sl0+n) (default: the rest from sl0) of a
+    reference-layout DEVICE tensor f (ntr, nzm, nx+6, ncrms), float64 or float32, in place: tracer tn becomes the condensate
+    and, with tt >= 0, tracer tt the temperature diagnosed from tracers th and tq on the interior columns; par a
+    SatadjParams, mode 0 or SATADJ_ICE; pres, gz, ncld, iters of the same dtype with the shapes of satadj_shapes(n, nx, nz)
+    (gz, ncld, iters may be None).  Asynchronous on `stream` (mpdata_satadj_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"satadj: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() != 4 or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis")
+    nt, nzm, nxp6, ncrms = f.shape
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = satadj_shapes(n, nxp6 - 6, nzm + 1)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("pres", pres), ("gz", gz), ("ncld", ncld), ("iters", iters))}
+    fn = lib().mpdata_satadj_device if f.dtype == torch.float64 else lib().mpdata_satadj_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(th), int(tq), int(tn), int(tt), P["pres"], P["gz"], _satadj_par(par),
+              int(mode), P["ncld"], P["iters"], _stream_handle(stream)))
 
 
 def convert_shapes(n, nx, nz):

@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3x).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_nonneg.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3y).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_satadj.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -17,6 +17,7 @@
 #include "mpdata_nonneg.h"
 #include "mpdata_plan_priv.h"
 #include "mpdata_relax.h"
+#include "mpdata_satadj.h"
 #include "mpdata_scale_uw.h"
 #include "mpdata_sediment.h"
 #include "mpdata_stats.h"
@@ -156,6 +157,20 @@ int stage_out(mpdata_plan* p, const HostArr (&a)[N]) {
     if (h.host && h.out) HIP_TRY(hipMemcpyAsync(const_cast<void*>(h.host), h.dev, h.bytes, hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return 0;
+}
+
+// 3y: the caller's numbers in the precision R, each rounded once, and the three derived ones, each operation rounded once
+template <typename R>
+void satadj_par(const mpdata_satadj_params* s, MpdataSatadjPar<R>* o) {
+  for (int c = 0; c < 9; ++c) {
+    o->esw[c] = (R)s->esw[c]; o->desw[c] = (R)s->desw[c];
+    o->esi[c] = (R)s->esi[c]; o->desi[c] = (R)s->desi[c];
+  }
+  o->t0 = (R)s->t0; o->xmin = (R)s->xmin; o->eps = (R)s->eps; o->lv = (R)s->lv; o->ls = (R)s->ls;
+  o->tmin = (R)s->tmin; o->tmax = (R)s->tmax; o->tol = (R)s->tol; o->maxit = s->maxit;
+  o->an = (R)1 / (o->tmax - o->tmin);
+  o->bn = o->tmin * o->an;
+  o->lf = o->ls - o->lv;
 }
 
 }  // namespace
@@ -1663,6 +1678,111 @@ int mpdata_nonneg_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl
 int mpdata_nonneg_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, float* sum, float* nneg,
                              void* stream) {
   return nonneg_array(ncrms, nx, nz, ntracers, sl0, n, f, sum, nneg, stream, 4);
+}
+
+// ---- 3y: saturation adjustment of the tracers of f, in place: the condensate (tracer tn) and on request the temperature
+// (tracer tt) from a temperature-like tracer th and total water tq, by a Newton iteration per cell on the caller's curves.
+// Reads pres and gz, writes ncld and iters, reads the INTERIOR columns of th and tq and rewrites those of tn and tt of the
+// block's instances; every other tracer, flux, u, w, rho, rhow, adz and the boundary mode are not touched and no event is
+// recorded.  Halo marks, seam marks and the phantom of tn and tt: word for word as 3t's (plan_convert) for its two tracers;
+// the marks of th and tq do not change.
+static MpdataSatadjArgs satadj_args(int eb, int th, int tq, int tn, int tt, const void* pres, const void* gz,
+                                    const mpdata_satadj_params* par, int mode, void* ncld, void* iters) {
+  MpdataSatadjArgs a;
+  a.th = th; a.tq = tq; a.tn = tn; a.tt = tt;
+  a.pres = pres; a.gz = gz; a.ice = (mode & MPDATA_SATADJ_ICE) != 0; a.ncld = ncld; a.iters = iters;
+  if (eb == 8) satadj_par(par, &a.par.d);
+  else satadj_par(par, &a.par.f);
+  return a;
+}
+static int plan_satadj(mpdata_plan* p, int64_t sl0, int64_t n, const MpdataSatadjArgs& a) {
+  if (plan_walked(p)) {
+    MpdataSatadjJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, 0, p->ntracers);
+    b.sel = block_sel(p, sl0, n);
+    b.a = a;
+    HIP_TRY(mpdata_satadj_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_satadj_ref(p->f, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, a, p->stream));
+  }
+  const int rc = plan_rewrote(p, sl0, n, a.tn, 1, SEAMS | HALOS);
+  return rc || a.tt < 0 ? rc : plan_rewrote(p, sl0, n, a.tt, 1, SEAMS | HALOS);
+}
+// the tracers, the rows, the numbers and the mode of a call, for the plan forms (ntracers of the plan) and the array forms alike
+static int satadj_check(const char* what, int ntracers, int th, int tq, int tn, int tt, const void* pres, const mpdata_satadj_params* par,
+                        int mode) {
+  if (th < 0 || th >= ntracers || tq < 0 || tq >= ntracers || tn < 0 || tn >= ntracers)
+    return set_err(MPDATA_EINVAL, "%s: tracers (th %d, tq %d, tn %d) outside the %d tracers", what, th, tq, tn, ntracers);
+  if (tt < -1 || tt >= ntracers) return set_err(MPDATA_EINVAL, "%s: tt = %d outside [-1, %d)", what, tt, ntracers);
+  if (th == tq || th == tn || tq == tn || tt == th || tt == tq || tt == tn)
+    return set_err(MPDATA_EINVAL, "%s: tracers th %d, tq %d, tn %d, tt %d are not distinct", what, th, tq, tn, tt);
+  if (!pres) return set_err(MPDATA_EINVAL, "%s: null pres", what);
+  if (!par) return set_err(MPDATA_EINVAL, "%s: null par", what);
+  if (par->maxit < 1 || par->maxit > 32) return set_err(MPDATA_EINVAL, "%s: maxit = %d outside 1 .. 32", what, par->maxit);
+  if (!(par->tol >= 0)) return set_err(MPDATA_EINVAL, "%s: tol = %g is not >= 0", what, par->tol);
+  if ((mode & MPDATA_SATADJ_ICE) && !(par->tmax > par->tmin))
+    return set_err(MPDATA_EINVAL, "%s: tmax = %g is not > tmin = %g", what, par->tmax, par->tmin);
+  if (mode & ~MPDATA_SATADJ_ICE) return set_err(MPDATA_EINVAL, "%s: unknown mode bits %d", what, mode);
+  return 0;
+}
+static int plan_satadj_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int th, int tq, int tn, int tt,
+                             const void* pres, const mpdata_satadj_params* par, int mode, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = satadj_check(what, p->ntracers, th, tq, tn, tt, pres, par, mode);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_satadj_device(mpdata_plan* p, int64_t sl0, int64_t n, int th, int tq, int tn, int tt, const void* pres, const void* gz,
+                              const mpdata_satadj_params* par, int mode, void* ncld, void* iters) {
+  const int rc = plan_satadj_check("mpdata_plan_satadj_device", p, sl0, n, th, tq, tn, tt, pres, par, mode, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_satadj(p, sl0, n, satadj_args(p->eb, th, tq, tn, tt, pres, gz, par, mode, ncld, iters));
+}
+static int plan_satadj_host(mpdata_plan* p, int64_t sl0, int64_t n, int th, int tq, int tn, int tt, const void* pres, const void* gz,
+                            const mpdata_satadj_params* par, int mode, void* ncld, void* iters, int eb) {
+  int rc = plan_satadj_check("mpdata_plan_satadj", p, sl0, n, th, tq, tn, tt, pres, par, mode, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb;
+  HostArr a[4] = {{pres, kb, false}, {gz, kb, false}, {ncld, kb, true}, {iters, kb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_satadj(p, sl0, n, satadj_args(eb, th, tq, tn, tt, a[0].dev, a[1].dev, par, mode, a[2].dev, a[3].dev));
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_satadj(mpdata_plan* p, int64_t sl0, int64_t n, int th, int tq, int tn, int tt, const double* pres, const double* gz,
+                       const mpdata_satadj_params* par, int mode, double* ncld, double* iters) {
+  return plan_satadj_host(p, sl0, n, th, tq, tn, tt, pres, gz, par, mode, ncld, iters, 8);
+}
+int mpdata_plan_satadj_f32(mpdata_plan* p, int64_t sl0, int64_t n, int th, int tq, int tn, int tt, const float* pres, const float* gz,
+                           const mpdata_satadj_params* par, int mode, float* ncld, float* iters) {
+  return plan_satadj_host(p, sl0, n, th, tq, tn, tt, pres, gz, par, mode, ncld, iters, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): in place, asynchronous
+static int satadj_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, int th, int tq, int tn, int tt,
+                        const void* pres, const void* gz, const mpdata_satadj_params* par, int mode, void* ncld, void* iters, void* stream,
+                        int eb) {
+  const char* const what = "mpdata_satadj_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  rc = satadj_check(what, ntracers, th, tq, tn, tt, pres, par, mode);
+  if (rc) return rc;
+  HIP_TRY(mpdata_satadj_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, satadj_args(eb, th, tq, tn, tt, pres, gz, par, mode, ncld, iters),
+                            (hipStream_t)stream));
+  return 0;
+}
+int mpdata_satadj_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, int th, int tq, int tn, int tt,
+                         const double* pres, const double* gz, const mpdata_satadj_params* par, int mode, double* ncld, double* iters,
+                         void* stream) {
+  return satadj_array(ncrms, nx, nz, ntracers, sl0, n, f, th, tq, tn, tt, pres, gz, par, mode, ncld, iters, stream, 8);
+}
+int mpdata_satadj_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int th, int tq, int tn, int tt,
+                             const float* pres, const float* gz, const mpdata_satadj_params* par, int mode, float* ncld, float* iters,
+                             void* stream) {
+  return satadj_array(ncrms, nx, nz, ntracers, sl0, n, f, th, tq, tn, tt, pres, gz, par, mode, ncld, iters, stream, 4);
 }
 
 }  // extern "C"

@@ -101,6 +101,24 @@ module mpdata_hip_mod
   ! interface block, behind 3w's
   public :: mpdata_plan_nonneg_device_c, mpdata_plan_nonneg_c, mpdata_plan_nonneg_f32_c
   public :: mpdata_nonneg_device_c, mpdata_nonneg_f32_device_c
+  ! saturation adjustment of a resident plan's tracers, in place (include/mpdata_hip.h section 3y): the derived type of the
+  ! caller's numbers (struct mpdata_satadj_params, passed as c_loc of a target variable) and all five entry points, each
+  ! bound by its literal name as 3x's are (tests/fortran/satadj_calls.F90); they stand in the second interface block,
+  ! behind 3x's
+  public :: mpdata_satadj_params
+  public :: mpdata_plan_satadj_device_c, mpdata_plan_satadj_c, mpdata_plan_satadj_f32_c
+  public :: mpdata_satadj_device_c, mpdata_satadj_f32_device_c
+  integer(c_int), parameter, public :: MPDATA_SATADJ_ICE = 1
+  type, bind(C) :: mpdata_satadj_params
+    real(c_double) :: esw(9), desw(9)   ! liquid: es(x), d es / dT (x), degree-8 polynomials in x, esw(1) the constant term
+    real(c_double) :: esi(9), desi(9)   ! ice: the same; read only with MPDATA_SATADJ_ICE
+    real(c_double) :: t0, xmin          ! x = T - t0, bounded below by xmin
+    real(c_double) :: eps               ! qs = (eps * es) / max(es, p - es)
+    real(c_double) :: lv, ls            ! L / cp of condensation and of sublimation
+    real(c_double) :: tmin, tmax        ! the mixed-phase ramp, tmin < tmax; ICE only
+    real(c_double) :: tol               ! Newton stops when |dT| <= tol ...
+    integer(c_int) :: maxit             ! ... or after maxit steps, 1 <= maxit <= 32
+  end type
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
   ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
   ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
@@ -744,6 +762,74 @@ module mpdata_hip_mod
       integer(c_int), value :: nx, nz, ntracers
       integer(c_int64_t), value :: sl0, n
       type(c_ptr), value :: f, sum, nneg
+      type(c_ptr), value :: stream
+    end function
+    ! ---- saturation adjustment in place (include/mpdata_hip.h section 3y; tracers counted from 0): tracer tn becomes the
+    ! condensate and, with tt >= 0, tracer tt the temperature diagnosed from the temperature-like tracer th and total water
+    ! tq on the interior columns, by a Newton iteration per cell on the curves of par (c_loc of a type(mpdata_satadj_params));
+    ! mode 0 or MPDATA_SATADJ_ICE; pres, gz, ncld, iters(n, nzm) (gz, ncld, iters c_null_ptr: absent / skipped); rows with
+    ! pres == 0 keep every bit; device arrays of the plan's precision, asynchronous on the plan's stream; windowed plans are
+    ! supported
+    integer(c_int) function mpdata_plan_satadj_device_c(plan, sl0, n, th, tq, tn, tt, pres, gz, par, mode, ncld, iters) &
+        bind(C, name="mpdata_plan_satadj_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: th, tq, tn, tt
+      type(c_ptr), value :: pres, gz, par
+      integer(c_int), value :: mode
+      type(c_ptr), value :: ncld, iters
+    end function
+    ! host arrays (c_loc of real(c_double) arrays, or c_null_ptr), synchronous
+    integer(c_int) function mpdata_plan_satadj_c(plan, sl0, n, th, tq, tn, tt, pres, gz, par, mode, ncld, iters) &
+        bind(C, name="mpdata_plan_satadj")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: th, tq, tn, tt
+      type(c_ptr), value :: pres, gz, par
+      integer(c_int), value :: mode
+      type(c_ptr), value :: ncld, iters
+    end function
+    ! ... of real(c_float) arrays, for fp32 plans
+    integer(c_int) function mpdata_plan_satadj_f32_c(plan, sl0, n, th, tq, tn, tt, pres, gz, par, mode, ncld, iters) &
+        bind(C, name="mpdata_plan_satadj_f32")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: th, tq, tn, tt
+      type(c_ptr), value :: pres, gz, par
+      integer(c_int), value :: mode
+      type(c_ptr), value :: ncld, iters
+    end function
+    ! the same on instances [sl0, sl0 + n) of a reference-layout device array f of real(c_double), in place
+    integer(c_int) function mpdata_satadj_device_c(ncrms, nx, nz, ntracers, sl0, n, f, th, tq, tn, tt, pres, gz, par, mode, &
+                                                   ncld, iters, stream) &
+        bind(C, name="mpdata_satadj_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f
+      integer(c_int), value :: th, tq, tn, tt
+      type(c_ptr), value :: pres, gz, par
+      integer(c_int), value :: mode
+      type(c_ptr), value :: ncld, iters
+      type(c_ptr), value :: stream
+    end function
+    ! ... of real(c_float)
+    integer(c_int) function mpdata_satadj_f32_device_c(ncrms, nx, nz, ntracers, sl0, n, f, th, tq, tn, tt, pres, gz, par, mode, &
+                                                       ncld, iters, stream) &
+        bind(C, name="mpdata_satadj_f32_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f
+      integer(c_int), value :: th, tq, tn, tt
+      type(c_ptr), value :: pres, gz, par
+      integer(c_int), value :: mode
+      type(c_ptr), value :: ncld, iters
       type(c_ptr), value :: stream
     end function
   end interface

@@ -1583,6 +1583,110 @@ int mpdata_nonneg_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl
 int mpdata_nonneg_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, float* sum, float* nneg,
                              void* stream);
 
+/* ---- 3y. Saturation adjustment of a resident plan's tracers, in place (the one step of a cloud model's scalar loop that
+ * still forced an export, a caller's kernel and an import: diagnosing the condensate, and the temperature that goes with
+ * it, from a conserved temperature-like tracer and total water -- SAM's `cloud`.  It makes the cloud water that 3t turns
+ * into rain and that 3v and 3w count as cloud fraction, base and top).  This section is the specification; the reference
+ * tree has no such routine.  All the physics is in the caller's numbers: the library hard-codes no constant.
+ * Rounding: every statement below is rounded once in the plan's precision, in this association, with nothing contracted;
+ * every `/` is a correctly rounded IEEE division; every comparison is plain compare-and-select, never fmax / fmin, so NaN
+ * and -0 take the "else" value.  EXACT and FAST plans give the same bits.
+ * Parameters: a host struct, passed by const pointer and read before the call returns.  Every double is rounded once to the
+ * plan's precision; three derived values are formed on the host in the plan's precision, each operation rounded once:
+ *   an = 1 / (tmax - tmin);   bn = tmin * an;   lf = ls - lv
+ * Scope: four distinct tracers -- th (input, the temperature-like tracer), tq (input, total water), tn (output, the
+ * condensate: overwritten), tt (optional output, the temperature; -1: absent) --, every instance sl in [sl0, sl0 + n) with
+ * b = sl - sl0, every level k = 1 .. nzm, nzm = nz - 1, and every INTERIOR column i = 1 .. nx.
+ * Rows: pres (required, in the unit of es) and gz (optional, NULL: T1 = h) are (n, nzm) arrays of the plan's precision,
+ * reference layout, instance index fastest, leading dimension n (the block's first instance at index 0), as r of 3t.
+ * p = pres(b,k), and rp = 1 / p is formed once per row.  Per cell:
+ *   pres(b,k) == 0 : the row keeps every bit of tn and tt and is not stored; ncld(b,k) = iters(b,k) = +0
+ *   h = f(i,k,th);  q = f(i,k,tq);  qq = (q > 0) ? q : +0;   T1 = gz ? h - gz(b,k) : h
+ *   curve(c, dc, T):  x = T - t0;  x = (x > xmin) ? x : xmin
+ *                     es = c[8]; for j = 7..0: es = c[j] + x * es          (de likewise from dc)
+ *                     pm = p - es;  den = (pm > es) ? pm : es;  qs = (eps * es) / den;  dq = (eps * de) * rp
+ *   sat(T):  without ICE, or T >= tmax :  (qs, dq) = curve(esw, desw, T);  L = lv;  dL = +0
+ *            ICE and T <= tmin         :  (qs, dq) = curve(esi, desi, T);  L = ls;  dL = +0
+ *            else: om = an * T - bn;  u = 1 - om;  (qw, dw), (qi, di) from the two curves;
+ *                  qs = om * qw + u * qi;  dq = om * dw + u * di;  L = lv + u * lf;  dL = an * lf
+ *   (qs, ..) = sat(T1);  T = T1
+ *   qq > qs :  it = 0
+ *              repeat: (qs, dq, L, dL) = sat(T);  e = qq - qs
+ *                      fff = (T1 - T) + L * e;  dfff = (dL * e - L * dq) - 1;  d = -fff / dfff
+ *                      T = T + d;  it = it + 1
+ *              while |d| > tol and it < maxit
+ *              qs = qs + dq * d;  qn = qq - qs;  qn = (qn > 0) ? qn : +0
+ *   else    :  qn = +0;  it = 0
+ *   f(i,k,tn) = qn;   tt >= 0 : f(i,k,tt) = T
+ *   ncld(b,k)  = number of interior columns with qn > 0       (optional output, NULL: skipped)
+ *   iters(b,k) = maximum of it over the interior columns      (optional output, NULL: skipped)
+ * ncld and iters are (n, nzm) reals of the plan's precision, like cnt of 3v.  th and tq are only read and keep every bit.
+ * Halo columns are neither read nor written.  Every tracer other than tn and tt keeps every bit.  The regime branches are
+ * selects by definition, so a wave may skip a curve that none of its lanes needs without changing a bit.  A cell stops
+ * iterating on ITS OWN d, whatever its neighbours in the wave do.  Without ICE esi, desi, ls, tmin and tmax reach no result.
+ * Towards the rest of a plan, as in 3t, for the written tracers tn and tt:
+ *   halo marks   PERIODIC plans: no wrap is launched; the halo marks of tn and tt are cleared afterwards.
+ *   windowed plans (3e, nz > 238) are supported: owned levels only, each with pres and gz of the tall level it stands for;
+ *     no seam refresh in front; the seam marks of tn and tt are cleared afterwards.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 in tn and tt wherever the block holds it and its pres
+ *     is not zero (on a windowed plan the host restores the inner plan's phantom behind the call, as in 3t).
+ *   untouched    the partner of a split fp32 pair, padding slots and instances outside the block keep every bit; the marks
+ *     of th and tq do not change.  The plan need not hold velocities; the call is outside the run's event pair.
+ * A kernel of its own on every kind of plan (mpdata_satadj.hip).  Wave-major and windowed plans: the lane-owned walk of 3t;
+ * p, rp and gz in registers per half; two read streams and one or two write streams at signed 64-bit tracer offsets; no
+ * LDS, no barrier, no cross-lane traffic but the __ballot that decides whether a wave goes on iterating (and whether it
+ * needs a curve).  The Newton loop is predicated per lane and per half -- a finished cell keeps its T, qs, dq, d by select
+ * -- and the loops of several columns of a lane run interleaved under one joint exit, so that their dependent Horner chains
+ * overlap.  Templates on ICE and on tt: the warm-only kernel carries neither the second curve nor the second store stream.
+ * Reference-layout plans and the array forms: one thread per instance and level row, one loop over i.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan; n < 1 or a block outside [0, ncrms); th, tq or tn outside [0, ntracers); tt outside
+ * [-1, ntracers); any two of the given tracers equal; null pres; null par; maxit outside 1 .. 32; tol not >= 0; with ICE,
+ * tmax not > tmin; a mode bit other than MPDATA_SATADJ_ICE; in the array forms the size, block and null-f checks of 3t first.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3x.  MPDATA_ESTATE: a host form of the other precision; a plan never
+ * filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md AI, tools/satadj_bench.py, profiles/satadj_bench.json), 65536 x 32 x 28, four tracers,
+ * cold, ICE and tt, fp64 / fp32: no cell saturated 0.466 / 0.277 ms; the recipe's mix (37.5 % of the cells saturated, 1 to 6
+ * steps) 1.906 / 1.313 ms; the mix sorted so that saturated cells fill whole rows and waves 0.970 / 0.614 ms.  Warm only, no tt:
+ * 0.340 / 0.179, 1.133 / 0.727, 0.608 / 0.349 ms.  Against existing calls in the same run: (a) export_device of th, tq +
+ * import_device of tn, tt, the old route without the caller's kernel (0.851 / 0.423 ms): 0.55 x / 0.65 x dry, 2.24 x / 3.10 x on the
+ * mix, 1.14 x / 1.45 x sorted; (b) mpdata_plan_convert_device with every option, the same two reads and two writes (0.422 /
+ * 0.221 ms): 1.11 x / 1.25 x dry, 4.52 x / 5.94 x on the mix -- the call is bound by the vector unit, not by bytes, wherever cells
+ * are saturated; (c) mix over sorted 1.97 x / 2.14 x: divergence inside a wave doubles the time; (d) columns interleaved per lane
+ * (MPDATA_SATADJ_NC), mix: 1: 1.915 / 1.247 ms, 2: 1.902 / 1.306, 4: 2.001 / 1.634, 8: 3.393 / 2.668 -- interleaving does not pay (it
+ * costs registers, hence waves per SIMD, and the waves overlap the chains as well); 2 is kept, level with 1 in fp64 and 4.5 %
+ * behind it in fp32.  A block of 64 instances: 0.137 / 0.185 ms.  4096 x 32 x 300 (6 windows): dry 0.433 / 0.235 ms, mix 1.133 / 0.848
+ * ms, 1.50 x / 1.40 x (a).  Said plainly: on the mix the call LOSES to the bare export + import; what it saves is the caller's own
+ * kernel on top of that route, the staging memory and two passes over f. */
+typedef struct mpdata_satadj_params {
+  double esw[9], desw[9]; /* liquid: es(x), d es / dT (x) as degree-8 polynomials in x, Horner from [8] down */
+  double esi[9], desi[9]; /* ice: the same; read only with MPDATA_SATADJ_ICE */
+  double t0, xmin;        /* x = T - t0;  x = (x > xmin) ? x : xmin */
+  double eps;             /* qs = (eps * es) / max(es, p - es) */
+  double lv, ls;          /* L / cp of condensation and of sublimation, in the unit of the temperature tracer */
+  double tmin, tmax;      /* the mixed-phase ramp, tmin < tmax; ICE only */
+  double tol;             /* Newton stops when |dT| <= tol ... */
+  int maxit;              /* ... or after maxit steps, 1 <= maxit <= 32 */
+} mpdata_satadj_params;
+#define MPDATA_SATADJ_ICE 1 /* mode bit: the ice curve below tmin and the linear ramp between tmin and tmax */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on
+ * the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_satadj_device(mpdata_plan* plan, int64_t sl0, int64_t n, int th, int tq, int tn, int tt, const void* pres,
+                              const void* gz, const mpdata_satadj_params* par, int mode, void* ncld, void* iters);
+/* host arrays, synchronous (the plan's block staging buffer, as the 3g - 3x host forms) */
+int mpdata_plan_satadj(mpdata_plan* plan, int64_t sl0, int64_t n, int th, int tq, int tn, int tt, const double* pres,
+                       const double* gz, const mpdata_satadj_params* par, int mode, double* ncld, double* iters);
+int mpdata_plan_satadj_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int th, int tq, int tn, int tt, const float* pres,
+                           const float* gz, const mpdata_satadj_params* par, int mode, float* ncld, float* iters);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm,ntracers) (leading
+ * dimension ncrms); pres, gz, ncld, iters as above (leading dimension n).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_satadj_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, int th, int tq, int tn,
+                         int tt, const double* pres, const double* gz, const mpdata_satadj_params* par, int mode, double* ncld,
+                         double* iters, void* stream);
+int mpdata_satadj_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int th, int tq, int tn,
+                             int tt, const float* pres, const float* gz, const mpdata_satadj_params* par, int mode, float* ncld,
+                             float* iters, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
