@@ -27,6 +27,7 @@ BOUNDARY_GIVEN, BOUNDARY_PERIODIC = 0, 1   # MPDATA_BOUNDARY_* (include/mpdata_h
 LEVEL_ADD, LEVEL_ADD_CLIP = 0, 1           # MPDATA_LEVEL_ADD* (include/mpdata_hip.h section 3i)
 CELL_ADD, CELL_ADD_CLIP = 0, 1             # MPDATA_CELL_ADD* (include/mpdata_hip.h section 3p)
 CONVERT_LIMIT = 1                          # MPDATA_CONVERT_LIMIT (include/mpdata_hip.h section 3t)
+COMBINE_CLIP, COMBINE_MAX = 1, 8            # MPDATA_COMBINE_* (include/mpdata_hip.h section 3z)
 SATADJ_ICE = 1                             # MPDATA_SATADJ_ICE (include/mpdata_hip.h section 3y)
 LEVEL_COV_RAW = 1                          # MPDATA_LEVEL_COV_RAW (include/mpdata_hip.h section 3u)
 
@@ -270,6 +271,15 @@ def lib():
         for name in ("mpdata_satadj_device", "mpdata_satadj_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, ci, ci, dp, dp, pp, ci, dp, dp, vp]
+        ip = ctypes.c_void_p                    # const int* src: a host array (_src_arg)
+        L.mpdata_plan_combine_device.restype = ci
+        L.mpdata_plan_combine_device.argtypes = [vp, i64, i64, ci, ci, ip, vp, vp, ci, vp]
+        for name in ("mpdata_plan_combine", "mpdata_plan_combine_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, ci, ip, dp, dp, ci, dp]
+        for name in ("mpdata_combine_device", "mpdata_combine_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, ip, dp, dp, ci, dp, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1200,6 +1210,35 @@ class Plan:
         _check(getattr(lib(), "mpdata_plan_convert" + self._sfx)(self._p, int(sl0), n, int(src), int(dst), ptrs["r"], ptrs["q0"],
                                                                  ptrs["y"], int(mode), ptrs["dsum"]))
 
+    def combine(self, dst, src, coef=None, c0=None, mode=0, sum=None, sl0=0, n=None):
+        """Linear combination of tracers in place (include/mpdata_hip.h 3z) on the interior columns of instances [sl0,
+        sl0+n) (default: the rest of the plan from sl0): f_dst = coef_0 * f_src[0] + coef_1 * f_src[1] + ... + c0, summed in
+        the order of src (any sequence of at most COMBINE_MAX ints; sources may repeat and may be dst, which is read old),
+        with mode COMBINE_CLIP followed by v = v > 0 ? v : +0; on the plan's stream (mpdata_plan_combine_device).
+        Reference-layout DEVICE tensors of the plan's precision, shapes combine_shapes(n, nx, nz, nsrc): coef (nsrc, nzm, n)
+        or None (no multiply: one source and no c0 is a bit copy); c0 (nzm, n) or None (required without a source); sum
+        (nzm, n) or None (skipped), the new row of dst summed over the interior columns.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        nsrc, srcp = _src_arg(src)
+        sh = combine_shapes(n, self.dims[1], self.dims[2], nsrc)
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("coef", coef), ("c0", c0), ("sum", sum))}
+        _check(lib().mpdata_plan_combine_device(self._p, int(sl0), n, int(dst), nsrc, srcp, P["coef"], P["c0"], int(mode), P["sum"]))
+
+    def combine_host(self, dst, src, coef=None, c0=None, mode=0, sum=None, sl0=0, n=None):
+        """The same from HOST arrays (numpy, Fortran order): coef (n, nzm, nsrc) or None, c0 (n, nzm) or None, sum (n, nzm)
+        or None (written), synchronous (mpdata_plan_combine[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        nsrc, srcp = _src_arg(src)
+        pc = None
+        if coef is not None:
+            pc = _host_ptr(coef, "coef", False, self._dt)
+            if tuple(coef.shape) != (n, nzm, nsrc):
+                raise MpdataError(-1, f"coef: shape {tuple(coef.shape)} != expected {(n, nzm, nsrc)}")
+        P = {name: None if a is None else self._block_host(a, name, (n, nzm), False, out) for name, a, out in (("c0", c0, False), ("sum", sum, True))}
+        _check(getattr(lib(), "mpdata_plan_combine" + self._sfx)(self._p, int(sl0), n, int(dst), nsrc, srcp, pc, P["c0"], int(mode),
+                                                                 P["sum"]))
+
     def level_cov(self, ta, tb, cov, ma=None, mb=None, mode=0, mean_a=None, mean_b=None, sl0=0, n=None):
         """Per-level covariance of tracers ta and tb (include/mpdata_hip.h 3u; ta == tb: the variance) over the interior
         columns of instances [sl0, sl0+n) (default: the rest of the plan from sl0): cov = the SUM over i of (a_i - m_a) *
@@ -1652,6 +1691,42 @@ def convert(f, src, dst, r, q0=None, y=None, mode=0, dsum=None, sl0=0, n=None, s
     P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("r", r), ("q0", q0), ("y", y), ("dsum", dsum))}
     fn = lib().mpdata_convert_device if f.dtype == torch.float64 else lib().mpdata_convert_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(src), int(dst), P["r"], P["q0"], P["y"], int(mode), P["dsum"],
+              _stream_handle(stream)))
+
+
+def _src_arg(src):
+    """the src argument of a combine call: any sequence of ints -> (nsrc, a C array of int or None for an empty one)"""
+    src = [int(t) for t in src]
+    return len(src), (ctypes.cast((ctypes.c_int * len(src))(*src), ctypes.c_void_p) if src else None)
+
+
+def combine_shapes(n, nx, nz, nsrc):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a combine call on n instances and nsrc
+    sources: coef (nsrc, nzm, n); c0, sum (nzm, n).  (nx is taken as the other shape functions take it; no array of the
+    call has a column axis.)"""
+    n, nx, nz, nsrc = int(n), int(nx), int(nz), int(nsrc)
+    return {"coef": (nsrc, nz - 1, n), "c0": (nz - 1, n), "sum": (nz - 1, n)}
+
+
+def combine(f, dst, src, coef=None, c0=None, mode=0, sum=None, sl0=0, n=None, stream=None):
+    """Linear combination of tracers (include/mpdata_hip.h 3z) of instances [sl0, sl0+n) (default: the rest from sl0) of a
+    reference-layout DEVICE tensor f (ntr, nzm, nx+6, ncrms), float64 or float32, in place: f_dst = coef_0 * f_src[0] + ... +
+    c0 on the interior columns, in the order of src (any sequence of at most COMBINE_MAX ints), with mode COMBINE_CLIP
+    clipped at zero; coef, c0, sum of the same dtype with the shapes of combine_shapes(n, nx, nz, nsrc) (each may be None;
+    c0 is required without a source).  Asynchronous on `stream` (mpdata_combine_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"combine: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() != 4 or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis")
+    nt, nzm, nxp6, ncrms = f.shape
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    nsrc, srcp = _src_arg(src)
+    sh = combine_shapes(n, nxp6 - 6, nzm + 1, nsrc)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("coef", coef), ("c0", c0), ("sum", sum))}
+    fn = lib().mpdata_combine_device if f.dtype == torch.float64 else lib().mpdata_combine_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(dst), nsrc, srcp, P["coef"], P["c0"], int(mode), P["sum"],
               _stream_handle(stream)))
 
 

@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3y).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_satadj.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3z).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_combine.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -7,6 +7,7 @@
 #include "mpdata_cell_add.h"
 #include "mpdata_column_path.h"
 #include "mpdata_column_step.h"
+#include "mpdata_combine.h"
 #include "mpdata_convert.h"
 #include "mpdata_courant.h"
 #include "mpdata_diffuse.h"
@@ -1783,6 +1784,97 @@ int mpdata_satadj_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_
                              const float* pres, const float* gz, const mpdata_satadj_params* par, int mode, float* ncld, float* iters,
                              void* stream) {
   return satadj_array(ncrms, nx, nz, ntracers, sl0, n, f, th, tq, tn, tt, pres, gz, par, mode, ncld, iters, stream, 4);
+}
+
+// ---- 3z: linear combination of tracers of f, in place: f(dst) = sum over j of coef_j * f(src_j) + c0 on the interior
+// columns, clipped at zero on request.  Reads coef and c0 and the sources, writes sum, rewrites the INTERIOR columns of
+// tracer dst of the block's instances; every other tracer (the sources that are not dst among them), flux, u, w, rho, rhow,
+// adz and the boundary mode are not touched and no event is recorded.  Halo marks, seam marks and the phantom: word for
+// word as 3t's (plan_convert), for the ONE written tracer dst; the marks of the sources are not touched -- the call reads
+// their interior columns and owned levels only, which are right whatever their halos and seams hold.
+static int plan_combine(mpdata_plan* p, int64_t sl0, int64_t n, int dst, int nsrc, const int* src, const void* coef, const void* c0,
+                        int mode, void* sum) {
+  const int clip = (mode & MPDATA_COMBINE_CLIP) != 0;
+  if (plan_walked(p)) {
+    MpdataCombineJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, 0, p->ntracers);
+    b.sel = block_sel(p, sl0, n);
+    b.dst = dst; b.nsrc = nsrc;
+    for (int q = 0; q < MPDATA_COMBINE_MAX; ++q) { b.src[q] = q < nsrc ? src[q] : dst; b.off[q] = 0; }
+    b.coef = coef; b.c0 = c0; b.clip = clip; b.sum = sum;
+    HIP_TRY(mpdata_combine_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_combine_ref(p->f, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, dst, nsrc, src, coef, c0, clip, sum, p->stream));
+  }
+  return plan_rewrote(p, sl0, n, dst, 1, SEAMS | HALOS);
+}
+// dst, the sources, c0 and the mode of a call, for the plan forms (ntracers of the plan) and the array forms alike
+static int combine_args(const char* what, int ntracers, int dst, int nsrc, const int* src, const void* c0, int mode) {
+  if (dst < 0 || dst >= ntracers) return set_err(MPDATA_EINVAL, "%s: dst %d outside the %d tracers", what, dst, ntracers);
+  if (nsrc < 0 || nsrc > MPDATA_COMBINE_MAX) return set_err(MPDATA_EINVAL, "%s: nsrc %d outside [0, %d]", what, nsrc, MPDATA_COMBINE_MAX);
+  if (nsrc > 0 && !src) return set_err(MPDATA_EINVAL, "%s: null src", what);
+  for (int j = 0; j < nsrc; ++j)
+    if (src[j] < 0 || src[j] >= ntracers)
+      return set_err(MPDATA_EINVAL, "%s: source %d (src[%d]) outside the %d tracers", what, src[j], j, ntracers);
+  if (nsrc == 0 && !c0) return set_err(MPDATA_EINVAL, "%s: null c0 with nsrc == 0", what);
+  if (mode & ~MPDATA_COMBINE_CLIP) return set_err(MPDATA_EINVAL, "%s: unknown mode bits %d", what, mode);
+  return 0;
+}
+static int plan_combine_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int dst, int nsrc, const int* src,
+                              const void* c0, int mode, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = combine_args(what, p->ntracers, dst, nsrc, src, c0, mode);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_combine_device(mpdata_plan* p, int64_t sl0, int64_t n, int dst, int nsrc, const int* src, const void* coef,
+                               const void* c0, int mode, void* sum) {
+  const int rc = plan_combine_check("mpdata_plan_combine_device", p, sl0, n, dst, nsrc, src, c0, mode, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_combine(p, sl0, n, dst, nsrc, src, coef, c0, mode, sum);
+}
+static int plan_combine_host(mpdata_plan* p, int64_t sl0, int64_t n, int dst, int nsrc, const int* src, const void* coef, const void* c0,
+                             int mode, void* sum, int eb) {
+  int rc = plan_combine_check("mpdata_plan_combine", p, sl0, n, dst, nsrc, src, c0, mode, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb;
+  HostArr a[3] = {{nsrc > 0 ? coef : nullptr, kb * nsrc, false}, {c0, kb, false}, {sum, kb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_combine(p, sl0, n, dst, nsrc, src, a[0].dev, a[1].dev, mode, a[2].dev);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_combine(mpdata_plan* p, int64_t sl0, int64_t n, int dst, int nsrc, const int* src, const double* coef, const double* c0,
+                        int mode, double* sum) {
+  return plan_combine_host(p, sl0, n, dst, nsrc, src, coef, c0, mode, sum, 8);
+}
+int mpdata_plan_combine_f32(mpdata_plan* p, int64_t sl0, int64_t n, int dst, int nsrc, const int* src, const float* coef,
+                            const float* c0, int mode, float* sum) {
+  return plan_combine_host(p, sl0, n, dst, nsrc, src, coef, c0, mode, sum, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): in place, asynchronous
+static int combine_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, int dst, int nsrc, const int* src,
+                         const void* coef, const void* c0, int mode, void* sum, void* stream, int eb) {
+  const char* const what = "mpdata_combine_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  rc = combine_args(what, ntracers, dst, nsrc, src, c0, mode);
+  if (rc) return rc;
+  HIP_TRY(mpdata_combine_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, dst, nsrc, src, coef, c0, (mode & MPDATA_COMBINE_CLIP) != 0, sum,
+                             (hipStream_t)stream));
+  return 0;
+}
+int mpdata_combine_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, int dst, int nsrc,
+                          const int* src, const double* coef, const double* c0, int mode, double* sum, void* stream) {
+  return combine_array(ncrms, nx, nz, ntracers, sl0, n, f, dst, nsrc, src, coef, c0, mode, sum, stream, 8);
+}
+int mpdata_combine_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int dst, int nsrc,
+                              const int* src, const float* coef, const float* c0, int mode, float* sum, void* stream) {
+  return combine_array(ncrms, nx, nz, ntracers, sl0, n, f, dst, nsrc, src, coef, c0, mode, sum, stream, 4);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
-// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3y:
-// the nineteen kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
+// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3z:
+// the twenty kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
 // mpdata_column_path.hip, mpdata_diffuse.hip, mpdata_subside.hip, mpdata_sediment.hip, mpdata_vsolve.hip, mpdata_cell_add.hip,
-// mpdata_column_step.hip, mpdata_relax.hip, mpdata_vdiffuse.hip, mpdata_convert.hip, mpdata_level_cov.hip, mpdata_level_cond.hip, mpdata_column_cond.hip, mpdata_nonneg.hip, mpdata_satadj.hip; their host side is mpdata_plan_blocks.hip): the selector of the block, the
+// mpdata_column_step.hip, mpdata_relax.hip, mpdata_vdiffuse.hip, mpdata_convert.hip, mpdata_level_cov.hip, mpdata_level_cond.hip, mpdata_column_cond.hip, mpdata_nonneg.hip, mpdata_satadj.hip, mpdata_combine.hip; their host side is mpdata_plan_blocks.hip): the selector of the block, the
 // element traits, and on the host side the tile grid, the column-group geometry of the seven kernels that stage columns
 // through LDS (col_groups_batched, col_groups_tiled), the LDS limit of a workgroup and the precision dispatch of the
 // reference-layout launches (ref_real).  The host side is free to share: a launcher fills its kernel's argument struct
@@ -24,7 +24,7 @@
 //   sl0, n, ncrms: the block and the plan's size in REAL instances.  Slots that are no instance of the block -- the
 //     padding of the last tile, the phantom half of an odd fp32 plan, the partner of a pair the block's ends split, a
 //     neighbour in the tile -- reach no output and keep their bits (the one exception: the phantom follows the last slot in the calls that
-//     rewrite the plan, mpdata_level_add.h, mpdata_scale_uw.h, mpdata_relax.h, mpdata_convert.h, mpdata_nonneg.h, mpdata_satadj.h).
+//     rewrite the plan, mpdata_level_add.h, mpdata_scale_uw.h, mpdata_relax.h, mpdata_convert.h, mpdata_nonneg.h, mpdata_satadj.h, mpdata_combine.h).
 //   ipe: reals per 8-byte element -- 1 (fp64), 2 (fp32 plans: pairs of adjacent instances)
 //   W = 1: the layout job describes the plan itself, nz = j.nlev + 1.
 //   W > 1: the layout job describes the INNER plan of a windowed plan (mpdata_windows.h): slot q = sl * W + h is window
@@ -35,7 +35,7 @@ struct MpdataBlockSel {
   int W, nz;
 };
 
-// everything below is for the nineteen kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
+// everything below is for the twenty kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
 // selector alone
 namespace wm_walk {
 

@@ -119,6 +119,13 @@ module mpdata_hip_mod
     real(c_double) :: tol               ! Newton stops when |dT| <= tol ...
     integer(c_int) :: maxit             ! ... or after maxit steps, 1 <= maxit <= 32
   end type
+  ! linear combinations of a resident plan's tracers, in place (include/mpdata_hip.h section 3z): all five entry points,
+  ! each bound by its literal name as 3y's are (tests/fortran/combine_calls.F90); src is c_loc of an integer(c_int) array
+  ! of the HOST in every form; they stand in the second interface block, behind 3y's
+  public :: mpdata_plan_combine_device_c, mpdata_plan_combine_c, mpdata_plan_combine_f32_c
+  public :: mpdata_combine_device_c, mpdata_combine_f32_device_c
+  integer(c_int), parameter, public :: MPDATA_COMBINE_CLIP = 1
+  integer(c_int), parameter, public :: MPDATA_COMBINE_MAX = 8
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
   ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
   ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
@@ -830,6 +837,73 @@ module mpdata_hip_mod
       type(c_ptr), value :: pres, gz, par
       integer(c_int), value :: mode
       type(c_ptr), value :: ncld, iters
+      type(c_ptr), value :: stream
+    end function
+    ! ---- linear combination of tracers in place (include/mpdata_hip.h section 3z; tracers counted from 0): on the interior
+    ! columns f_dst = coef(:,:,1) * f_src(1) + coef(:,:,2) * f_src(2) + ... + c0, summed in the order of src, the sources read
+    ! old also where one is dst; mode 0 or MPDATA_COMBINE_CLIP (v = v > 0 ? v : +0); src: c_loc of an integer(c_int) HOST
+    ! array of nsrc <= MPDATA_COMBINE_MAX tracers (c_null_ptr with nsrc = 0, which needs c0); coef(n, nzm, nsrc), c0(n, nzm),
+    ! sum(n, nzm) (each c_null_ptr: no multiply / nothing added / skipped); device arrays of the plan's precision,
+    ! asynchronous on the plan's stream; windowed plans are supported
+    ! (device arrays)
+    integer(c_int) function mpdata_plan_combine_device_c(plan, sl0, n, dst, nsrc, src, coef, c0, mode, sum) &
+        bind(C, name="mpdata_plan_combine_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: dst, nsrc
+      type(c_ptr), value :: src, coef, c0
+      integer(c_int), value :: mode
+      type(c_ptr), value :: sum
+    end function
+    ! host arrays (c_loc of real(c_double) arrays, or c_null_ptr), synchronous
+    integer(c_int) function mpdata_plan_combine_c(plan, sl0, n, dst, nsrc, src, coef, c0, mode, sum) &
+        bind(C, name="mpdata_plan_combine")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: dst, nsrc
+      type(c_ptr), value :: src, coef, c0
+      integer(c_int), value :: mode
+      type(c_ptr), value :: sum
+    end function
+    ! ... of real(c_float) arrays, for fp32 plans
+    integer(c_int) function mpdata_plan_combine_f32_c(plan, sl0, n, dst, nsrc, src, coef, c0, mode, sum) &
+        bind(C, name="mpdata_plan_combine_f32")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: dst, nsrc
+      type(c_ptr), value :: src, coef, c0
+      integer(c_int), value :: mode
+      type(c_ptr), value :: sum
+    end function
+    ! the same on instances [sl0, sl0 + n) of a reference-layout device array f of real(c_double), in place
+    integer(c_int) function mpdata_combine_device_c(ncrms, nx, nz, ntracers, sl0, n, f, dst, nsrc, src, coef, c0, mode, sum, stream) &
+        bind(C, name="mpdata_combine_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f
+      integer(c_int), value :: dst, nsrc
+      type(c_ptr), value :: src, coef, c0
+      integer(c_int), value :: mode
+      type(c_ptr), value :: sum
+      type(c_ptr), value :: stream
+    end function
+    ! ... of real(c_float)
+    integer(c_int) function mpdata_combine_f32_device_c(ncrms, nx, nz, ntracers, sl0, n, f, dst, nsrc, src, coef, c0, mode, sum, stream) &
+        bind(C, name="mpdata_combine_f32_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f
+      integer(c_int), value :: dst, nsrc
+      type(c_ptr), value :: src, coef, c0
+      integer(c_int), value :: mode
+      type(c_ptr), value :: sum
       type(c_ptr), value :: stream
     end function
   end interface

@@ -1687,6 +1687,90 @@ int mpdata_satadj_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_
                              int tt, const float* pres, const float* gz, const mpdata_satadj_params* par, int mode, float* ncld,
                              float* iters, void* stream);
 
+/* ---- 3z. Linear combinations of a resident plan's tracers, in place (what is left of a cloud model's scalar loop once 3t and
+ * 3y hold its microphysical state: the fields DERIVED from that state -- the buoyancy, a level-dependent linear combination
+ * of temperature, vapour, cloud and precipitating water plus a level constant; total water qt = qv + qn in front of 3y and
+ * qv = qt - qn behind it; liquid/ice static energy from T and the condensates; a snapshot of a tracer in front of a step and
+ * the tendency (f_new - f_old) / dt behind it; a tracer set to a profile; any a * x + b * y between tracers.  3t couples
+ * exactly two tracers by one fixed formula and every other call of 3g - 3y sees one tracer at a time; this one builds one
+ * tracer from a list).  This section is the specification; the reference tree has no such routine.  For one destination
+ * tracer dst and a list of nsrc source tracers src[0 .. nsrc-1] (a host array of int, read during the call), every instance
+ * sl in [sl0, sl0 + n) with b = sl - sl0, every level k = 1 .. nzm, nzm = nz - 1, and every INTERIOR column i = 1 .. nx, with
+ * x_j = f_old(i,k,src[j]) -- the OLD value also where src[j] == dst --, every statement below is rounded once in the plan's
+ * precision, in this association, with no contraction; comparisons are plain compare-and-select, never fmax / fmin:
+ *   nsrc >= 1:  v = coef ? coef(b,k,0) * x_0 : x_0
+ *               do j = 1, nsrc-1:  p = coef ? coef(b,k,j) * x_j : x_j ;  v = v + p
+ *               c0 given:  v = v + c0(b,k)
+ *   nsrc == 0:  v = c0(b,k)                                (c0 required)
+ *   mode & MPDATA_COMBINE_CLIP:  v = (v > 0) ? v : +0      (so NaN and -0 give +0)
+ *   f(i,k,dst) = v
+ *   sum(b,k):  s = +0; do i = 1, nx: s = s + v(i)          (NULL: skipped; the sum of 3g of the NEW dst row)
+ * coef (optional input, (n, nzm, nsrc), coef(b,k,j) at b + n * (k + nzm * j); NULL: no multiply at all -- with nsrc == 1 and
+ * no c0 the call is then a bit copy: every NaN payload and every -0.0 is preserved), c0 (optional input, (n, nzm)) and sum
+ * (optional output, (n, nzm)) are arrays of the plan's precision, reference layout, instance index fastest, leading
+ * dimension n (the block's first instance at index 0), as r of 3t.  nsrc lies in [0, MPDATA_COMBINE_MAX]; sources may
+ * repeat; dst may be among the sources (the in-place form, f_dst = 2 f_dst - f_t): all loads of a cell precede its store.
+ * Halo columns are neither read nor written.  A tracer other than dst keeps every bit.  EXACT and FAST plans give the same
+ * bits.  No byte outside the arrays is read or written.  Afterwards the plan behaves exactly as if the interior of dst had
+ * been exported, set as above and imported again.
+ * Towards the rest of a plan, for the one written tracer dst:
+ *   halo marks   only interior columns are read and written.  GIVEN plans: halos keep every bit.  PERIODIC plans: no wrap
+ *     is launched; the halo mark of dst is cleared afterwards, so the next run or read-back hands out wrapped halos of the
+ *     new field.  The sources' marks are not touched.
+ *   windowed plans (3e, nz > 238) are supported, as in 3t: the operator is pointwise, the call reads and writes OWNED levels
+ *     only, each with coef and c0 of the tall level it stands for, needs no seam refresh in front and clears the seam mark
+ *     of dst afterwards; sum of a level is written by that level's owner.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 in dst whenever the block holds it (on a windowed plan
+ *     the phantom of the inner plan is restored behind the call, as in 3t).
+ *   untouched    an fp32 block that splits a pair stores the partner back as loaded: a -0.0 there stays; padding slots,
+ *     neighbours in a tile, instances outside the block, every other tracer, flux, u, w, rho, rhow, adz, the held-velocity
+ *     flags, the boundary mode and the timing pair keep every bit.  The call is outside the run's event pair; the plan need
+ *     not hold velocities.
+ * A kernel of its own on every kind of plan (mpdata_combine.hip), not fused into the run.  Wave-major and windowed plans: the
+ * lane-owned walk of 3t with 1 + nsrc streams: the dst tracer is the base and every source lies at a signed 64-bit offset from
+ * it; the kernel is a template on nsrc, with 8 columns in flight per source for 0 to 2 sources, 4 for 3 and 4, and for 5
+ * to 8 sources 3 on fp64 and 2 on fp32 plans (8 to 24 loads in flight per lane; no kernel above 128 VGPRs, none with scratch).  coef and c0 are in registers, sum is
+ * lane-local in column order: no LDS, no barrier, no cross-lane traffic.  nsrc == 0 loads nothing from f; a wave none of whose
+ * elements lies in the block loads and stores nothing.  Reference-layout plans and the array forms: one thread per instance
+ * and level row, one loop over i, in place.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan; n < 1 or a range outside [0, ncrms); dst outside [0, ntracers); nsrc outside
+ * [0, MPDATA_COMBINE_MAX]; nsrc > 0 with a null src; a src[j] outside [0, ntracers); nsrc == 0 with a null c0; a mode bit other
+ * than MPDATA_COMBINE_CLIP; in the array forms bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays,
+ * a null f, then dst, nsrc, src, c0 and the mode as above.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3y (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md AJ, tools/combine_bench.py, profiles/combine_bench.json), 65536 x 32 x 28, nine tracers,
+ * cold, nsrc = 0 / 1 / 2 / 4 / 8 distinct sources with coef, c0 and sum: 0.121 / 0.214 / 0.307 / 0.507 / 0.894 ms fp64, 0.054 / 0.109 /
+ * 0.152 / 0.261 / 0.474 ms fp32 -- 3.7 / 4.2 / 4.4 / 4.5 / 4.6 TB/s fp64 of the algorithmic bytes (the interior of nsrc tracers read and
+ * one written); without coef, c0 and sum 1 % to 10 % less (the copy: 0.203 / 0.099 ms).  Against existing calls in the same run:
+ * (a) 0.60 x / 0.51 x / 0.50 x / 0.49 x / 0.48 x fp64 and 0.50 x to 0.46 x fp32 mpdata_plan_export_device of the nsrc sources +
+ * mpdata_plan_import_device of dst (the old route without the caller's kernel); (b) nsrc = 1: 0.97 x fp64, 0.90 x fp32 one
+ * mpdata_plan_level_add_device; (c) nsrc = 2: 0.75 x mpdata_plan_convert_device with r alone, which writes one tracer more.  The
+ * in-place form costs 3 % to 6 % more.  A block of 64 instances, 8 sources: 0.013 / 0.019 ms.  Tall plans, 4096 x 32 x 300 (6
+ * windows): 0.107 / 0.187 / 0.255 / 0.396 / 0.659 ms fp64, 0.079 / 0.107 / 0.142 / 0.220 / 0.380 ms fp32, 0.54 x to 0.44 x and 0.49 x to
+ * 0.29 x (a).  Said plainly: on tall plans one source LOSES to level_add (1.23 x fp64, 1.27 x fp32), and the write-only form
+ * nsrc = 0 is the slowest per byte (2.0 to 2.9 TB/s there).  Columns in flight, timed per class on libraries of their own: 8 / 4
+ * are the fastest or within 1 % for 0 to 4 sources; for 5 to 8 sources 3 beat 2 by 3.9 % in fp64 and lose by 1.5 % in fp32, which
+ * is what is kept -- differences that two processes of one session do not resolve (identical kernels differ by up to 3 %). */
+#define MPDATA_COMBINE_CLIP 1 /* mode bit: v = (v > 0) ? v : +0 in front of the store */
+#define MPDATA_COMBINE_MAX 8  /* the sources of one call at most */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  src: a HOST array of nsrc ints in every form.
+ * Device arrays of the plan's precision on the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_combine_device(mpdata_plan* plan, int64_t sl0, int64_t n, int dst, int nsrc, const int* src, const void* coef,
+                               const void* c0, int mode, void* sum);
+/* host arrays, synchronous (the plan's block staging buffer, as the 3g - 3y host forms) */
+int mpdata_plan_combine(mpdata_plan* plan, int64_t sl0, int64_t n, int dst, int nsrc, const int* src, const double* coef,
+                        const double* c0, int mode, double* sum);
+int mpdata_plan_combine_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int dst, int nsrc, const int* src, const float* coef,
+                            const float* c0, int mode, float* sum);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm,ntracers) (leading
+ * dimension ncrms); coef, c0, sum as above (leading dimension n).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_combine_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, int dst, int nsrc,
+                          const int* src, const double* coef, const double* c0, int mode, double* sum, void* stream);
+int mpdata_combine_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int dst, int nsrc,
+                              const int* src, const float* coef, const float* c0, int mode, float* sum, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
