@@ -28,6 +28,7 @@ LEVEL_ADD, LEVEL_ADD_CLIP = 0, 1           # MPDATA_LEVEL_ADD* (include/mpdata_h
 CELL_ADD, CELL_ADD_CLIP = 0, 1             # MPDATA_CELL_ADD* (include/mpdata_hip.h section 3p)
 CONVERT_LIMIT = 1                          # MPDATA_CONVERT_LIMIT (include/mpdata_hip.h section 3t)
 COMBINE_CLIP, COMBINE_MAX = 1, 8            # MPDATA_COMBINE_* (include/mpdata_hip.h section 3z)
+COLUMN_SCAN_DOWN, COLUMN_SCAN_EXCLUSIVE = 1, 2   # MPDATA_COLUMN_SCAN_* (include/mpdata_hip.h section 3aa)
 SATADJ_ICE = 1                             # MPDATA_SATADJ_ICE (include/mpdata_hip.h section 3y)
 LEVEL_COV_RAW = 1                          # MPDATA_LEVEL_COV_RAW (include/mpdata_hip.h section 3u)
 
@@ -280,6 +281,14 @@ def lib():
         for name in ("mpdata_combine_device", "mpdata_combine_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, ip, dp, dp, ci, dp, vp]
+        L.mpdata_plan_column_scan_device.restype = ci
+        L.mpdata_plan_column_scan_device.argtypes = [vp, i64, i64, ci, ci, vp, vp, ci]
+        for name in ("mpdata_plan_column_scan", "mpdata_plan_column_scan_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, ci, dp, dp, ci]
+        for name in ("mpdata_column_scan_device", "mpdata_column_scan_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, dp, dp, ci, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1239,6 +1248,27 @@ class Plan:
         _check(getattr(lib(), "mpdata_plan_combine" + self._sfx)(self._p, int(sl0), n, int(dst), nsrc, srcp, pc, P["c0"], int(mode),
                                                                  P["sum"]))
 
+    def column_scan(self, src, dst, wgt=None, total=None, mode=0, sl0=0, n=None):
+        """Running column integral of tracer src into tracer dst, in place (include/mpdata_hip.h 3aa), on the interior columns
+        of instances [sl0, sl0+n) (default: the rest of the plan from sl0): p(k) = wgt(k) * f(k, src), s summed from the
+        surface upward (mode COLUMN_SCAN_DOWN: from the top downward), f(k, dst) = s including p(k) (COLUMN_SCAN_EXCLUSIVE:
+        in front of it); dst == src is the in-place form; on the plan's stream (mpdata_plan_column_scan_device).
+        Reference-layout DEVICE tensors of the plan's precision, shapes column_scan_shapes(n, nx, nz): wgt (nzm, n) or None
+        (rho * adz of the plan, as column_path); total (nx, n) or None (skipped), the final s.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        sh = column_scan_shapes(n, self.dims[1], self.dims[2])
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("wgt", wgt), ("total", total))}
+        _check(lib().mpdata_plan_column_scan_device(self._p, int(sl0), n, int(src), int(dst), P["wgt"], P["total"], int(mode)))
+
+    def column_scan_host(self, src, dst, wgt=None, total=None, mode=0, sl0=0, n=None):
+        """The same from HOST arrays (numpy, Fortran order): wgt (n, nzm) or None, total (n, nx) or None (written),
+        synchronous (mpdata_plan_column_scan[_f32])."""
+        n = self._block_n(sl0, n)
+        P = {name: None if a is None else self._block_host(a, name, want, False, out)
+             for name, a, want, out in (("wgt", wgt, (n, self.dims[2] - 1), False), ("total", total, (n, self.dims[1]), True))}
+        _check(getattr(lib(), "mpdata_plan_column_scan" + self._sfx)(self._p, int(sl0), n, int(src), int(dst), P["wgt"], P["total"],
+                                                                     int(mode)))
+
     def level_cov(self, ta, tb, cov, ma=None, mb=None, mode=0, mean_a=None, mean_b=None, sl0=0, n=None):
         """Per-level covariance of tracers ta and tb (include/mpdata_hip.h 3u; ta == tb: the variance) over the interior
         columns of instances [sl0, sl0+n) (default: the rest of the plan from sl0): cov = the SUM over i of (a_i - m_a) *
@@ -1728,6 +1758,33 @@ def combine(f, dst, src, coef=None, c0=None, mode=0, sum=None, sl0=0, n=None, st
     fn = lib().mpdata_combine_device if f.dtype == torch.float64 else lib().mpdata_combine_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(dst), nsrc, srcp, P["coef"], P["c0"], int(mode), P["sum"],
               _stream_handle(stream)))
+
+
+def column_scan_shapes(n, nx, nz):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a column_scan call on n instances: wgt
+    (nzm, n), total (nx, n)."""
+    n, nx, nz = int(n), int(nx), int(nz)
+    return {"wgt": (nz - 1, n), "total": (nx, n)}
+
+
+def column_scan(f, src, dst, wgt, total=None, mode=0, sl0=0, n=None, stream=None):
+    """Running column integral (include/mpdata_hip.h 3aa) of tracer src into tracer dst of instances [sl0, sl0+n) (default:
+    the rest from sl0) of a reference-layout DEVICE tensor f (ntr, nzm, nx+6, ncrms), float64 or float32, in place: f(k, dst)
+    = the sum of wgt * f(src) from the surface up to k (mode COLUMN_SCAN_DOWN: from the top down to it; COLUMN_SCAN_EXCLUSIVE:
+    without level k itself) on the interior columns; wgt (required) and total (or None) of the same dtype with the shapes of
+    column_scan_shapes(n, nx, nz).  Asynchronous on `stream` (mpdata_column_scan_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"column_scan: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() != 4 or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis")
+    nt, nzm, nxp6, ncrms = f.shape
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    sh = column_scan_shapes(n, nxp6 - 6, nzm + 1)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("wgt", wgt), ("total", total))}
+    fn = lib().mpdata_column_scan_device if f.dtype == torch.float64 else lib().mpdata_column_scan_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(src), int(dst), P["wgt"], P["total"], int(mode), _stream_handle(stream)))
 
 
 def level_cov_shapes(n, nx, nz):

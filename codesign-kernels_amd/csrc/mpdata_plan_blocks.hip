@@ -1,11 +1,12 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3z).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_combine.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3aa).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_column_scan.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
 
 #include "mpdata_cell_add.h"
 #include "mpdata_column_path.h"
+#include "mpdata_column_scan.h"
 #include "mpdata_column_step.h"
 #include "mpdata_combine.h"
 #include "mpdata_convert.h"
@@ -1875,6 +1876,88 @@ int mpdata_combine_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t s
 int mpdata_combine_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int dst, int nsrc,
                               const int* src, const float* coef, const float* c0, int mode, float* sum, void* stream) {
   return combine_array(ncrms, nx, nz, ntracers, sl0, n, f, dst, nsrc, src, coef, c0, mode, sum, stream, 4);
+}
+
+// ---- 3aa: running column integral of tracer src into tracer dst, in place: o(k) = the sum of wgt * f(src) from the surface
+// up to k (or from the top down to it), f(dst) = o on the interior columns, total = the final sum per column.  Reads wgt (or
+// the plan's rho and adz) and the interior of src, writes total, rewrites the INTERIOR columns of tracer dst of the block's
+// instances; every other tracer (src where it is not dst among them), flux, u, w, rho, rhow, adz and the boundary mode are
+// not touched and no event is recorded.  Halo marks, seam marks and the phantom: word for word as 3z's (plan_combine), for
+// the ONE written tracer dst; the marks of src are not touched -- the call reads its interior columns and owned levels
+// only, which are right whatever its halos and seams hold.  The velocities are not looked at.
+static int plan_column_scan(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const void* wgt, void* total, int mode) {
+  if (plan_walked(p)) {
+    const mpdata_plan* q = wm_plan(p);
+    MpdataColumnScanJob b;
+    b.j = wm_job(q, 0, nullptr, src, 1);
+    kc_rho_adz(q, b);
+    b.sel = block_sel(p, sl0, n);
+    b.doff = (long long)(dst - src) * b.j.prv_tstride;
+    b.wgt = wgt; b.total = total; b.mode = mode;
+    HIP_TRY(mpdata_column_scan_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_column_scan_ref(p->f, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, src, dst, wgt, p->rho, p->adz, total, mode,
+                                   p->stream));
+  }
+  return plan_rewrote(p, sl0, n, dst, 1, SEAMS | HALOS);
+}
+// src, dst and the mode of a call, for the plan forms (ntracers of the plan) and the array forms alike
+static int column_scan_args(const char* what, int ntracers, int src, int dst, int mode) {
+  if (src < 0 || src >= ntracers) return set_err(MPDATA_EINVAL, "%s: src %d outside the %d tracers", what, src, ntracers);
+  if (dst < 0 || dst >= ntracers) return set_err(MPDATA_EINVAL, "%s: dst %d outside the %d tracers", what, dst, ntracers);
+  if (mode & ~(MPDATA_COLUMN_SCAN_DOWN | MPDATA_COLUMN_SCAN_EXCLUSIVE)) return set_err(MPDATA_EINVAL, "%s: unknown mode bits %d", what, mode);
+  return 0;
+}
+static int plan_column_scan_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, int mode, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = column_scan_args(what, p->ntracers, src, dst, mode);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_column_scan_device(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const void* wgt, void* total, int mode) {
+  const int rc = plan_column_scan_check("mpdata_plan_column_scan_device", p, sl0, n, src, dst, mode, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_column_scan(p, sl0, n, src, dst, wgt, total, mode);
+}
+static int plan_column_scan_host(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const void* wgt, void* total, int mode, int eb) {
+  int rc = plan_column_scan_check("mpdata_plan_column_scan", p, sl0, n, src, dst, mode, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  HostArr a[2] = {{wgt, (size_t)n * (p->nz - 1) * eb, false}, {total, (size_t)n * p->nx * eb, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_column_scan(p, sl0, n, src, dst, a[0].dev, a[1].dev, mode);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_column_scan(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const double* wgt, double* total, int mode) {
+  return plan_column_scan_host(p, sl0, n, src, dst, wgt, total, mode, 8);
+}
+int mpdata_plan_column_scan_f32(mpdata_plan* p, int64_t sl0, int64_t n, int src, int dst, const float* wgt, float* total, int mode) {
+  return plan_column_scan_host(p, sl0, n, src, dst, wgt, total, mode, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): in place, asynchronous; wgt is
+// required -- the arrays have no rho and adz
+static int column_scan_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, void* f, int src, int dst, const void* wgt,
+                             void* total, int mode, void* stream, int eb) {
+  const char* const what = "mpdata_column_scan_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  if (!wgt) return set_err(MPDATA_EINVAL, "%s: null wgt", what);
+  rc = column_scan_args(what, ntracers, src, dst, mode);
+  if (rc) return rc;
+  HIP_TRY(mpdata_column_scan_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, src, dst, wgt, nullptr, nullptr, total, mode, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_column_scan_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, int src, int dst,
+                              const double* wgt, double* total, int mode, void* stream) {
+  return column_scan_array(ncrms, nx, nz, ntracers, sl0, n, f, src, dst, wgt, total, mode, stream, 8);
+}
+int mpdata_column_scan_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int src, int dst,
+                                  const float* wgt, float* total, int mode, void* stream) {
+  return column_scan_array(ncrms, nx, nz, ntracers, sl0, n, f, src, dst, wgt, total, mode, stream, 4);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
-// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3z:
-// the twenty kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
+// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3aa:
+// the twenty-one kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
 // mpdata_column_path.hip, mpdata_diffuse.hip, mpdata_subside.hip, mpdata_sediment.hip, mpdata_vsolve.hip, mpdata_cell_add.hip,
-// mpdata_column_step.hip, mpdata_relax.hip, mpdata_vdiffuse.hip, mpdata_convert.hip, mpdata_level_cov.hip, mpdata_level_cond.hip, mpdata_column_cond.hip, mpdata_nonneg.hip, mpdata_satadj.hip, mpdata_combine.hip; their host side is mpdata_plan_blocks.hip): the selector of the block, the
-// element traits, and on the host side the tile grid, the column-group geometry of the seven kernels that stage columns
+// mpdata_column_step.hip, mpdata_relax.hip, mpdata_vdiffuse.hip, mpdata_convert.hip, mpdata_level_cov.hip, mpdata_level_cond.hip, mpdata_column_cond.hip, mpdata_nonneg.hip, mpdata_satadj.hip, mpdata_combine.hip, mpdata_column_scan.hip; their host side is mpdata_plan_blocks.hip): the selector of the block, the
+// element traits, and on the host side the tile grid, the column-group geometry of the eight kernels that stage columns
 // through LDS (col_groups_batched, col_groups_tiled), the LDS limit of a workgroup and the precision dispatch of the
 // reference-layout launches (ref_real).  The host side is free to share: a launcher fills its kernel's argument struct
 // from the result and the kernel is compiled as before.  Each of those files still keeps its kernel whole -- the map
@@ -24,7 +24,7 @@
 //   sl0, n, ncrms: the block and the plan's size in REAL instances.  Slots that are no instance of the block -- the
 //     padding of the last tile, the phantom half of an odd fp32 plan, the partner of a pair the block's ends split, a
 //     neighbour in the tile -- reach no output and keep their bits (the one exception: the phantom follows the last slot in the calls that
-//     rewrite the plan, mpdata_level_add.h, mpdata_scale_uw.h, mpdata_relax.h, mpdata_convert.h, mpdata_nonneg.h, mpdata_satadj.h, mpdata_combine.h).
+//     rewrite the plan, mpdata_level_add.h, mpdata_scale_uw.h, mpdata_relax.h, mpdata_convert.h, mpdata_nonneg.h, mpdata_satadj.h, mpdata_combine.h, mpdata_column_scan.h).
 //   ipe: reals per 8-byte element -- 1 (fp64), 2 (fp32 plans: pairs of adjacent instances)
 //   W = 1: the layout job describes the plan itself, nz = j.nlev + 1.
 //   W > 1: the layout job describes the INNER plan of a windowed plan (mpdata_windows.h): slot q = sl * W + h is window
@@ -35,7 +35,7 @@ struct MpdataBlockSel {
   int W, nz;
 };
 
-// everything below is for the twenty kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
+// everything below is for the twenty-one kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
 // selector alone
 namespace wm_walk {
 
@@ -110,7 +110,7 @@ inline hipError_t ref_real(const int elem_bytes, F&& launch) {
 }
 
 // ---- column groups: the workgroups of the kernels that stage whole columns of a group of instances through LDS
-// (mpdata_column_path.hip, mpdata_vsolve.hip, mpdata_column_step.hip, mpdata_vdiffuse.hip, mpdata_column_cond.hip: columns in batches; mpdata_sediment.hip,
+// (mpdata_column_path.hip, mpdata_vsolve.hip, mpdata_column_step.hip, mpdata_vdiffuse.hip, mpdata_column_cond.hip, mpdata_column_scan.hip: columns in batches; mpdata_sediment.hip,
 // mpdata_cell_add.hip: CB columns in flight, a tile per wave).  A UNIT is one 8-byte element of the instance axis (an
 // instance, or the pair 2 * ue, 2 * ue + 1 of an fp32 plan): slot ue % slp of tile ue / slp, or, in a windowed plan, the
 // tiles ue * W .. ue * W + W - 1.  A workgroup takes UG adjacent units (a power of two, a multiple of slp) and CB
@@ -128,7 +128,7 @@ struct ColGroups {
   long long lds_e;          // 8-byte elements of LDS of the launch
 };
 
-// the result into the fields all seven argument structs have (g0, ngroup: int; long long in column_path's)
+// the result into the fields all eight argument structs have (g0, ngroup: int; long long in column_path's)
 template <typename Args>
 inline void col_groups_fill(const ColGroups& c, Args* a) {
   a->UG = c.UG; a->CB = c.CB; a->ns = c.ns;
@@ -137,7 +137,7 @@ inline void col_groups_fill(const ColGroups& c, Args* a) {
 
 // what the two rules share, behind UG, CB, ncb and lds_e: the groups the block's tiles touch and the union of the
 // launchers' guards.  unit_mul: what the kernel multiplies a unit by in int arithmetic -- 1, W where it forms tiles of a
-// windowed plan from units (mpdata_vsolve.hip), 0 where it counts units in long long (mpdata_column_path.hip, mpdata_column_cond.hip: their groups
+// windowed plan from units (mpdata_vsolve.hip, mpdata_column_scan.hip), 0 where it counts units in long long (mpdata_column_path.hip, mpdata_column_cond.hip: their groups
 // may lie beyond 2^31 units, and it goes on running such a plan).
 //   UG is a power of two: it starts at 16 or 4 * slp and halves, and slp is 1, 2, 4 or 8 in every plan mpdata_plan_create
 //     makes (64 / LPS; 1 above 64 levels and in the inner plan of a windowed one), so the test refuses no plan of the

@@ -126,6 +126,13 @@ module mpdata_hip_mod
   public :: mpdata_combine_device_c, mpdata_combine_f32_device_c
   integer(c_int), parameter, public :: MPDATA_COMBINE_CLIP = 1
   integer(c_int), parameter, public :: MPDATA_COMBINE_MAX = 8
+  ! running column integrals of a resident plan's tracers, in place (include/mpdata_hip.h section 3aa): all five entry
+  ! points, each bound by its literal name as 3z's are (tests/fortran/column_scan_calls.F90); they stand in the second
+  ! interface block, behind 3z's
+  public :: mpdata_plan_column_scan_device_c, mpdata_plan_column_scan_c, mpdata_plan_column_scan_f32_c
+  public :: mpdata_column_scan_device_c, mpdata_column_scan_f32_device_c
+  integer(c_int), parameter, public :: MPDATA_COLUMN_SCAN_DOWN = 1
+  integer(c_int), parameter, public :: MPDATA_COLUMN_SCAN_EXCLUSIVE = 2
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
   ! section 3s): the device form only, one binding for both precisions as for 3o, next to it in the first interface block;
   ! mpdata_plan_vdiffuse[_f32] and mpdata_vdiffuse[_f32]_device have no Fortran interface yet
@@ -904,6 +911,67 @@ module mpdata_hip_mod
       type(c_ptr), value :: src, coef, c0
       integer(c_int), value :: mode
       type(c_ptr), value :: sum
+      type(c_ptr), value :: stream
+    end function
+    ! ---- running column integral of tracer src into tracer dst, in place (include/mpdata_hip.h section 3aa; tracers counted
+    ! from 0): on the interior columns p(k) = wgt(k) * f(k, src), s summed from the surface upward (mode
+    ! MPDATA_COLUMN_SCAN_DOWN: from the top downward), f(k, dst) = s with p(k) (MPDATA_COLUMN_SCAN_EXCLUSIVE: without it),
+    ! total = the final s; wgt(n, nzm) (c_null_ptr: rho * adz of the plan), total(n, nx) (c_null_ptr: skipped); device arrays
+    ! of the plan's precision, asynchronous on the plan's stream; windowed plans are supported
+    ! (device arrays)
+    integer(c_int) function mpdata_plan_column_scan_device_c(plan, sl0, n, src, dst, wgt, total, mode) &
+        bind(C, name="mpdata_plan_column_scan_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: src, dst
+      type(c_ptr), value :: wgt, total
+      integer(c_int), value :: mode
+    end function
+    ! host arrays (c_loc of real(c_double) arrays, or c_null_ptr), synchronous
+    integer(c_int) function mpdata_plan_column_scan_c(plan, sl0, n, src, dst, wgt, total, mode) &
+        bind(C, name="mpdata_plan_column_scan")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: src, dst
+      type(c_ptr), value :: wgt, total
+      integer(c_int), value :: mode
+    end function
+    ! ... of real(c_float) arrays, for fp32 plans
+    integer(c_int) function mpdata_plan_column_scan_f32_c(plan, sl0, n, src, dst, wgt, total, mode) &
+        bind(C, name="mpdata_plan_column_scan_f32")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: src, dst
+      type(c_ptr), value :: wgt, total
+      integer(c_int), value :: mode
+    end function
+    ! the same on instances [sl0, sl0 + n) of a reference-layout device array f of real(c_double), in place; wgt is required
+    integer(c_int) function mpdata_column_scan_device_c(ncrms, nx, nz, ntracers, sl0, n, f, src, dst, wgt, total, mode, stream) &
+        bind(C, name="mpdata_column_scan_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f
+      integer(c_int), value :: src, dst
+      type(c_ptr), value :: wgt, total
+      integer(c_int), value :: mode
+      type(c_ptr), value :: stream
+    end function
+    ! ... of real(c_float)
+    integer(c_int) function mpdata_column_scan_f32_device_c(ncrms, nx, nz, ntracers, sl0, n, f, src, dst, wgt, total, mode, stream) &
+        bind(C, name="mpdata_column_scan_f32_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f
+      integer(c_int), value :: src, dst
+      type(c_ptr), value :: wgt, total
+      integer(c_int), value :: mode
       type(c_ptr), value :: stream
     end function
   end interface

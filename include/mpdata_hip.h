@@ -1771,6 +1771,90 @@ int mpdata_combine_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t s
 int mpdata_combine_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int dst, int nsrc,
                               const int* src, const float* coef, const float* c0, int mode, float* sum, void* stream);
 
+/* ---- 3aa. Running column integrals of a resident plan's tracers, in place (the calls along the levels of 3g - 3z either
+ * reduce a column to one number, 3k and 3w, or solve a recurrence in it, 3o, 3q and 3s; none hands out the RUNNING integral,
+ * the value at every level of the sum from the surface up to it or from the model top down to it: the water above each level
+ * that a radiation or overlap scheme reads, the hydrostatic pressure perturbation that belongs to the buoyancy 3z builds,
+ * integrated downward, the cumulative flux of a column of sources or sinks, which 3n offers for its own wp * f only).  This
+ * section is the specification; the reference tree has no such routine.  For a source tracer src and a destination tracer
+ * dst, every instance sl in [sl0, sl0 + n) with b = sl - sl0 and every INTERIOR column i = 1 .. nx, with nzm = nz - 1,
+ * everything in the plan's precision, every statement below one rounded operation, with no contraction, every f the value
+ * before the call:
+ *   p(k) = wgt(b,k) * f(sl,i,k,src)                       the product rounded; no fma
+ *   UP (default):  s = +0.0;  k = 1 .. nzm
+ *   DOWN:          s = +0.0;  k = nzm .. 1
+ *      inclusive (default):  s = s + p(k);  o(k) = s
+ *      EXCLUSIVE:            o(k) = s;      s = s + p(k)
+ *   f(sl,i,k,dst) = o(k);     total(b,i) = the final s
+ * mode is an OR of MPDATA_COLUMN_SCAN_DOWN and MPDATA_COLUMN_SCAN_EXCLUSIVE.  wgt (optional input, (n, nzm), wgt(b,k) at
+ * b + n * (k - 1)) and total (optional output, (n, nx), total(b,i) at b + n * (i - 1)) are arrays of the plan's precision,
+ * reference layout, instance index fastest, leading dimension n (the block's first instance at index 0); on a windowed plan
+ * wgt is addressed by the TALL level.  wgt NULL: the weight is rho(sl,k) * adz(sl,k), one rounded multiply, exactly as 3k
+ * forms it (on a windowed plan each window uses its own rho and adz); total then has, with UP and in either inclusion
+ * mode, the bits of 3k's path.  total NULL: skipped.  dst == src is allowed and means in place.  With dst != src the source
+ * keeps every bit, and so does every other tracer.  The first o of an EXCLUSIVE scan is +0.0.  EXACT and FAST plans give the
+ * same bits.  NaN and infinities are outside the contract, as in 3k.  No byte outside the arrays is read or written.
+ * Afterwards the plan behaves exactly as if the interior of src had been exported, scanned as above and imported into dst.
+ * Towards the rest of a plan, for the one written tracer dst:
+ *   halo marks   only interior columns of dst are written, and halo columns are never read.  GIVEN plans: dst's halos keep
+ *     every bit.  PERIODIC plans: no wrap is launched in front; only the halo mark of dst is cleared afterwards, so the next
+ *     run or read-back hands out wrapped halos of the new field.  The mark of src is not touched.
+ *   windowed plans (3e, nz > 238 with tall columns on) are supported: the call reads and writes OWNED levels only, which
+ *     are right whatever the seams hold, so there is no seam refresh in front; only the seam mark of dst is cleared
+ *     afterwards.  UP walks the windows upward and DOWN walks them downward, the running s carried in registers: the merged
+ *     result is the tall scan bit for bit, and f is read once and written once on every kind of plan.
+ *   odd fp32 plans (3f)  the phantom half follows instance ncrms - 1 in dst whenever the block holds it (on a windowed plan
+ *     the phantom of the inner plan is restored behind the call, as in 3m - 3o).
+ *   untouched    an fp32 block that splits a pair stores the partner's half of dst back as loaded: a -0.0 there stays;
+ *     padding slots, neighbours in a tile, instances outside the block, every other tracer, flux, u, w, rho, rhow, adz, the
+ *     held-velocity flags, the boundary mode and the timing pair keep every bit.  The call is outside the run's event pair;
+ *     the plan need not hold velocities.
+ * A kernel of its own on every kind of plan (mpdata_column_scan.hip), not fused into the run.  Wave-major and windowed
+ * plans: the staging of 3k and 3o.  A workgroup copies the column slots of 16 adjacent 8-byte instance elements (fewer where
+ * the levels would not fit the 40 KiB of LDS those kernels keep) and a batch of columns of src through LDS as linear
+ * streams, the weight row with them; a lane per (instance element, column) sweeps its column in LDS in place, sequential
+ * in k, and stores total; the waves store LDS to dst's slots, at a signed 64-bit offset from src's, as the same linear
+ * streams.  Every global load of a batch precedes a barrier and every global store follows the sweep's barrier; workgroups
+ * own disjoint elements.  Direction and inclusion are uniform values of the launch: one copy of the staging
+ * code.  No reduction or scan across lanes.  Reference-layout plans and the array forms: one thread per instance and column
+ * owns its column, 64-bit offsets.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan; n < 1 or a range outside [0, ncrms); src, then dst outside [0, ntracers); a mode bit other than
+ * the two above; in the array forms bad sizes (ncrms < 1, nx < 1, nz < 2, ntracers < 1), a block outside the arrays, a null
+ * f, then a null wgt, then src, dst and the mode as above.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3z (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md AK, tools/column_scan_bench.py, profiles/column_scan_bench.json): 65536 x 32 x 28,
+ * three tracers, cold, tracer 0 into tracer 1 with wgt and total, the median of five rounds: 0.215 ms fp64, 0.115 ms fp32 in
+ * each of the four modes -- 4.2 / 3.9 TB/s of the algorithmic bytes (the interior of one tracer read and one written); in
+ * place 0.226 / 0.112 ms; without wgt and total the same (0.216 / 0.115 ms).  Against existing calls in the same run on the same
+ * plans: (a) 0.81 x fp64, 0.70 x fp32 mpdata_plan_vsolve_device (the same staging, two sweeps, a factor kernel); (b) 1.57 x /
+ * 1.55 x mpdata_plan_column_path_device of one tracer (the same staging, read only: the price of the stores); (c) 0.89 x /
+ * 0.95 x one mpdata_plan_level_add_device (the same bytes and the halo columns on top, no staging; in fp32 level_add's own
+ * rounds spread by 6 %, so that ratio is unresolved); (d) 0.49 x / 0.51 x mpdata_plan_export_device +
+ * mpdata_plan_import_device of the tracer (the old route without the caller's kernel).  Tall plans, 4096 x 32 x 300 (6
+ * windows): 0.244 / 0.156 ms (2.6 / 2.0 TB/s), in place 0.220 / 0.134 ms; 0.24 x / 0.23 x vsolve, 1.00 x / 0.78 x column_path,
+ * 0.62 x / 0.49 x (d).  Said plainly: on tall plans the call LOSES to level_add (1.44 x fp64, 1.72 x fp32).  DOWN against UP:
+ * 0.998, 0.998 and 1.001 (plain fp64, plain fp32, tall fp64), below the 0.3 % to 1.1 % by which five rounds spread: unresolved;
+ * tall fp32 1.010 at a spread of 0.2 %: DOWN costs 1 % more there, resolved. */
+#define MPDATA_COLUMN_SCAN_DOWN 1      /* mode bit: from the model top down, k = nzm .. 1 */
+#define MPDATA_COLUMN_SCAN_EXCLUSIVE 2 /* mode bit: o(k) is the sum in front of level k */
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  Device arrays of the plan's precision on the
+ * plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_column_scan_device(mpdata_plan* plan, int64_t sl0, int64_t n, int src, int dst, const void* wgt, void* total,
+                                   int mode);
+/* host arrays, synchronous (the plan's block staging buffer, as the 3g - 3z host forms) */
+int mpdata_plan_column_scan(mpdata_plan* plan, int64_t sl0, int64_t n, int src, int dst, const double* wgt, double* total,
+                            int mode);
+int mpdata_plan_column_scan_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int src, int dst, const float* wgt, float* total,
+                                int mode);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm,ntracers) (leading
+ * dimension ncrms); wgt (required) and total as above (leading dimension n).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_column_scan_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, double* f, int src, int dst,
+                              const double* wgt, double* total, int mode, void* stream);
+int mpdata_column_scan_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int src, int dst,
+                                  const float* wgt, float* total, int mode, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
