@@ -28,6 +28,7 @@ LEVEL_ADD, LEVEL_ADD_CLIP = 0, 1           # MPDATA_LEVEL_ADD* (include/mpdata_h
 CELL_ADD, CELL_ADD_CLIP = 0, 1             # MPDATA_CELL_ADD* (include/mpdata_hip.h section 3p)
 CONVERT_LIMIT = 1                          # MPDATA_CONVERT_LIMIT (include/mpdata_hip.h section 3t)
 COMBINE_CLIP, COMBINE_MAX = 1, 8            # MPDATA_COMBINE_* (include/mpdata_hip.h section 3z)
+LEVEL_HIST_MAX_BINS = 32   # MPDATA_LEVEL_HIST_MAX_BINS (include/mpdata_hip.h section 3ab)
 COLUMN_SCAN_DOWN, COLUMN_SCAN_EXCLUSIVE = 1, 2   # MPDATA_COLUMN_SCAN_* (include/mpdata_hip.h section 3aa)
 SATADJ_ICE = 1                             # MPDATA_SATADJ_ICE (include/mpdata_hip.h section 3y)
 LEVEL_COV_RAW = 1                          # MPDATA_LEVEL_COV_RAW (include/mpdata_hip.h section 3u)
@@ -289,6 +290,15 @@ def lib():
         for name in ("mpdata_column_scan_device", "mpdata_column_scan_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, dp, dp, ci, vp]
+        ep = ctypes.c_void_p                    # const double* edges: a host array (_edges_arg)
+        L.mpdata_plan_level_hist_device.restype = ci
+        L.mpdata_plan_level_hist_device.argtypes = [vp, i64, i64, ci, ci, ep, vp, vp, ci, ci]
+        for name in ("mpdata_plan_level_hist", "mpdata_plan_level_hist_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, ci, ep, dp, dp]
+        for name in ("mpdata_level_hist_device", "mpdata_level_hist_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, ep, dp, dp, ci, ci, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1355,6 +1365,30 @@ class Plan:
         _check(getattr(lib(), "mpdata_plan_column_cond" + self._sfx)(self._p, int(sl0), n, int(tc), P["lo"], P["hi"], P["kcnt"], P["kbot"],
                                                                     P["ktop"], P["cpath"], P["cover"], P["mass"]))
 
+    def level_hist(self, tc, edges, cnt=None, bsum=None, first_tracer=0, nb=None, sl0=0, n=None):
+        """Per-level histograms (include/mpdata_hip.h 3ab) over the interior columns of instances [sl0, sl0+n) (default: the
+        rest of the plan from sl0): edges is a HOST sequence of nb + 1 non-decreasing numbers (nb: default len(edges) - 1,
+        at most LEVEL_HIST_MAX_BINS); a column is in bin j where edges[j] < f(tc) <= edges[j+1]; cnt[j] = the number of
+        columns in bin j, bsum[r, j] = the SUM of tracer first_tracer + r over exactly those columns; on the plan's stream
+        (mpdata_plan_level_hist_device).  Reference-layout DEVICE tensors of the plan's precision, shapes
+        level_hist_shapes(n, nx, nz, nb, ntr): cnt (nb, nzm, n), bsum (ntr, nb, nzm, n) with ntr its leading axis; cnt or
+        bsum may be None (skipped), not both.  Changes nothing of the plan.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        nb, pe = _edges_arg(edges, nb)
+        ntr = 0 if bsum is None or bsum.dim() != 4 else int(bsum.shape[0])
+        sh = level_hist_shapes(n, self.dims[1], self.dims[2], nb, ntr)
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt()) for k, t in (("cnt", cnt), ("bsum", bsum))}
+        _check(lib().mpdata_plan_level_hist_device(self._p, int(sl0), n, int(tc), nb, pe, P["cnt"], P["bsum"], int(first_tracer), ntr))
+
+    def level_hist_host(self, tc, edges, cnt=None, bsum=None, nb=None, sl0=0, n=None):
+        """The same for all tracers with HOST arrays (numpy, Fortran order): cnt (written) (n, nzm, nb), bsum (written) (n,
+        nzm, nb, ntracers); cnt or bsum may be None; synchronous (mpdata_plan_level_hist[_f32])."""
+        n = self._block_n(sl0, n)
+        nb, pe = _edges_arg(edges, nb)
+        want = (n, self.dims[2] - 1, nb)
+        P = {name: None if a is None else self._block_host(a, name, want, tr, True) for name, a, tr in (("cnt", cnt, False), ("bsum", bsum, True))}
+        _check(getattr(lib(), "mpdata_plan_level_hist" + self._sfx)(self._p, int(sl0), n, int(tc), nb, pe, P["cnt"], P["bsum"]))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1721,6 +1755,50 @@ def convert(f, src, dst, r, q0=None, y=None, mode=0, dsum=None, sl0=0, n=None, s
     P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("r", r), ("q0", q0), ("y", y), ("dsum", dsum))}
     fn = lib().mpdata_convert_device if f.dtype == torch.float64 else lib().mpdata_convert_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(src), int(dst), P["r"], P["q0"], P["y"], int(mode), P["dsum"],
+              _stream_handle(stream)))
+
+
+def _edges_arg(edges, nb=None):
+    """the (nb, edges) arguments of a level_hist call: any sequence of numbers -> (nb, a C array of double); None reaches the
+    library as a null pointer (nb as given, or 0); nb defaults to len(edges) - 1 and may not ask for more edges than given"""
+    if edges is None:
+        return (0 if nb is None else int(nb)), None
+    e = [float(x) for x in edges]
+    nb = len(e) - 1 if nb is None else int(nb)
+    if nb + 1 > len(e):
+        raise MpdataError(-1, f"edges: {len(e)} values are fewer than nb + 1 = {nb + 1}")
+    return nb, (ctypes.cast((ctypes.c_double * len(e))(*e), ctypes.c_void_p) if e else None)
+
+
+def level_hist_shapes(n, nx, nz, nb, ntr=1):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a level_hist call on n instances, nb bins
+    and ntr value tracers: cnt (nb, nzm, n), bsum (ntr, nb, nzm, n).  (nx is taken as the other shape functions take it; no
+    array of the call has a column axis.)"""
+    n, nx, nz, nb, ntr = int(n), int(nx), int(nz), int(nb), int(ntr)
+    return {"cnt": (nb, nz - 1, n), "bsum": (ntr, nb, nz - 1, n)}
+
+
+def level_hist(f, tc, edges, cnt=None, bsum=None, first_tracer=0, nb=None, sl0=0, n=None, stream=None):
+    """Per-level histograms (include/mpdata_hip.h 3ab) of instances [sl0, sl0+n) (default: the rest from sl0) of a
+    reference-layout DEVICE tensor f (ntr, nzm, nx+6, ncrms), float64 or float32, which is only read: a column is in bin j
+    where edges[j] < f[tc] <= edges[j+1] (edges: a HOST sequence of nb + 1 non-decreasing numbers); cnt[j] = the number of
+    interior columns in bin j, bsum[r, j] = the sum of tracer first_tracer + r over them.  cnt, bsum of the same dtype with
+    the shapes of level_hist_shapes(n, nx, nz, nb, ntr), ntr the leading axis of bsum (cnt or bsum may be None).
+    Asynchronous on `stream` (mpdata_level_hist_device)."""
+    import torch
+    if f.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, f"level_hist: dtype {f.dtype} is neither float64 nor float32")
+    if f.dim() != 4 or f.shape[-2] < 7:
+        raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis")
+    nt, nzm, nxp6, ncrms = f.shape
+    n = ncrms - int(sl0) if n is None else int(n)
+    pf = _dev_ptr(f, tuple(f.shape), "f", f.dtype)
+    nb, pe = _edges_arg(edges, nb)
+    ntr = 0 if bsum is None or bsum.dim() != 4 else int(bsum.shape[0])
+    sh = level_hist_shapes(n, nxp6 - 6, nzm + 1, nb, ntr)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, f.dtype) for k, t in (("cnt", cnt), ("bsum", bsum))}
+    fn = lib().mpdata_level_hist_device if f.dtype == torch.float64 else lib().mpdata_level_hist_f32_device
+    _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(tc), nb, pe, P["cnt"], P["bsum"], int(first_tracer), ntr,
               _stream_handle(stream)))
 
 

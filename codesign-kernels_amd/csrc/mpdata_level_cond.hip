@@ -144,6 +144,7 @@ __device__ inline void mask_sum(const R2* p, const long long step, const int nx,
 }
 
 // Plan layout: a wave per (tile of the block, 64-element slice of the chunk), lane -> element e = s * nlev + kk.
+// (The head of the kernel down to the ballot has a twin, hist_rows of mpdata_level_hist.hip: a change to either belongs in both.)
 // R2: one 8-byte element (double, or the float2 of two adjacent slots); FORM: MASK or RE_READ.
 template <typename R2, int FORM>
 __global__ void __launch_bounds__(256) wm_level_cond_kernel(const MpdataLevelCondJob b, const long long t0, const int ntile, const int nslice) {

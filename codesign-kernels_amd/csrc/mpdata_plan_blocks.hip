@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3aa).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_column_scan.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3ab).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_level_hist.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -16,6 +16,7 @@
 #include "mpdata_level_cond.h"
 #include "mpdata_column_cond.h"
 #include "mpdata_level_cov.h"
+#include "mpdata_level_hist.h"
 #include "mpdata_nonneg.h"
 #include "mpdata_plan_priv.h"
 #include "mpdata_relax.h"
@@ -1958,6 +1959,95 @@ int mpdata_column_scan_device(int64_t ncrms, int nx, int nz, int ntracers, int64
 int mpdata_column_scan_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int src, int dst,
                                   const float* wgt, float* total, int mode, void* stream) {
   return column_scan_array(ncrms, nx, nz, ntracers, sl0, n, f, src, dst, wgt, total, mode, stream, 4);
+}
+
+// ---- 3ab: per-level histograms of f: how many interior columns have tracer tc inside each of the nb bins (e_j, e_{j+1}],
+// and the sum of every value tracer over exactly the columns of each bin.  Reads f and the HOST array edges, writes cnt and
+// bsum: as 3v, no flag of the plan is touched, no event is recorded, and a windowed plan's inner plan is read where it lies.
+static int plan_level_hist(mpdata_plan* p, int64_t sl0, int64_t n, int tc, int nb, const double* edges, void* cnt, void* bsum, int first,
+                           int count) {
+  if (plan_walked(p)) {
+    MpdataLevelHistJob b;
+    b.j = wm_job(wm_plan(p), 0, nullptr, 0, p->ntracers);
+    b.sel = block_sel(p, sl0, n);
+    b.tc = tc; b.first = first; b.ntr = count; b.nb = nb;
+    b.cnt = cnt; b.bsum = bsum;
+    HIP_TRY(mpdata_level_hist_wm(b, edges, p->stream));
+  } else {
+    HIP_TRY(mpdata_level_hist_ref(p->f, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, tc, nb, edges, cnt, bsum, first, count,
+                                  p->stream));
+  }
+  return 0;
+}
+// the binned tracer, the bins, the outputs and the value tracers of a call, for the plan forms (ntracers of the plan) and
+// the array forms alike; the edges are checked as given (rounding to fp32 is monotone); without bsum the range is not
+// looked at
+static int level_hist_args(const char* what, int ntracers, int tc, int nb, const double* edges, const void* cnt, const void* bsum,
+                           int first, int count) {
+  if (tc < 0 || tc >= ntracers) return set_err(MPDATA_EINVAL, "%s: binned tracer tc %d outside the %d tracers", what, tc, ntracers);
+  if (nb < 1 || nb > MPDATA_LEVEL_HIST_MAX_BINS)
+    return set_err(MPDATA_EINVAL, "%s: nb %d outside [1, %d]", what, nb, MPDATA_LEVEL_HIST_MAX_BINS);
+  if (!edges) return set_err(MPDATA_EINVAL, "%s: null edges", what);
+  for (int j = 0; j <= nb; ++j) {
+    if (edges[j] != edges[j]) return set_err(MPDATA_EINVAL, "%s: edges[%d] is a NaN", what, j);
+    if (j < nb && edges[j] > edges[j + 1]) return set_err(MPDATA_EINVAL, "%s: edges[%d] > edges[%d]", what, j, j + 1);
+  }
+  if (!cnt && !bsum) return set_err(MPDATA_EINVAL, "%s: cnt and bsum are both NULL", what);
+  if (bsum && (first < 0 || count < 1 || first > ntracers - count))
+    return set_err(MPDATA_EINVAL, "%s: tracer range [%d, %lld) outside the %d tracers", what, first, (long long)first + count, ntracers);
+  return 0;
+}
+static int plan_level_hist_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int tc, int nb, const double* edges,
+                                 const void* cnt, const void* bsum, int first, int count, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = level_hist_args(what, p->ntracers, tc, nb, edges, cnt, bsum, first, count);
+  return rc ? rc : plan_state(what, p, eb);
+}
+int mpdata_plan_level_hist_device(mpdata_plan* p, int64_t sl0, int64_t n, int tc, int nb, const double* edges, void* cnt, void* bsum,
+                                  int first_tracer, int ntracers) {
+  const int rc = plan_level_hist_check("mpdata_plan_level_hist_device", p, sl0, n, tc, nb, edges, cnt, bsum, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_level_hist(p, sl0, n, tc, nb, edges, cnt, bsum, first_tracer, ntracers);
+}
+static int plan_level_hist_host(mpdata_plan* p, int64_t sl0, int64_t n, int tc, int nb, const double* edges, void* cnt, void* bsum, int eb) {
+  int rc = plan_level_hist_check("mpdata_plan_level_hist", p, sl0, n, tc, nb, edges, cnt, bsum, 0, p ? p->ntracers : 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * nb * eb;
+  HostArr a[2] = {{cnt, kb, true}, {bsum, kb * p->ntracers, true}};
+  rc = stage_in(p, a);
+  if (!rc) rc = plan_level_hist(p, sl0, n, tc, nb, edges, a[0].dev, a[1].dev, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_level_hist(mpdata_plan* p, int64_t sl0, int64_t n, int tc, int nb, const double* edges, double* cnt, double* bsum) {
+  return plan_level_hist_host(p, sl0, n, tc, nb, edges, cnt, bsum, 8);
+}
+int mpdata_plan_level_hist_f32(mpdata_plan* p, int64_t sl0, int64_t n, int tc, int nb, const double* edges, float* cnt, float* bsum) {
+  return plan_level_hist_host(p, sl0, n, tc, nb, edges, cnt, bsum, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): asynchronous
+static int level_hist_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const void* f, int tc, int nb,
+                            const double* edges, void* cnt, void* bsum, int first, int count, void* stream, int eb) {
+  const char* const what = "mpdata_level_hist_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!f) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  rc = level_hist_args(what, ntracers, tc, nb, edges, cnt, bsum, first, count);
+  if (rc) return rc;
+  HIP_TRY(mpdata_level_hist_ref(f, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tc, nb, edges, cnt, bsum, first, count, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_level_hist_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, int tc, int nb,
+                             const double* edges, double* cnt, double* bsum, int first_tracer, int ntr, void* stream) {
+  return level_hist_array(ncrms, nx, nz, ntracers, sl0, n, f, tc, nb, edges, cnt, bsum, first_tracer, ntr, stream, 8);
+}
+int mpdata_level_hist_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int tc, int nb,
+                                 const double* edges, float* cnt, float* bsum, int first_tracer, int ntr, void* stream) {
+  return level_hist_array(ncrms, nx, nz, ntracers, sl0, n, f, tc, nb, edges, cnt, bsum, first_tracer, ntr, stream, 4);
 }
 
 }  // extern "C"

@@ -131,6 +131,12 @@ module mpdata_hip_mod
   ! interface block, behind 3z's
   public :: mpdata_plan_column_scan_device_c, mpdata_plan_column_scan_c, mpdata_plan_column_scan_f32_c
   public :: mpdata_column_scan_device_c, mpdata_column_scan_f32_device_c
+  ! per-level histograms of a resident plan's tracers (include/mpdata_hip.h section 3ab): all five entry points, each bound
+  ! by its literal name as 3aa's are (tests/fortran/level_hist_calls.F90); they stand in the second interface block, behind
+  ! 3aa's.  edges is a HOST array of real(c_double) in every form
+  public :: mpdata_plan_level_hist_device_c, mpdata_plan_level_hist_c, mpdata_plan_level_hist_f32_c
+  public :: mpdata_level_hist_device_c, mpdata_level_hist_f32_device_c
+  integer(c_int), parameter, public :: MPDATA_LEVEL_HIST_MAX_BINS = 32
   integer(c_int), parameter, public :: MPDATA_COLUMN_SCAN_DOWN = 1
   integer(c_int), parameter, public :: MPDATA_COLUMN_SCAN_EXCLUSIVE = 2
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
@@ -972,6 +978,65 @@ module mpdata_hip_mod
       integer(c_int), value :: src, dst
       type(c_ptr), value :: wgt, total
       integer(c_int), value :: mode
+      type(c_ptr), value :: stream
+    end function
+    ! ---- per-level histograms (include/mpdata_hip.h section 3ab; tracers counted from 0): column i of a level is in bin j
+    ! where edges(j) < f(tc) <= edges(j + 1), edges a HOST array of nb + 1 non-decreasing real(c_double) (c_loc of it) in
+    ! every form; cnt(n, nzm, nb) = the number of interior columns in each bin, bsum(n, nzm, nb, ntracers) = the SUM of
+    ! tracers first_tracer .. first_tracer + ntracers - 1 over exactly those columns (c_null_ptr: skipped; one of the two is
+    ! needed); nothing of the plan changes; windowed plans are supported
+    ! (device arrays of the plan's precision, asynchronous on the plan's stream)
+    integer(c_int) function mpdata_plan_level_hist_device_c(plan, sl0, n, tc, nb, edges, cnt, bsum, first_tracer, ntracers) &
+        bind(C, name="mpdata_plan_level_hist_device")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc, nb
+      type(c_ptr), value :: edges, cnt, bsum
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! host arrays (c_loc of real(c_double) arrays, or c_null_ptr), all tracers, synchronous
+    integer(c_int) function mpdata_plan_level_hist_c(plan, sl0, n, tc, nb, edges, cnt, bsum) &
+        bind(C, name="mpdata_plan_level_hist")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc, nb
+      type(c_ptr), value :: edges, cnt, bsum
+    end function
+    ! ... of real(c_float) arrays, for fp32 plans (edges stays real(c_double))
+    integer(c_int) function mpdata_plan_level_hist_f32_c(plan, sl0, n, tc, nb, edges, cnt, bsum) &
+        bind(C, name="mpdata_plan_level_hist_f32")
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc, nb
+      type(c_ptr), value :: edges, cnt, bsum
+    end function
+    ! the same on instances [sl0, sl0 + n) of a reference-layout device array f of real(c_double), which is only read
+    integer(c_int) function mpdata_level_hist_device_c(ncrms, nx, nz, ntracers, sl0, n, f, tc, nb, edges, cnt, bsum, first_tracer, &
+                                                       ntr, stream) bind(C, name="mpdata_level_hist_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f
+      integer(c_int), value :: tc, nb
+      type(c_ptr), value :: edges, cnt, bsum
+      integer(c_int), value :: first_tracer, ntr
+      type(c_ptr), value :: stream
+    end function
+    ! ... of real(c_float)
+    integer(c_int) function mpdata_level_hist_f32_device_c(ncrms, nx, nz, ntracers, sl0, n, f, tc, nb, edges, cnt, bsum, first_tracer, &
+                                                           ntr, stream) bind(C, name="mpdata_level_hist_f32_device")
+      import :: c_int, c_int64_t, c_ptr
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f
+      integer(c_int), value :: tc, nb
+      type(c_ptr), value :: edges, cnt, bsum
+      integer(c_int), value :: first_tracer, ntr
       type(c_ptr), value :: stream
     end function
   end interface

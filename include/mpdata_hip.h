@@ -1855,6 +1855,89 @@ int mpdata_column_scan_device(int64_t ncrms, int nx, int nz, int ntracers, int64
 int mpdata_column_scan_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, float* f, int src, int dst,
                                   const float* wgt, float* total, int mode, void* stream);
 
+/* ---- 3ab. Per-level histograms of a resident plan's tracers (the fourth kind of horizontal statistic a host model takes
+ * from its CRM instances, next to the first moments of 3g, the second moments of 3u and the conditional sums of 3v: the
+ * DISTRIBUTION -- the PDF of a tracer per level, a CFAD, mass or tracer content binned by a conserved variable.  3v names
+ * the route "a histogram of a tracer per level taken bin by bin": one mpdata_plan_level_cond_device call per bin, each of
+ * which reads the condition tracer, and with sums every value tracer, again.  This call bins every column ONCE in one
+ * walk over the field).  This section is the specification; the reference tree has no such routine.  For one binned tracer
+ * tc, nb bins with 1 <= nb <= MPDATA_LEVEL_HIST_MAX_BINS, a HOST array edges of nb + 1 doubles, a range of value tracers
+ * [first_tracer, first_tracer + ntracers) -- tc may lie inside it --, every instance sl in [sl0, sl0 + n) with b = sl - sl0,
+ * every level k = 1 .. nzm, nzm = nz - 1, over the INTERIOR columns i = 1 .. nx, with c_i = f(sl,i,k,tc) and v_i =
+ * f(sl,i,k,t), every statement below is rounded ONCE in the plan's precision, in this association, with nothing contracted,
+ * and the comparisons are plain compare-and-select, so EXACT and FAST plans give the same bits:
+ *   e_j = edges[j] rounded once to the plan's precision          j = 0 .. nb
+ *   m_i = the number of j in 0 .. nb with c_i > e_j              (0 .. nb + 1)
+ *   column i is in bin j = m_i - 1 when 1 <= m_i <= nb, else in no bin
+ *   cnt(b,k,j)    :  q = +0;  do i = 1, nx:  if column i in bin j:  q = q + 1
+ *   bsum(b,k,j,r) :  s = +0;  do i = 1, nx:  if column i in bin j:  s = s + v_i     (r = t - first_tracer)
+ * With the non-decreasing edges the call demands, bin j is the half-open interval (e_j, e_{j+1}] -- the interval of 3v, so
+ * cnt(:,:,j) and bsum(:,:,j,:) have the bits of 3v's cnt and csum called with lo = e_j and hi = e_{j+1}.  A column with c_i
+ * <= e_0 or c_i > e_nb is in no bin; outer edges of -inf / +inf collect everything.  Equal neighbouring edges make an empty
+ * bin.  A NaN in c_i is INSIDE the contract: every comparison is false, m_i = 0, the column is in no bin.  Selection means
+ * selection, as in 3v: an excluded v_i never reaches a sum, whatever its bits -- no multiplication by a mask; adding a
+ * selected +0 is allowed by 3v's argument.  cnt is a real of the plan's precision and exact (nx < 2^24): an implementation
+ * may count in integers and convert.
+ * edges is a HOST pointer in EVERY form, the device forms included (as mpdata_satadj_params of 3y): it is read before the
+ * call returns and may be reused at once; the edges travel to the kernel as launch arguments.  cnt is (n, nzm, nb), bsum is
+ * (n, nzm, nb, ntracers), both of the plan's precision, reference layout, instance index fastest, leading dimension n (the
+ * block's first instance at index 0).  Either output may be NULL, not both; with bsum == NULL the tracer range is not
+ * looked at.  Sums are SUMS and cnt is a count: the caller divides.
+ * Towards the rest of a plan, exactly as 3v: halo columns are never read, so a PERIODIC plan needs no wrap; nothing of the
+ * plan's state changes -- filled, have_u, have_w, the halo marks, the seam marks, the timing pair and last_kernel_ms --;
+ * the call is outside the run's event pair; the plan need not hold velocities.
+ *   windowed plans (3e, nz > 238) are supported: only OWNED levels are read, each is written to the tall level it stands
+ *     for, and no seam refresh is launched in front.
+ *   no output is reached by the phantom half of an odd fp32 plan (3f), the partner of a split fp32 pair or a padding slot,
+ *     and no byte outside cnt and bsum is touched.
+ * A kernel of its own on every kind of plan (mpdata_level_hist.hip), not fused into the run.  Wave-major and windowed plans:
+ * the lane-owned walk of 3v -- a lane owns one (instance, level) element, for fp32 both halves, and walks its interior
+ * column slots as read-only linear streams, 8 columns in flight; the value tracers lie at signed 64-bit offsets from the tc
+ * stream and are a loop inside the kernel; every accumulator is lane-local in column order.  The bins of a lane are
+ * REGISTERS: a compile-time array of the bin class (4, 8 or 16 bins, the least class that holds the bins of the walk), m_i by
+ * one compare per edge of the class (edges behind nb are +inf), then an unrolled chain of selects, s[j] = (m == j + 1) ? s[j]
+ * + v : s[j]; no array is indexed at run time.  A walk carries at most 16 bins in fp64 and 8 in fp32 -- wider classes spill
+ * scalar registers --, and a call of more bins is one launch per GROUP of bins, each reading tc again.  The counters are 32-bit integers, made reals at the store.  One walk per value
+ * tracer over the tc stream and the t stream (one stream for t == tc), the first of which also counts; there is no cache of
+ * the bin index per column, tc is read and binned again with every value tracer.  No LDS, no barrier, no cross-lane
+ * traffic.  A candidate with lane-private bins in LDS was built outside the tree, timed and not taken: DESIGN.md 4.31 with
+ * the timings.  Reference-layout plans and the array forms:
+ * one thread per instance and level row, loops over i, 64-bit offsets, groups of 8 bins.
+ * Checked before any device call, in this order -- a failed call changes nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), tc outside [0, ntracers), nb outside [1, 32], null edges, a
+ * NaN edge or edges[j] > edges[j+1] (checked on the doubles as given: rounding is monotone), cnt and bsum both NULL, with a
+ * non-null bsum a tracer range that is empty or outside the plan; in the array forms bad sizes (ncrms < 1, nx < 1, nz < 2,
+ * ntracers < 1), a block outside the arrays, a null f, then the same list as above.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3aa (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled.
+ * Time on the MI355X (docs/EXPERIMENTS.md AL, tools/level_hist_bench.py, profiles/level_hist_bench.json), 65536 x 32 x 28,
+ * cold, plans of four tracers, the median of five rounds (their spread at most 1.9 %), fp64 / fp32: cnt alone at nb = 2, 4, 8, 16, 32
+ * 0.114 / 0.066, 0.128 / 0.079, 0.176 / 0.115, 0.255 / 0.229, 0.525 / 0.456 ms; cnt and bsum of one value tracer at nb = 8 and 32
+ * 0.380 / 0.228 and 1.155 / 0.926 ms, of three 0.771 / 0.515 and 2.570 / 2.070 ms.  Against (a) nb mpdata_plan_level_cond_device
+ * calls, the route this replaces: 0.55 x / 0.59 x at nb = 2, 0.31 x / 0.37 x, 0.21 x / 0.28 x, 0.15 x / 0.28 x, 0.16 x / 0.28 x at 4, 8, 16,
+ * 32; with sums 0.18 x to 0.29 x.  Against (b) ONE such call, the floor of one read of the same bytes: 1.10 x / 1.09 x at nb = 2,
+ * 5.0 x / 7.5 x at nb = 32.  Against (c) mpdata_plan_export_device of the tracers: 0.55 x / 0.58 x at nb = 2, 0.84 x / 1.01 x
+ * (unresolved) at 8, 1.22 x / 2.0 x at 16, 2.5 x / 4.0 x at 32.  Said plainly: the call is bound by the vector ALU (about 3 nb
+ * operations per cell; 0.85 TB/s at nb = 32) and it LOSES to the export from nb = 16 on in both precisions.  4096 x 32 x 300 (6 windows): cnt 0.093 to 0.618 / 0.062 to 0.651 ms for nb = 2 to 32. */
+#define MPDATA_LEVEL_HIST_MAX_BINS 32
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  edges: HOST; cnt, bsum: device arrays of the
+ * plan's precision on the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_level_hist_device(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, int nb, const double* edges, void* cnt,
+                                  void* bsum, int first_tracer, int ntracers);
+/* host arrays, all tracers (bsum (n, nzm, nb, ntracers of the plan)), synchronous (the plan's block staging buffer, as the
+ * 3g - 3aa host forms) */
+int mpdata_plan_level_hist(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, int nb, const double* edges, double* cnt,
+                           double* bsum);
+int mpdata_plan_level_hist_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, int nb, const double* edges, float* cnt,
+                               float* bsum);
+/* the same on instances [sl0, sl0+n) of a reference-layout DEVICE array f(ncrms,-2:nx+3,1,nzm,ntracers) (leading
+ * dimension ncrms), which is only read; edges HOST; cnt, bsum as above (leading dimension n; bsum (n, nzm, nb, ntr)).
+ * Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_level_hist_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, int tc, int nb,
+                             const double* edges, double* cnt, double* bsum, int first_tracer, int ntr, void* stream);
+int mpdata_level_hist_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int tc,
+                                 int nb, const double* edges, float* cnt, float* bsum, int first_tracer, int ntr, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
