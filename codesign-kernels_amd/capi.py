@@ -299,6 +299,15 @@ def lib():
         for name in ("mpdata_level_hist_device", "mpdata_level_hist_f32_device"):
             getattr(L, name).restype = ci
             getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, ci, ci, ep, dp, dp, ci, ci, vp]
+        cd = ctypes.c_double
+        L.mpdata_plan_level_draft_device.restype = ci
+        L.mpdata_plan_level_draft_device.argtypes = [vp, i64, i64, ci, vp, vp, cd, cd, vp, vp, vp, vp, ci, ci]
+        for name in ("mpdata_plan_level_draft", "mpdata_plan_level_draft_f32"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [vp, i64, i64, ci, dp, dp, cd, cd, dp, dp, dp, dp]
+        for name in ("mpdata_level_draft_device", "mpdata_level_draft_f32_device"):
+            getattr(L, name).restype = ci
+            getattr(L, name).argtypes = [i64, ci, ci, ci, i64, i64, dp, dp, ci, dp, dp, cd, cd, dp, dp, dp, dp, ci, ci, vp]
         L.mpdata_plan_set_stream.restype = ci
         L.mpdata_plan_set_stream.argtypes = [vp, vp]
         for name in ("mpdata_plan_layout", "mpdata_plan_device"):
@@ -1389,6 +1398,38 @@ class Plan:
         P = {name: None if a is None else self._block_host(a, name, want, tr, True) for name, a, tr in (("cnt", cnt, False), ("bsum", bsum, True))}
         _check(getattr(lib(), "mpdata_plan_level_hist" + self._sfx)(self._p, int(sl0), n, int(tc), nb, pe, P["cnt"], P["bsum"]))
 
+    def level_draft(self, tc=-1, lo=None, hi=None, wup=0.0, wdn=0.0, cnt=None, wsum=None, fsum=None, wfsum=None, first_tracer=0,
+                    sl0=0, n=None):
+        """Per-level updraft / downdraft sampling (include/mpdata_hip.h 3ac) over the interior columns of instances [sl0,
+        sl0+n) (default: the rest of the plan from sl0): with wc = 0.5 * (w(k) + w(k+1)) (+0 above the top) a column where lo
+        < f(tc) <= hi (tc = -1: every column; a bound that is None does not bind) is UP (class 0) where wc > wup, DOWN (1)
+        where wc < wdn, ENV (2) otherwise; cnt[c] = the columns of class c, wsum[c] = the SUM of wc over them, fsum[j, c] = the
+        sum of tracer first_tracer + j, wfsum[j, c] = the sum of wc * tracer; on the plan's stream
+        (mpdata_plan_level_draft_device).  wdn <= wup, +-inf allowed.  Reference-layout DEVICE tensors of the plan's
+        precision, shapes level_draft_shapes(n, nx, nz, ntr): lo, hi (nzm, n), cnt, wsum (3, nzm, n), fsum, wfsum (ntr, 3,
+        nzm, n) with ntr their leading axis; any output may be None (skipped), not all.  The plan must hold w.  Changes
+        nothing of the plan.  Windowed plans are supported."""
+        n = self._block_n(sl0, n)
+        ntr = _draft_ntr(fsum, wfsum)
+        sh = level_draft_shapes(n, self.dims[1], self.dims[2], ntr)
+        P = {k: None if t is None else _dev_ptr(t, sh[k], k, self._tdt())
+             for k, t in (("lo", lo), ("hi", hi), ("cnt", cnt), ("wsum", wsum), ("fsum", fsum), ("wfsum", wfsum))}
+        _check(lib().mpdata_plan_level_draft_device(self._p, int(sl0), n, int(tc), P["lo"], P["hi"], float(wup), float(wdn), P["cnt"],
+                                                    P["wsum"], P["fsum"], P["wfsum"], int(first_tracer), ntr))
+
+    def level_draft_host(self, tc=-1, lo=None, hi=None, wup=0.0, wdn=0.0, cnt=None, wsum=None, fsum=None, wfsum=None, sl0=0, n=None):
+        """The same for all tracers with HOST arrays (numpy, Fortran order): lo, hi or None (n, nzm), cnt, wsum (written) (n,
+        nzm, 3), fsum, wfsum (written) (n, nzm, 3, ntracers); any output may be None, not all; synchronous
+        (mpdata_plan_level_draft[_f32])."""
+        n = self._block_n(sl0, n)
+        nzm = self.dims[2] - 1
+        P = {name: None if a is None else self._block_host(a, name, want, tr, out)
+             for name, a, want, tr, out in (("lo", lo, (n, nzm), False, False), ("hi", hi, (n, nzm), False, False),
+                                            ("cnt", cnt, (n, nzm, 3), False, True), ("wsum", wsum, (n, nzm, 3), False, True),
+                                            ("fsum", fsum, (n, nzm, 3), True, True), ("wfsum", wfsum, (n, nzm, 3), True, True))}
+        _check(getattr(lib(), "mpdata_plan_level_draft" + self._sfx)(self._p, int(sl0), n, int(tc), P["lo"], P["hi"], float(wup),
+                                                                     float(wdn), P["cnt"], P["wsum"], P["fsum"], P["wfsum"]))
+
     def shard_plan(self, g):
         """The single-device plan of GPU g of a multi-GPU plan (mpdata_plan_shard_plan) as a non-owning Plan: device
         import / export and the block calls (shard-local sl0) on the shard where it lives.  Closing the view frees
@@ -1800,6 +1841,56 @@ def level_hist(f, tc, edges, cnt=None, bsum=None, first_tracer=0, nb=None, sl0=0
     fn = lib().mpdata_level_hist_device if f.dtype == torch.float64 else lib().mpdata_level_hist_f32_device
     _check(fn(ncrms, nxp6 - 6, nzm + 1, nt, int(sl0), n, pf, int(tc), nb, pe, P["cnt"], P["bsum"], int(first_tracer), ntr,
               _stream_handle(stream)))
+
+
+def _draft_ntr(fsum, wfsum):
+    """the value tracers of a level_draft call: the leading axis of fsum, else of wfsum (0: neither given, or no 4-d tensor;
+    a wfsum of another count than fsum fails the shape check)"""
+    for t in (fsum, wfsum):
+        if t is not None:
+            return int(t.shape[0]) if t.dim() == 4 else 0
+    return 0
+
+
+def level_draft_shapes(n, nx, nz, ntr=1):
+    """Torch shapes (reversed-axes view of the reference layout) of the arrays of a level_draft call on n instances and ntr
+    value tracers: lo, hi (nzm, n), cnt, wsum (3, nzm, n), fsum, wfsum (ntr, 3, nzm, n); the class axis is UP, DOWN, ENV.
+    (nx is taken as the other shape functions take it; no array of the call has a column axis.)"""
+    n, nx, nz, ntr = int(n), int(nx), int(nz), int(ntr)
+    return {"lo": (nz - 1, n), "hi": (nz - 1, n), "cnt": (3, nz - 1, n), "wsum": (3, nz - 1, n), "fsum": (ntr, 3, nz - 1, n),
+            "wfsum": (ntr, 3, nz - 1, n)}
+
+
+def level_draft(f, w, tc=-1, lo=None, hi=None, wup=0.0, wdn=0.0, cnt=None, wsum=None, fsum=None, wfsum=None, first_tracer=0, sl0=0,
+                n=None, stream=None):
+    """Per-level updraft / downdraft sampling (include/mpdata_hip.h 3ac) of instances [sl0, sl0+n) (default: the rest from
+    sl0) of reference-layout DEVICE tensors f (ntr, nzm, nx+6, ncrms) and w (nz, nx+4, ncrms), float64 or float32, which are
+    only read: with wc = 0.5 * (w[k] + w[k+1]) (+0 above the top; w[nz-1] is never read) a column where lo < f[tc] <= hi (tc =
+    -1: every column) is UP where wc > wup, DOWN where wc < wdn, ENV otherwise; cnt, wsum, fsum, wfsum per class as
+    Plan.level_draft, of the same dtype with the shapes of level_draft_shapes(n, nx, nz, ntr).  f may be None where tc < 0 and
+    neither fsum nor wfsum is given.  Asynchronous on `stream` (mpdata_level_draft_device)."""
+    import torch
+    if w is None or w.dtype not in (torch.float64, torch.float32):
+        raise MpdataError(-1, "level_draft: w is None or neither float64 nor float32")
+    if w.dim() != 3 or w.shape[-2] < 5 or w.shape[0] < 2:
+        raise MpdataError(-1, f"w: shape {tuple(w.shape)} is no reference-layout w")
+    nz, nxp4, ncrms = w.shape
+    nt = 1
+    pf = None
+    if f is not None:
+        if f.dim() != 4 or tuple(f.shape[1:]) != (nz - 1, nxp4 + 2, ncrms):
+            raise MpdataError(-1, f"f: shape {tuple(f.shape)} is no reference-layout f with a tracer axis beside w {tuple(w.shape)}")
+        nt = int(f.shape[0])
+        pf = _dev_ptr(f, tuple(f.shape), "f", w.dtype)
+    n = ncrms - int(sl0) if n is None else int(n)
+    pw = _dev_ptr(w, tuple(w.shape), "w", w.dtype)
+    ntr = _draft_ntr(fsum, wfsum)
+    sh = level_draft_shapes(n, nxp4 - 4, nz, ntr)
+    P = {k: None if t is None else _dev_ptr(t, sh[k], k, w.dtype)
+         for k, t in (("lo", lo), ("hi", hi), ("cnt", cnt), ("wsum", wsum), ("fsum", fsum), ("wfsum", wfsum))}
+    fn = lib().mpdata_level_draft_device if w.dtype == torch.float64 else lib().mpdata_level_draft_f32_device
+    _check(fn(ncrms, nxp4 - 4, nz, nt, int(sl0), n, pf, pw, int(tc), P["lo"], P["hi"], float(wup), float(wdn), P["cnt"], P["wsum"],
+              P["fsum"], P["wfsum"], int(first_tracer), ntr, _stream_handle(stream)))
 
 
 def _src_arg(src):

@@ -1,5 +1,5 @@
-// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3ab).  Host
-// code only: the kernels are in mpdata_stats.hip .. mpdata_level_hist.hip.  A call is its kernel file, a dispatch on the
+// mpdata_plan_blocks.hip -- the calls on a block of instances of a resident plan (include/mpdata_hip.h 3g .. 3ac).  Host
+// code only: the kernels are in mpdata_stats.hip .. mpdata_level_draft.hip.  A call is its kernel file, a dispatch on the
 // layout (plan_X), one check function for both of its forms (plan_X_check) and, for the host form, a table of its arrays;
 // the tails the calls share are array_block, scratch_done and plan_rewrote.
 #include <cstring>
@@ -16,6 +16,7 @@
 #include "mpdata_level_cond.h"
 #include "mpdata_column_cond.h"
 #include "mpdata_level_cov.h"
+#include "mpdata_level_draft.h"
 #include "mpdata_level_hist.h"
 #include "mpdata_nonneg.h"
 #include "mpdata_plan_priv.h"
@@ -2048,6 +2049,111 @@ int mpdata_level_hist_device(int64_t ncrms, int nx, int nz, int ntracers, int64_
 int mpdata_level_hist_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int tc, int nb,
                                  const double* edges, float* cnt, float* bsum, int first_tracer, int ntr, void* stream) {
   return level_hist_array(ncrms, nx, nz, ntracers, sl0, n, f, tc, nb, edges, cnt, bsum, first_tracer, ntr, stream, 4);
+}
+
+// ---- 3ac: per-level updraft / downdraft sampling of f by the cell-centred w: the interior columns of a level in three
+// classes by wc = 0.5 * (w(k) + w(k+1)) against wup and wdn, where tracer tc lies inside (lo, hi]; per class the count, the
+// sum of wc, of every value tracer and of wc * tracer.  Reads f, w, lo and hi, writes the four outputs: as 3h and 3v, no
+// flag of the plan is touched, no event is recorded, and a windowed plan's inner plan is read where it lies.  The plan must
+// hold w; u is not looked at.
+struct LevelDraftOut {
+  void *cnt, *wsum, *fsum, *wfsum;
+};
+static int plan_level_draft(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, double wup, double wdn,
+                            const LevelDraftOut& o, int first, int count) {
+  if (plan_walked(p)) {
+    const mpdata_plan* q = wm_plan(p);
+    MpdataLevelDraftJob b;
+    b.j = wm_job(q, 0, nullptr, 0, p->ntracers);
+    b.w = wm_job(q, 2, nullptr, 0, 1).prv;
+    b.sel = block_sel(p, sl0, n);
+    b.tc = tc; b.first = first; b.ntr = count;
+    b.lo = lo; b.hi = hi; b.wup = wup; b.wdn = wdn;
+    b.cnt = o.cnt; b.wsum = o.wsum; b.fsum = o.fsum; b.wfsum = o.wfsum;
+    HIP_TRY(mpdata_level_draft_wm(b, p->stream));
+  } else {
+    HIP_TRY(mpdata_level_draft_ref(p->f, p->w, p->eb, p->ncrms, sl0, n, p->nx, p->nz - 1, p->ntracers, tc, lo, hi, wup, wdn, o.cnt, o.wsum,
+                                   o.fsum, o.wfsum, first, count, p->stream));
+  }
+  return 0;
+}
+// the condition, the bounds, the thresholds, the outputs and the value tracers of a call, for the plan forms (ntracers of
+// the plan) and the array forms alike; the thresholds are checked as given (rounding to fp32 is monotone); without fsum and
+// wfsum the range is not looked at
+static int level_draft_args(const char* what, int ntracers, int tc, const void* lo, const void* hi, double wup, double wdn,
+                            const LevelDraftOut& o, int first, int count) {
+  if (tc < -1 || tc >= ntracers) return set_err(MPDATA_EINVAL, "%s: condition tracer tc %d outside [-1, %d)", what, tc, ntracers);
+  if (tc < 0 && (lo || hi)) return set_err(MPDATA_EINVAL, "%s: lo or hi given without a condition tracer (tc = -1)", what);
+  if (wup != wup || wdn != wdn) return set_err(MPDATA_EINVAL, "%s: a threshold is a NaN", what);
+  if (wdn > wup) return set_err(MPDATA_EINVAL, "%s: wdn %g > wup %g", what, wdn, wup);
+  if (!o.cnt && !o.wsum && !o.fsum && !o.wfsum) return set_err(MPDATA_EINVAL, "%s: cnt, wsum, fsum and wfsum are all NULL", what);
+  if ((o.fsum || o.wfsum) && (first < 0 || count < 1 || first > ntracers - count))
+    return set_err(MPDATA_EINVAL, "%s: tracer range [%d, %lld) outside the %d tracers", what, first, (long long)first + count, ntracers);
+  return 0;
+}
+static int plan_level_draft_check(const char* what, const mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi,
+                                  double wup, double wdn, const LevelDraftOut& o, int first, int count, int eb) {
+  int rc = block_range(what, p, sl0, n);
+  if (rc) return rc;
+  rc = level_draft_args(what, p->ntracers, tc, lo, hi, wup, wdn, o, first, count);
+  return rc ? rc : plan_state(what, p, eb, false, true);
+}
+int mpdata_plan_level_draft_device(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, double wup, double wdn,
+                                   void* cnt, void* wsum, void* fsum, void* wfsum, int first_tracer, int ntracers) {
+  const LevelDraftOut o = {cnt, wsum, fsum, wfsum};
+  const int rc = plan_level_draft_check("mpdata_plan_level_draft_device", p, sl0, n, tc, lo, hi, wup, wdn, o, first_tracer, ntracers, 0);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  return plan_level_draft(p, sl0, n, tc, lo, hi, wup, wdn, o, first_tracer, ntracers);
+}
+static int plan_level_draft_host(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, double wup, double wdn,
+                                 const LevelDraftOut& o, int eb) {
+  int rc = plan_level_draft_check("mpdata_plan_level_draft", p, sl0, n, tc, lo, hi, wup, wdn, o, 0, p ? p->ntracers : 0, eb);
+  if (rc) return rc;
+  DevGuard g(p->device);
+  const size_t kb = (size_t)n * (p->nz - 1) * eb, cb = kb * MPDATA_LEVEL_DRAFT_CLASSES;
+  HostArr a[6] = {{lo, kb, false}, {hi, kb, false}, {o.cnt, cb, true}, {o.wsum, cb, true}, {o.fsum, cb * p->ntracers, true},
+                  {o.wfsum, cb * p->ntracers, true}};
+  rc = stage_in(p, a);
+  const LevelDraftOut d = {a[2].dev, a[3].dev, a[4].dev, a[5].dev};
+  if (!rc) rc = plan_level_draft(p, sl0, n, tc, a[0].dev, a[1].dev, wup, wdn, d, 0, p->ntracers);
+  return rc ? rc : stage_out(p, a);
+}
+int mpdata_plan_level_draft(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const double* lo, const double* hi, double wup, double wdn,
+                            double* cnt, double* wsum, double* fsum, double* wfsum) {
+  return plan_level_draft_host(p, sl0, n, tc, lo, hi, wup, wdn, {cnt, wsum, fsum, wfsum}, 8);
+}
+int mpdata_plan_level_draft_f32(mpdata_plan* p, int64_t sl0, int64_t n, int tc, const float* lo, const float* hi, double wup, double wdn,
+                                float* cnt, float* wsum, float* fsum, float* wfsum) {
+  return plan_level_draft_host(p, sl0, n, tc, lo, hi, wup, wdn, {cnt, wsum, fsum, wfsum}, 4);
+}
+// the same on reference-layout device arrays (arguments checked before any device call): asynchronous.  w is required; f
+// only where the condition or a sum reads it
+static int level_draft_array(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const void* f, const void* w, int tc,
+                             const void* lo, const void* hi, double wup, double wdn, const LevelDraftOut& o, int first, int count,
+                             void* stream, int eb) {
+  const char* const what = "mpdata_level_draft_device";
+  int rc = array_sizes(what, ncrms, nx, nz, &ntracers);
+  if (rc) return rc;
+  rc = array_block(what, ncrms, sl0, n);
+  if (rc) return rc;
+  if (!w) return set_err(MPDATA_EINVAL, "%s: null w", what);
+  if (!f && (tc >= 0 || o.fsum || o.wfsum)) return set_err(MPDATA_EINVAL, "%s: null f", what);
+  rc = level_draft_args(what, ntracers, tc, lo, hi, wup, wdn, o, first, count);
+  if (rc) return rc;
+  HIP_TRY(mpdata_level_draft_ref(f, w, eb, ncrms, sl0, n, nx, nz - 1, ntracers, tc, lo, hi, wup, wdn, o.cnt, o.wsum, o.fsum, o.wfsum, first,
+                                 count, (hipStream_t)stream));
+  return 0;
+}
+int mpdata_level_draft_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, const double* w, int tc,
+                              const double* lo, const double* hi, double wup, double wdn, double* cnt, double* wsum, double* fsum,
+                              double* wfsum, int first_tracer, int ntr, void* stream) {
+  return level_draft_array(ncrms, nx, nz, ntracers, sl0, n, f, w, tc, lo, hi, wup, wdn, {cnt, wsum, fsum, wfsum}, first_tracer, ntr, stream, 8);
+}
+int mpdata_level_draft_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, const float* w, int tc,
+                                  const float* lo, const float* hi, double wup, double wdn, float* cnt, float* wsum, float* fsum,
+                                  float* wfsum, int first_tracer, int ntr, void* stream) {
+  return level_draft_array(ncrms, nx, nz, ntracers, sl0, n, f, w, tc, lo, hi, wup, wdn, {cnt, wsum, fsum, wfsum}, first_tracer, ntr, stream, 4);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
-// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3ab:
-// the twenty-two kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
+// mpdata_wm_walk.h -- what the calls on a block of instances of a resident plan share (include/mpdata_hip.h 3g .. 3ac:
+// the twenty-three kernel files mpdata_stats.hip, mpdata_courant.hip, mpdata_level_add.hip, mpdata_scale_uw.hip,
 // mpdata_column_path.hip, mpdata_diffuse.hip, mpdata_subside.hip, mpdata_sediment.hip, mpdata_vsolve.hip, mpdata_cell_add.hip,
-// mpdata_column_step.hip, mpdata_relax.hip, mpdata_vdiffuse.hip, mpdata_convert.hip, mpdata_level_cov.hip, mpdata_level_cond.hip, mpdata_column_cond.hip, mpdata_nonneg.hip, mpdata_satadj.hip, mpdata_combine.hip, mpdata_column_scan.hip, mpdata_level_hist.hip; their host side is mpdata_plan_blocks.hip): the selector of the block, the
+// mpdata_column_step.hip, mpdata_relax.hip, mpdata_vdiffuse.hip, mpdata_convert.hip, mpdata_level_cov.hip, mpdata_level_cond.hip, mpdata_column_cond.hip, mpdata_nonneg.hip, mpdata_satadj.hip, mpdata_combine.hip, mpdata_column_scan.hip, mpdata_level_hist.hip, mpdata_level_draft.hip; their host side is mpdata_plan_blocks.hip): the selector of the block, the
 // element traits, and on the host side the tile grid, the column-group geometry of the eight kernels that stage columns
 // through LDS (col_groups_batched, col_groups_tiled), the LDS limit of a workgroup and the precision dispatch of the
 // reference-layout launches (ref_real).  The host side is free to share: a launcher fills its kernel's argument struct
@@ -35,7 +35,7 @@ struct MpdataBlockSel {
   int W, nz;
 };
 
-// everything below is for the twenty-two kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
+// everything below is for the twenty-three kernel files (`using namespace wm_walk`); a host file that builds the jobs needs the
 // selector alone
 namespace wm_walk {
 

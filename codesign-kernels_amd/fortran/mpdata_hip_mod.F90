@@ -137,6 +137,14 @@ module mpdata_hip_mod
   public :: mpdata_plan_level_hist_device_c, mpdata_plan_level_hist_c, mpdata_plan_level_hist_f32_c
   public :: mpdata_level_hist_device_c, mpdata_level_hist_f32_device_c
   integer(c_int), parameter, public :: MPDATA_LEVEL_HIST_MAX_BINS = 32
+  ! per-level updraft / downdraft sampling of a resident plan (include/mpdata_hip.h section 3ac): all five entry points,
+  ! each bound by its literal name as 3ab's are (tests/fortran/level_draft_calls.F90); they stand in the second interface
+  ! block, behind 3ab's.  wup and wdn are real(c_double) by value in every form
+  public :: mpdata_plan_level_draft_device_c, mpdata_plan_level_draft_c, mpdata_plan_level_draft_f32_c
+  public :: mpdata_level_draft_device_c, mpdata_level_draft_f32_device_c
+  integer(c_int), parameter, public :: MPDATA_LEVEL_DRAFT_UP = 0
+  integer(c_int), parameter, public :: MPDATA_LEVEL_DRAFT_DOWN = 1
+  integer(c_int), parameter, public :: MPDATA_LEVEL_DRAFT_ENV = 2
   integer(c_int), parameter, public :: MPDATA_COLUMN_SCAN_DOWN = 1
   integer(c_int), parameter, public :: MPDATA_COLUMN_SCAN_EXCLUSIVE = 2
   ! implicit vertical diffusion of a resident plan's tracers with a per-cell diffusivity, in place (include/mpdata_hip.h
@@ -1036,6 +1044,76 @@ module mpdata_hip_mod
       type(c_ptr), value :: f
       integer(c_int), value :: tc, nb
       type(c_ptr), value :: edges, cnt, bsum
+      integer(c_int), value :: first_tracer, ntr
+      type(c_ptr), value :: stream
+    end function
+    ! ---- per-level updraft / downdraft sampling (include/mpdata_hip.h section 3ac; tracers counted from 0, tc = -1: no
+    ! tracer condition): with wc = 0.5 * (w(k) + w(k+1)) (+0 above the top) a column of a level where lo < f(tc) <= hi is in
+    ! class UP (0) where wc > wup, DOWN (1) where wc < wdn, ENV (2) otherwise; cnt(n, nzm, 3) = the columns of each class,
+    ! wsum(n, nzm, 3) = the SUM of wc over them, fsum and wfsum(n, nzm, 3, ntracers) = the sums of tracers first_tracer ..
+    ! first_tracer + ntracers - 1 and of wc times them (c_null_ptr: skipped; one of the four is needed; lo, hi: c_null_ptr
+    ! does not bind); the plan must hold w; nothing of the plan changes; windowed plans are supported
+    ! (device arrays of the plan's precision, asynchronous on the plan's stream)
+    integer(c_int) function mpdata_plan_level_draft_device_c(plan, sl0, n, tc, lo, hi, wup, wdn, cnt, wsum, fsum, wfsum, &
+                                                             first_tracer, ntracers) bind(C, name="mpdata_plan_level_draft_device")
+      import :: c_int, c_int64_t, c_ptr, c_double
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi
+      real(c_double), value :: wup, wdn
+      type(c_ptr), value :: cnt, wsum, fsum, wfsum
+      integer(c_int), value :: first_tracer, ntracers
+    end function
+    ! host arrays (c_loc of real(c_double) arrays, or c_null_ptr), all tracers, synchronous
+    integer(c_int) function mpdata_plan_level_draft_c(plan, sl0, n, tc, lo, hi, wup, wdn, cnt, wsum, fsum, wfsum) &
+        bind(C, name="mpdata_plan_level_draft")
+      import :: c_int, c_int64_t, c_ptr, c_double
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi
+      real(c_double), value :: wup, wdn
+      type(c_ptr), value :: cnt, wsum, fsum, wfsum
+    end function
+    ! ... of real(c_float) arrays, for fp32 plans (wup, wdn stay real(c_double))
+    integer(c_int) function mpdata_plan_level_draft_f32_c(plan, sl0, n, tc, lo, hi, wup, wdn, cnt, wsum, fsum, wfsum) &
+        bind(C, name="mpdata_plan_level_draft_f32")
+      import :: c_int, c_int64_t, c_ptr, c_double
+      type(c_ptr), value :: plan
+      integer(c_int64_t), value :: sl0, n
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi
+      real(c_double), value :: wup, wdn
+      type(c_ptr), value :: cnt, wsum, fsum, wfsum
+    end function
+    ! the same on instances [sl0, sl0 + n) of reference-layout device arrays f and w of real(c_double), which are only read
+    integer(c_int) function mpdata_level_draft_device_c(ncrms, nx, nz, ntracers, sl0, n, f, w, tc, lo, hi, wup, wdn, cnt, wsum, &
+                                     fsum, wfsum, first_tracer, ntr, stream) bind(C, name="mpdata_level_draft_device")
+      import :: c_int, c_int64_t, c_ptr, c_double
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f, w
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi
+      real(c_double), value :: wup, wdn
+      type(c_ptr), value :: cnt, wsum, fsum, wfsum
+      integer(c_int), value :: first_tracer, ntr
+      type(c_ptr), value :: stream
+    end function
+    ! ... of real(c_float)
+    integer(c_int) function mpdata_level_draft_f32_device_c(ncrms, nx, nz, ntracers, sl0, n, f, w, tc, lo, hi, wup, wdn, cnt, wsum, &
+                                     fsum, wfsum, first_tracer, ntr, stream) bind(C, name="mpdata_level_draft_f32_device")
+      import :: c_int, c_int64_t, c_ptr, c_double
+      integer(c_int64_t), value :: ncrms
+      integer(c_int), value :: nx, nz, ntracers
+      integer(c_int64_t), value :: sl0, n
+      type(c_ptr), value :: f, w
+      integer(c_int), value :: tc
+      type(c_ptr), value :: lo, hi
+      real(c_double), value :: wup, wdn
+      type(c_ptr), value :: cnt, wsum, fsum, wfsum
       integer(c_int), value :: first_tracer, ntr
       type(c_ptr), value :: stream
     end function

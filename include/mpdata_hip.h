@@ -1938,6 +1938,107 @@ int mpdata_level_hist_device(int64_t ncrms, int nx, int nz, int ntracers, int64_
 int mpdata_level_hist_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, int tc,
                                  int nb, const double* edges, float* cnt, float* bsum, int first_tracer, int ntr, void* stream);
 
+/* ---- 3ac. Per-level updraft and downdraft sampling of a resident plan (the one block call that looks at a tracer and
+ * the vertical velocity of a cell TOGETHER: 3g - 3ab reduce the tracers, 3h and 3j touch the velocities, none joins the two
+ * halves of a plan's state.  The pair is what the statistics of a cloud-resolving model are built on: SAM's conditional
+ * averages -- core, downdraft core, environment -- sample by the cell-centred w and a cloud condition; the same sampling
+ * gives the cloudy and unsaturated up and down mass fluxes an MMF hands back to the global model every step, the in-core
+ * means and the resolved flux w f split by draft).  This section is the specification; the reference tree has no such
+ * routine.  For a condition tracer tc (tc = -1: no tracer condition), a range of value tracers [first_tracer, first_tracer
+ * + ntracers) -- tc may lie inside it --, every instance sl in [sl0, sl0 + n) with b = sl - sl0, every level k = 1 .. nzm,
+ * nzm = nz - 1, over the INTERIOR columns i = 1 .. nx, with c_i = f(sl,i,k,tc) and v_i = f(sl,i,k,first_tracer + j), every
+ * statement below is rounded ONCE in the plan's precision, in this association, with nothing contracted, and the
+ * comparisons are plain compare-and-select, so EXACT and FAST plans give the same bits:
+ *   wk1  = w(sl,i,k+1) for k < nzm,  +0 for k = nzm        (as 3h: the caller's w(:,:,:,nz) is never read)
+ *   a    = w(sl,i,k) + wk1 ;  wc = 0.5 * a                  (the cell-centred vertical velocity)
+ *   in_i = tc < 0 ? true : (lo ? c_i > lo(b,k) : true) and (hi ? c_i <= hi(b,k) : true)          (exactly 3v)
+ *   class of column i, only where in_i:   UP (0): wc > wup    DOWN (1): wc < wdn    ENV (2): otherwise
+ *   cnt  (b,k,c)    :  q = +0;  do i = 1, nx:  if class_i == c:  q = q + 1
+ *   wsum (b,k,c)    :  s = +0;  do i = 1, nx:  if class_i == c:  s = s + wc
+ *   fsum (b,k,c,j)  :  s = +0;  do i = 1, nx:  if class_i == c:  s = s + v_i
+ *   wfsum(b,k,c,j)  :  s = +0;  do i = 1, nx:  if class_i == c:  p = wc * v_i;  s = s + p
+ * wup and wdn are doubles by value, each rounded once to the plan's precision (as c of 3p); wdn <= wup is required, +-inf
+ * are allowed, so one-sided classes or no draft classes at all are a single call; wc == wup and wc == wdn are ENV.  A NaN
+ * in w, c_i, lo or hi is outside the contract.  Selection means selection, as in 3v: a column outside a class contributes
+ * nothing to it, whatever bits its value tracer holds -- no multiplication by a mask; a column that is not in_i is in no
+ * class.  Sums are SUMS: the caller multiplies by rho and divides by cnt.  cnt is a real of the plan's precision and exact
+ * (nx < 2^24): an implementation may count in integers and convert.
+ * All four outputs are optional, at least one is required; lo and hi are optional, and with tc < 0 both must be NULL.  lo
+ * and hi are (n, nzm), cnt and wsum (n, nzm, 3), fsum and wfsum (n, nzm, 3, ntracers): the plan's precision, reference
+ * layout, the instance index fastest with leading dimension n (the block's first instance at index 0), then the level,
+ * the class, the tracer -- the order of 3ab's cnt and bsum.  The tracer range is looked at only when fsum or wfsum is given.
+ * Bit relations (they tie the call to 3g and 3v without passing through its own model):
+ *   wup = +inf, wdn = -inf: cnt(:,:,ENV) and fsum(:,:,ENV,:) have the bits of 3v's cnt and csum with the same tc, lo, hi;
+ *     UP and DOWN are +0 throughout.  With tc = -1 as well: fsum(:,:,ENV,:) has the bits of 3g's sum and cnt(:,:,ENV) = nx.
+ *   any thresholds: cnt(UP) + cnt(DOWN) + cnt(ENV) equals 3v's cnt (all exact integers).
+ * Towards the rest of a plan: nothing of the plan changes -- f, u, w, filled, have_u, have_w, the halo marks, the seam
+ * marks, the timing pair and last_kernel_ms --; halo columns of f and w are never read, so a PERIODIC plan needs no wrap;
+ * the call is outside the run's event pair.  The plan must hold w: after mpdata_plan_run_uw the call returns MPDATA_ESTATE
+ * until w has been imported whole again; u is not needed -- a plan that holds w but not u works.
+ *   windowed plans (3e, nz > 238) are supported: only OWNED levels are read, each with lo / hi of its tall level, each
+ *     written to the tall level it stands for; no seam refresh is launched in front; wk1 is taken inside the window as 3h
+ *     takes it and is +0 only at the tall top.
+ *   no output is reached by the phantom half of an odd fp32 plan (3f), the partner of a split fp32 pair or a padding slot,
+ *     and no byte outside the four outputs is touched.
+ * A kernel of its own on every kind of plan (mpdata_level_draft.hip), not fused into the run.  Wave-major and windowed
+ * plans: the lane-owned walk of 3v -- a lane owns one (instance, level) element, for fp32 both halves, and walks its
+ * interior column slots as read-only linear streams; w(k) and w(k+1) are the two streams of 3h (element e + 1 through an
+ * address and a column stride of its own); the value tracers lie at signed 64-bit offsets from the tc stream and are a loop
+ * inside the kernel; every accumulator is lane-local in column order; no atomics, no cross-lane traffic, no LDS.  ONE form
+ * at every nx: nothing of a column is kept between walks -- no class mask, no cached wc --, the class is formed again in
+ * every walk from w(k), w(k+1) and c_i, and a walk carries a GROUP of 4, 2 or 1 value tracers (the most that is left, 8
+ * or 4 columns in flight), so the three class streams are read once per group; the first walk also forms cnt and wsum.
+ * The counters are 32-bit integers, made reals at the store.  Reference-layout plans and the array forms: one thread per
+ * instance and level row, loops over i, 64-bit offsets, one value tracer a walk.
+ * Checked before any device call, in this order -- a failed call changes nothing and launches nothing:
+ * MPDATA_EINVAL: null plan, n < 1, a range outside [0, ncrms), tc outside [-1, ntracers), lo or hi given with tc < 0, a NaN
+ * in wup or wdn, wdn > wup (checked on the doubles as given: rounding is monotone), all four outputs NULL, with fsum or
+ * wfsum a tracer range that is empty or outside the plan; in the array forms bad sizes (ncrms < 1, nx < 1, nz < 2,
+ * ntracers < 1), a block outside the arrays, a null w, a null f where tc >= 0, fsum or wfsum needs it, then the same list.
+ * MPDATA_EUNSUPPORTED: a multi-GPU handle, as in 3d - 3ab (take mpdata_plan_shard_plan(plan, g) and a shard-local sl0).
+ * MPDATA_ESTATE: a host form of the other precision; a plan never filled; a plan that does not hold w.
+ * Time on the MI355X (docs/EXPERIMENTS.md AM, tools/level_draft_bench.py, profiles/level_draft_bench.json):
+ * 65536 x 32 x 28, cold, plans of nine tracers, tc with lo and hi, wup = 0.25, wdn = -0.25 (6 % of the cells UP, 6 % DOWN, 38 %
+ * ENV), the median of five rounds (their spread at most 1.5 %; the block of 64: 3.0 %), fp64 / fp32: cnt and wsum alone 0.255 /
+ * 0.157 ms; fsum of 1, 3, 8 tracers 0.314 / 0.174, 0.631 / 0.349, 1.381 / 0.795 ms; fsum and wfsum of the same 0.349 / 0.204, 0.734 /
+ * 0.467, 1.693 / 1.082 ms; a block of 64 instances (fsum and wfsum of 3) 0.021 / 0.031 ms.  Achieved on the algorithmic bytes (the
+ * interior of w twice, of tc and the value tracers once): 5.3 / 4.3 TB/s for cnt and wsum, 5.8 / 5.2, 4.3 / 3.9, 3.6 / 3.1 TB/s for
+ * fsum of 1, 3, 8 and 5.2 / 4.4, 3.7 / 2.9, 2.9 / 2.3 TB/s with wfsum (the two w streams overlap by all but one level, so the
+ * bytes that reach memory are fewer).  Against (a) mpdata_plan_level_cond_device with the same tracers, one stream fewer:
+ * cnt and wsum 2.43 x / 2.51 x its cnt; fsum 1.49 x, 1.59 x, 1.57 x / 1.52 x, 1.56 x, 1.60 x; with wfsum 1.66 x, 1.85 x, 1.92 x /
+ * 1.78 x, 2.08 x, 2.18 x.  Against (b) mpdata_plan_courant_device, the same two w streams and u: cnt and wsum 1.18 x / 1.41 x.
+ * Against (c) mpdata_plan_export_device of the T + 1 tracers, the old route, which still leaves the caller's kernel and their
+ * copy of w: fsum 0.75 x, 0.76 x, 0.75 x / 0.82 x, 0.85 x, 0.88 x; with wfsum 0.83 x, 0.88 x, 0.92 x / 0.96 x, 1.13 x, 1.20 x.  Said
+ * plainly: the call costs 1.5 x to 2.2 x a level_cond call on the same tracers -- the class is formed again in every walk and
+ * every cell pays six selected adds per value tracer with wfsum --, cnt and wsum alone cost 2.4 x level_cond's cnt, and in fp32
+ * with wfsum of three or more tracers it LOSES to the plain export of the tracers (1.13 x, 1.20 x).  4096 x 32 x 300 (6 windows;
+ * spread at most 2.9 %): cnt and wsum 0.235 / 0.180 ms; fsum 0.260, 0.534, 1.141 / 0.157, 0.351, 0.711 ms; with wfsum 0.293, 0.647,
+ * 1.416 / 0.210, 0.491, 1.065 ms; 1.44 x to 2.61 x level_cond; against the export fsum 0.81 x, 0.85 x, 0.81 x / 0.54 x, 0.62 x, 0.56 x,
+ * with wfsum 0.92 x, 1.03 x (a loss), 1.01 x (unresolved) / 0.73 x, 0.86 x, 0.84 x.  The groups of 4, 2, 1 tracers a walk against
+ * walks of one or of two at most: not measured. */
+#define MPDATA_LEVEL_DRAFT_UP 0
+#define MPDATA_LEVEL_DRAFT_DOWN 1
+#define MPDATA_LEVEL_DRAFT_ENV 2
+/* instances [sl0, sl0+n) of a resident plan; whole plan: sl0 = 0, n = ncrms.  lo, hi, cnt, wsum, fsum, wfsum: device arrays
+ * of the plan's precision on the plan's device, asynchronous on the plan's stream. */
+int mpdata_plan_level_draft_device(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const void* lo, const void* hi, double wup,
+                                   double wdn, void* cnt, void* wsum, void* fsum, void* wfsum, int first_tracer, int ntracers);
+/* host arrays, all tracers (fsum, wfsum (n, nzm, 3, ntracers of the plan)), synchronous (the plan's block staging buffer, as
+ * the 3g - 3ab host forms) */
+int mpdata_plan_level_draft(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const double* lo, const double* hi, double wup,
+                            double wdn, double* cnt, double* wsum, double* fsum, double* wfsum);
+int mpdata_plan_level_draft_f32(mpdata_plan* plan, int64_t sl0, int64_t n, int tc, const float* lo, const float* hi, double wup,
+                                double wdn, float* cnt, float* wsum, float* fsum, float* wfsum);
+/* the same on instances [sl0, sl0+n) of reference-layout DEVICE arrays f(ncrms,-2:nx+3,1,nzm,ntracers) and
+ * w(ncrms,-1:nx+2,1,nz) (leading dimension ncrms), which are only read; w is required, f only where tc >= 0, fsum or wfsum
+ * needs it; the outputs as above (leading dimension n).  Asynchronous on `stream`; 64-bit offsets. */
+int mpdata_level_draft_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const double* f, const double* w,
+                              int tc, const double* lo, const double* hi, double wup, double wdn, double* cnt, double* wsum,
+                              double* fsum, double* wfsum, int first_tracer, int ntr, void* stream);
+int mpdata_level_draft_f32_device(int64_t ncrms, int nx, int nz, int ntracers, int64_t sl0, int64_t n, const float* f, const float* w,
+                                  int tc, const float* lo, const float* hi, double wup, double wdn, float* cnt, float* wsum,
+                                  float* fsum, float* wfsum, int first_tracer, int ntr, void* stream);
+
 /* ---- 4. Synthetic inputs on the device (bench/tests; the reference's init,
  * :645-660, with a portable counter-based generator instead of the
  * compiler's random_number).  Fills `rows` x `nloc` doubles of array `sid`
