@@ -8,7 +8,10 @@
 // from the result and the kernel is compiled as before.  Each of those files still keeps its kernel whole -- the map
 // wave -> (tracer, tile, element of the column chunk), the map slot -> (instance, tall level) and its march: moving
 // the two maps into functions of this header changes the instructions of the plan-layout kernels (docs/EXPERIMENTS.md
-// N), so they stay where they are until that form has been timed.
+// N).  That form has been built and timed for the nine row kernels whose slot map is the same, relax .. level_draft
+// (docs/EXPERIMENTS.md AN): no spelling keeps the occupancy of all their kernels, and the two benches run against the
+// parent, level_hist and level_cond, miss the bar "the new side's best run does not exceed the parent's worst" in 7 of 40
+// and 8 of 44 measurements, by up to 0.3 % and 1.5 %.  So the maps stay where they are.
 //   A wave owns 64 elements of a tile's column chunk ([tile][column][instance][level], the whole 128-byte lines of every
 //   column first, the rests behind them: mpdata_layout.h) and walks the column slots as linear streams, NB columns in
 //   flight.  The walk knows the storage layout only: LPS 8 .. 64, the one-instance-per-tile forms above 64 levels
